@@ -6,7 +6,9 @@ decode + rotated NMS -> results on the host), inputs already resident in HBM.  O
 driver launches this file under torch.distributed.run and every rank runs K frames of its own (weak scaling, frames
 are independent: no data-path collective); the job's time is the max over ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps frames and
+prints the headline (`value` frames/s, `ms_per_step`); `--dump-outputs DIR` then writes the detections of the last timed frame
+as DIR/<name>.npy (float32).  `--full` adds the figures that take runs of their own:
   roofline     -- the dominant hand-written kernel of the workload against the 157.3 TFLOP/s f32 MFMA peak, from HIP events
                   on the launch stream around every launch: LC = srf_wino43_mm_k (the multiply kernel of the Winograd
                   F(4x4, 3x3) layers of the camera branch: FLOPs it executes on the MFMA = direct FLOPs / 4, direct-equivalent
@@ -16,7 +18,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                   roofline.stage = the WHOLE sparse-conv stage (all 21 launches: sum of algorithmic FLOPs and bytes over the sum
                   of their event times, against the MFMA and the HBM peak);
   cpu_baseline -- oracle/pipeline.py (the CPU port of the same path: C/OpenMP operators + torch-CPU dense layers)
-                  timed on this host, rank 0 at N=1 only.
+                  timed on this host, rank 0 at N=1 only;
+  f32_mfma_only -- LC only: the same frames timed again with SRF_GEMM_SPLIT=0 on a second model instance.
 """
 import argparse
 import json
@@ -56,6 +59,49 @@ def randomize_bn(model, seed=0):
             m.running_var.copy_(torch.rand(m.running_var.shape, generator=g) + 0.5)
 
 
+def headline(args, wl, n_points, world, elapsed, model):
+    """The result line without the --full figures (roofline, cpu_baseline, f32_mfma_only, config.gemm_route: None)."""
+    from srfdet3d_amd import graphs, nhwc, ops
+    nhwc_on = nhwc.enabled()
+    split_on = ops.gemm_split_enabled() and nhwc_on
+    total_frames = args.steps * world
+    return dict(metric=f"frames/sec, {wl['cfg']} synthetic {n_points // 1000}k-pt sweeps", value=round(total_frames / elapsed, 3),
+                unit="frames/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
+                ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling="weak",
+                vs_baseline=None, dtype="f32" if args.img_dtype == "fp32" else f"f32 (image branch {args.img_dtype})",
+                data="synthetic",
+                config=dict(workload=wl["desc"], num_proposals=args.np, points_per_frame=n_points,
+                            frames_per_rank=args.steps, hip_graph_tail=not args.eager,
+                            whole_frame_graph=bool(getattr(model, "_graphed_frame", None) is not None), img_branch_overlap=bool(args.img_overlap and model.use_img),
+                            img_features_precomputed=bool(args.img_precomputed and model.use_img),
+                            img_branch=("channels-last on srf_wino43 / srf_wino3x3 / srf_conv1x1_nhwc" if nhwc.wino43_enabled() else "channels-last on srf_wino3x3 / srf_conv1x1_nhwc") if (model.use_img and nhwc_on) else ("MIOpen" if model.use_img else None),
+                            gemm_1x1=(("f32 GEMM on the bf16 MFMA (srf_gemm_split_k): every f32 operand split EXACTLY into three bf16 values, six of "
+                                       "the nine exact partial products accumulated in f32, dropped terms < 2^-23 of a product = one f32 "
+                                       "rounding; error vs float64 equal to the f32 fma chain's (tests/test_gpu_gemm_split.py); exact for "
+                                       "finite operands with 2^-110 <= |x| <= 3.3895e38 (the bf16 maximum) and zero: smaller ones add an "
+                                       "absolute error <= 2^-126 each, larger activations / inf give NaN rows (weights of that size keep the "
+                                       "layer on the f32 MFMA); SRF_GEMM_SPLIT=0 -> f32_mfma_only") if split_on else "f32 MFMA (k-ordered fma chain)")
+                            if (model.use_img and nhwc_on) else None,
+                            gemm_route=None,
+                            graph_validation_failures=len(graphs.VALIDATION_LOG),
+                            weights="seeded random init, randomised BN statistics",
+                            parallelism=f"replica per GPU x{world}, frames sharded, no data-path collective"),
+                roofline=None, cpu_baseline=None, f32_mfma_only=None)
+
+
+def dump_outputs(result, out_dir):
+    """What a caller of the timed path receives for the last timed frame: per sample the decoded boxes (n, box_dim), their
+    scores (n,) and labels (n,), as float32 .npy files (one frame per step: <name>.npy; more samples: sample<i>_<name>.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for i, r in enumerate(result):
+        r = r.get("pts_bbox", r)
+        arrays = dict(boxes_3d=r["boxes_3d"].tensor, scores_3d=r["scores_3d"], labels_3d=r["labels_3d"])
+        for name, t in arrays.items():
+            fname = name if len(result) == 1 else f"sample{i}_{name}"
+            np.save(os.path.join(out_dir, fname + ".npy"), t.detach().cpu().to(torch.float32).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -64,9 +110,14 @@ def main():
     ap.add_argument("--workload", default="nusc_LC", choices=sorted(WORKLOADS),
                     help="default: the configuration BASELINE.json's metric is quoted on (srfdet_voxel_nusc_LC)")
     ap.add_argument("--np", type=int, default=200, help="num_proposals override (BASELINE.json: np~200)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline (per-launch HIP events, extra eager frames after the "
+                         "timed region), f32_mfma_only and cpu_baseline.  Off: only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detections of the last timed frame (rank 0) as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-f32-mfma-line", action="store_true",
-                    help="LC only: skip the second timed loop that runs the same frames with SRF_GEMM_SPLIT=0 (f32_mfma_only in the line)")
+                    help="with --full, LC only: skip the second timed loop that runs the same frames with SRF_GEMM_SPLIT=0 (f32_mfma_only in the line)")
     ap.add_argument("--eager", action="store_true", help="do not replay the static tail as a hipGraph")
     ap.add_argument("--whole-frame", default="auto", choices=["auto", "on", "off"],
                     help="replay voxelization + sparse encoder + tail as hipGraphs with capacity-padded static shapes (one graph "
@@ -103,7 +154,7 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    from srfdet3d_amd import graphs, nhwc, ops, synthetic, workloads
+    from srfdet3d_amd import nhwc, ops, synthetic, workloads
     nhwc_on = nhwc.enabled()
     from srfdet3d_amd.compat.boxes import LiDARInstance3DBoxes
 
@@ -148,6 +199,7 @@ def main():
 
     for i in range(args.warmup):
         step(i)
+    result = None
 
     def fence():
         torch.cuda.synchronize()
@@ -155,13 +207,27 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    ops.KERNEL_TIMING = {"spconv": [], "wino": [], "gemm": [], "gsplit": [], "cgemm": [], "w43x": [], "w43m": []}  # HIP-event pairs around every launch of the timed region
+    if args.full:
+        ops.KERNEL_TIMING = {"spconv": [], "wino": [], "gemm": [], "gsplit": [], "cgemm": [], "w43x": [], "w43m": []}  # HIP-event pairs around every launch of the timed region
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        result = step(args.warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = t.item()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(result, args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, wl, n_points, world, elapsed, model)))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     records = ops.KERNEL_TIMING["spconv"]
     roofline_source = "HIP events on the launch stream around every launch of the timed region"
     gf = getattr(model, "_graphed_frame", None)
@@ -195,10 +261,6 @@ def main():
     w43x_rec, w43m_rec = ops.KERNEL_TIMING["w43x"], ops.KERNEL_TIMING["w43m"]
     cgemm_rec = ops.KERNEL_TIMING["cgemm"]
     ops.KERNEL_TIMING = None
-    if world > 1:
-        t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = t.item()
 
     if rank == 0:
         def _source_id():
@@ -430,29 +492,9 @@ def main():
                                 sample=f"median of {len(times)} frame(s) after 1 warm-up frame of the same workload through "
                                        f"oracle/pipeline.py (C/OpenMP operators + torch-CPU dense layers); frames took "
                                        + ", ".join(f"{t:.2f}" for t in times) + " s")
-        total_frames = args.steps * world
-        out = dict(metric=f"frames/sec, {wl['cfg']} synthetic {n_points // 1000}k-pt sweeps", value=round(total_frames / elapsed, 3),
-                   unit="frames/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
-                   ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling="weak",
-                   vs_baseline=None, dtype="f32" if args.img_dtype == "fp32" else f"f32 (image branch {args.img_dtype})",
-                   data="synthetic",
-                   config=dict(workload=wl["desc"], num_proposals=args.np, points_per_frame=n_points,
-                               frames_per_rank=args.steps, hip_graph_tail=not args.eager,
-                               whole_frame_graph=bool(getattr(model, "_graphed_frame", None) is not None), img_branch_overlap=bool(args.img_overlap and model.use_img),
-                               img_features_precomputed=bool(args.img_precomputed and model.use_img),
-                               img_branch=("channels-last on srf_wino43 / srf_wino3x3 / srf_conv1x1_nhwc" if nhwc.wino43_enabled() else "channels-last on srf_wino3x3 / srf_conv1x1_nhwc") if (model.use_img and nhwc_on) else ("MIOpen" if model.use_img else None),
-                               gemm_1x1=(("f32 GEMM on the bf16 MFMA (srf_gemm_split_k): every f32 operand split EXACTLY into three bf16 values, six of "
-                                          "the nine exact partial products accumulated in f32, dropped terms < 2^-23 of a product = one f32 "
-                                          "rounding; error vs float64 equal to the f32 fma chain's (tests/test_gpu_gemm_split.py); exact for "
-                                          "finite operands with 2^-110 <= |x| <= 3.3895e38 (the bf16 maximum) and zero: smaller ones add an "
-                                          "absolute error <= 2^-126 each, larger activations / inf give NaN rows (weights of that size keep the "
-                                          "layer on the f32 MFMA); SRF_GEMM_SPLIT=0 -> f32_mfma_only") if split_on else "f32 MFMA (k-ordered fma chain)")
-                               if (model.use_img and nhwc_on) else None,
-                               gemm_route=gemm_route,
-                               graph_validation_failures=len(graphs.VALIDATION_LOG),
-                               weights="seeded random init, randomised BN statistics",
-                               parallelism=f"replica per GPU x{world}, frames sharded, no data-path collective"),
-                   roofline=roofline, cpu_baseline=cpu_baseline, f32_mfma_only=f32_mfma_only)
+        out = headline(args, wl, n_points, world, elapsed, model)
+        out["config"]["gemm_route"] = gemm_route
+        out.update(roofline=roofline, cpu_baseline=cpu_baseline, f32_mfma_only=f32_mfma_only)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

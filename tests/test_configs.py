@@ -10,7 +10,9 @@ import srfdet3d_amd as S
 from srfdet3d_amd import workloads
 from srfdet3d_amd.compat.config import Config
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_configs.json")
+with open(GOLDEN) as _f:
+    REF_CFGS = json.load(_f)   # the reference's config files as Config.fromfile evaluates them (tests/golden/make_config_fixture.py)
 NAMES = {"srfdet_voxel_nusc_L": "configs/nus/srfdet_voxel_nusc_L.py", "srfdet_voxel_nusc_LC": "configs/nus/srfdet_voxel_nusc_LC.py",
          "srfdet_voxel_kitti_L": "configs/kitti/srfdet_voxel_kitti_L.py", "srfdet_dvoxel_waymo_L": "configs/waymo/srfdet_dvoxel_waymo_L.py",
          "srfdet_pillar_nusc_L": "configs/nus/srfdet_pillar_nusc_L.py", "srfdet_voxel_kitti_LC": "configs/kitti/srfdet_voxel_kitti_LC.py",
@@ -28,12 +30,30 @@ def _plain(o):
     return o
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", sorted(NAMES))
 def test_workload_json_equals_live_reference_config(name):
-    cfg = Config.fromfile(os.path.join(REF, NAMES[name]))
-    assert cfg.plugin is True and cfg.plugin_dir == "mmdet3d_plugin"
-    assert _plain(cfg.model) == _plain(workloads.model_cfg(name))
+    ref = REF_CFGS[name]
+    assert ref["source"] == NAMES[name]
+    assert ref["plugin"] is True and ref["plugin_dir"] == "mmdet3d_plugin"
+    assert _plain(workloads._untuple(ref["model"])) == _plain(workloads.model_cfg(name))
+
+
+def test_config_fromfile_reads_python_config(tmp_path):
+    """Config.fromfile on a config written the way the reference's are: module-level dicts / lists / tuples, helper
+    variables, an imported module (dropped), attribute access on nested dicts."""
+    f = tmp_path / "cfg.py"
+    f.write_text("import os\n"
+                 "point_cloud_range = [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0]\n"
+                 "voxel_size = [0.075, 0.075, 0.2]\n"
+                 "plugin = True\n"
+                 "plugin_dir = 'mmdet3d_plugin'\n"
+                 "model = dict(type='SRFDet', pts_voxel_layer=dict(max_num_points=10, voxel_size=voxel_size,\n"
+                 "             point_cloud_range=point_cloud_range, max_voxels=(120000, 160000)))\n")
+    cfg = Config.fromfile(str(f))
+    assert cfg.plugin is True and cfg.plugin_dir == "mmdet3d_plugin" and "os" not in cfg
+    assert cfg.model.pts_voxel_layer.max_voxels == (120000, 160000)
+    assert cfg.model.pts_voxel_layer.point_cloud_range == [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0]
+    assert cfg.filename == str(f)
 
 
 def test_cfg_options_override():

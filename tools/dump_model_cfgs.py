@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Evaluate the unchanged reference config files and store their `model` dicts (values only) as JSON under
 srfdet3d_amd/workloads/, so that bench.py and the GPU tests -- which run where /root/reference does not exist --
-build exactly the models the reference configs describe.  tests/test_configs.py re-evaluates the configs whenever
-the reference is present and fails if a JSON has drifted.
+build exactly the models the reference configs describe.  tests/test_configs.py compares every JSON with
+tests/golden/reference_configs.json (written by tests/golden/make_config_fixture.py) and fails if one has drifted.
 
 usage: python tools/dump_model_cfgs.py [--ref /root/reference]
 """
