@@ -226,8 +226,15 @@ int srf_spconv_bwd_weight(const float *in, int A_in, int Cin, const float *grad_
                           int nbr_stride, int K, float *grad_W, srf_stream_t stream);
 
 /* Fast path of K5 for constant weights: re-lay W once (srf_spconv_pack_weights -> packed, of
- * srf_spconv_packed_weight_bytes bytes) into the LDS operand image of the kernel, then call srf_spconv_fwd_packed with
- * the same remaining arguments.  Results are bit-identical to srf_spconv_fwd.  Cout in {32, 64, 128}, Cin % 4 == 0. */
+ * srf_spconv_packed_weight_bytes bytes) into the operand layout of the kernel, then call srf_spconv_fwd_packed with
+ * the same remaining arguments.  Results are bit-identical to srf_spconv_fwd.  The shapes with a packed form:
+ *   Cin -> Cout        K
+ *   16 / 32 -> 32      27
+ *   32 / 64 -> 64      any
+ *   64 / 128 -> 128    any
+ * srf_spconv_packed_weight_bytes returns 0 for every other shape (no packed form: use srf_spconv_fwd); there
+ * srf_spconv_pack_weights and srf_spconv_fwd_packed return SRF_EUNSUPPORTED.  srf_spconv_fwd_packed also returns
+ * SRF_EUNSUPPORTED for an input of 2 GiB or more (A_in * Cin * 4 >= 2^31) or with no rows (A_in == 0). */
 size_t srf_spconv_packed_weight_bytes(int K, int Cin, int Cout);
 int srf_spconv_pack_weights(const float *W, int K, int Cin, int Cout, float *packed, srf_stream_t stream);
 int srf_spconv_fwd_packed(const float *in, int A_in, int Cin, const float *W_packed, int K, const int *nbr,

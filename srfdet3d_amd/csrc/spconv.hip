@@ -270,79 +270,24 @@ __global__ __launch_bounds__(256) void srf_spconv_mfma32_k(const float *__restri
 }
 
 // =====================================================================================================================
-// Packed-weight kernel (the fast path; weights are constants at inference, so they are re-laid-out once per layer).
-//
-// Operand images in LDS are built so that a lane fetches its 16 k-values of a 32-channel chunk with four ds_read_b128:
-//   row of the image = one gathered input row (A) or one output column (B), 32 floats = 8 slots of 16 B;
-//   logical slot s = 4*h + g holds channels c0 + 2*(4g + i) + h, i = 0..3  (h = parity of the channel: the f32 32x32x2
-//   MFMA takes channel 2j from lanes 0-31 and 2j+1 from lanes 32-63);
-//   physical slot = s ^ ((row >> 1) & 7): with 128-B rows this XOR swizzle puts the 16 lanes of every ds_read_b128
-//   lane group on 16 different (half, slot) pairs, i.e. conflict-free without padding (48 KB per workgroup -> three
-//   workgroups per CU).
-// srf_spconv_pack_weights writes W in exactly that image, per (offset k, chunk), so the slab copy global -> LDS is
-// linear.  The accumulation order per output element is unchanged (k ascending, channel ascending): results stay
-// bit-identical to srf_spconv_fwd and to the oracle.
+// Packed weights (inference: the weights are constants, so they are re-laid-out once per layer).  A layer shape has at most
+// one packed layout, and srf_spconv_fwd_packed runs one kernel on it:
+//   w32: K = 27, Cout = 32, Cin in {16, 32}                     -> srf_spconv_w32_k (srf_pack_weights_w32_k)
+//   gs:  Cout = 64, Cin in {32, 64}; Cout = 128, Cin in {64, 128}; any K -> srf_spconv_gsp_k (srf_pack_weights_gs_k)
+// Every other shape has none (srf_spconv_packed_weight_bytes = 0) and runs on srf_spconv_fwd, which gives the same bits.
 // =====================================================================================================================
-// direct (LDS-free B operand) layout of the COUT = 128 kernel, see srf_spconv_direct_k below
-static bool srf_direct64_enabled()
+enum SrfPackedLayout { SRF_PACKED_NONE, SRF_PACKED_W32, SRF_PACKED_GS };
+static SrfPackedLayout srf_packed_layout(int K, int Cin, int Cout)
 {
-    static const bool on = [] {
-        const char *e = getenv("SRF_SPCONV_PACKED64");  // developer switch: the LDS-staged kernel for 64 -> 64, for A/B timing
-        return !(e && e[0] == '1');
-    }();
-    return on;
+    if (K <= 0 || K > SRF_KMAX) return SRF_PACKED_NONE;
+    if (K == SRF_KMAX && Cout == 32 && (Cin == 16 || Cin == 32)) return SRF_PACKED_W32;
+    if ((Cout == 64 && (Cin == 32 || Cin == 64)) || (Cout == 128 && (Cin == 64 || Cin == 128))) return SRF_PACKED_GS;
+    return SRF_PACKED_NONE;
 }
-static bool srf_direct_layout(int Cin, int Cout)
-{
-    return (Cout == 128 && (Cin == 64 || Cin == 128)) || (Cout == 64 && Cin == 64 && srf_direct64_enabled());
-}
-// compacted-offset layout of the same shapes (srf_spconv_gs_k below), the default
-static bool srf_gs_layout(int Cin, int Cout);
+
 __global__ void srf_pack_weights_gs_k(const float *__restrict__ W, int K, int Cin, int Cout, int nchunk, float *__restrict__ P);
 
-__global__ __launch_bounds__(256) void srf_pack_weights_direct_k(const float *__restrict__ W, int K, int Cin, int Cout,
-                                                               int nchunk, float *__restrict__ P)
-{
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long total = (long long)K * nchunk * Cout * 32;
-    if (t >= total) return;
-    const int nwc = Cout / 32;  // 32-column slices: 4 (COUT = 128) or 2 (COUT = 64)
-    const int i = (int)(t & 3), lane = (int)((t >> 2) & 63), g = (int)((t >> 8) & 3);
-    long long rest = t >> 10;
-    const int wc = (int)(rest % nwc);
-    rest /= nwc;
-    const int chunk = (int)(rest % nchunk), k = (int)(rest / nchunk);
-    const int col = wc * 32 + (lane & 31);
-    const int c = chunk * 32 + 2 * (4 * g + i) + (lane >> 5);
-    P[t] = c < Cin ? W[((size_t)k * Cin + c) * Cout + col] : 0.0f;
-}
-
-__global__ __launch_bounds__(256) void srf_pack_weights_k(const float *__restrict__ W, int K, int Cin, int Cout, int nchunk,
-                                                        float *__restrict__ P)
-{
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long total = (long long)K * nchunk * Cout * 32;
-    if (t >= total) return;
-    const int e = (int)(t & 31);
-    long long rest = t >> 5;
-    const int col = (int)(rest % Cout);
-    rest /= Cout;
-    const int chunk = (int)(rest % nchunk), k = (int)(rest / nchunk);
-    const int phys = e >> 2, i = e & 3;
-    const int sl = phys ^ ((col >> 1) & 7);
-    const int c = chunk * 32 + 2 * ((sl & 3) * 4 + i) + (sl >> 2);
-    P[t] = c < Cin ? W[((size_t)k * Cin + c) * Cout + col] : 0.0f;
-}
-
 // wave-private layout of the 32-output-channel layers (srf_spconv_w32_k below): [k][group of 4 steps][channel parity][col 32][4]
-static bool srf_w32_layout(int K, int Cin, int Cout)
-{
-    static const bool off = [] {
-        const char *e = getenv("SRF_SPCONV_W32");  // developer switch: 0 = the LDS-staged tile kernel, for A/B timing
-        return e && e[0] == '0';
-    }();
-    return !off && K == SRF_KMAX && Cout == 32 && (Cin == 16 || Cin == 32);
-}
 
 __global__ __launch_bounds__(256) void srf_pack_weights_w32_k(const float *__restrict__ W, int K, int Cin, float *__restrict__ P)
 {
@@ -359,490 +304,29 @@ __global__ __launch_bounds__(256) void srf_pack_weights_w32_k(const float *__res
 
 extern "C" size_t srf_spconv_packed_weight_bytes(int K, int Cin, int Cout)
 {
-    if (K <= 0 || Cin <= 0 || Cout <= 0) return 0;
+    if (srf_packed_layout(K, Cin, Cout) == SRF_PACKED_NONE) return 0;
     return (size_t)K * ((Cin + 31) / 32) * Cout * 32 * sizeof(float);
 }
 
 extern "C" int srf_spconv_pack_weights(const float *W, int K, int Cin, int Cout, float *packed, srf_stream_t stream)
 {
     if (!W || !packed || K <= 0 || K > SRF_KMAX || Cin <= 0 || Cout <= 0) return SRF_EINVAL;
-    const int nchunk = (Cin + 31) / 32;
-    const long long total = (long long)K * nchunk * Cout * 32;
-    if (srf_w32_layout(K, Cin, Cout))
+    const SrfPackedLayout layout = srf_packed_layout(K, Cin, Cout);
+    if (layout == SRF_PACKED_NONE) return SRF_EUNSUPPORTED;
+    if (layout == SRF_PACKED_W32) {
         hipLaunchKernelGGL(srf_pack_weights_w32_k, dim3(srf_ceil_div((long long)K * Cin * 32, 256)), dim3(256), 0, (hipStream_t)stream, W, K,
                            Cin, packed);
-    else if (srf_gs_layout(Cin, Cout))
-        hipLaunchKernelGGL(srf_pack_weights_gs_k, dim3(srf_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, W, K, Cin,
-                           Cout, nchunk, packed);
-    else if (srf_direct_layout(Cin, Cout))
-        hipLaunchKernelGGL(srf_pack_weights_direct_k, dim3(srf_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, W, K,
-                           Cin, Cout, nchunk, packed);
-    else
-        hipLaunchKernelGGL(srf_pack_weights_k, dim3(srf_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, W, K, Cin, Cout,
-                           nchunk, packed);
+    } else {
+        const int nchunk = (Cin + 31) / 32;
+        hipLaunchKernelGGL(srf_pack_weights_gs_k, dim3(srf_ceil_div((long long)K * nchunk * Cout * 32, 256)), dim3(256), 0, (hipStream_t)stream,
+                           W, K, Cin, Cout, nchunk, packed);
+    }
     SRF_LAUNCH_CHECK();
     return SRF_OK;
 }
 
-template <int COUT, int TM, int NA, int NW>
-__device__ __forceinline__ void srf_pk_load(const float *__restrict__ in, int Cin, const float *__restrict__ slab,
-                                            const int *nbr_k, int rows_left, int c0, f32x4 (&ra)[NA], f32x4 (&rw)[NW],
-                                            unsigned &okmask)
-{
-    const int tid = threadIdx.x;
-    unsigned m = 0;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int e = tid + j * 256;
-        const int r = e >> 3, q = e & 7;
-        const int i = r < rows_left ? nbr_k[r] : -1;
-        const int c = c0 + q * 4;
-        const bool ok = (i >= 0) & (c < Cin);
-        const int ii = i >= 0 ? i : 0;
-        const int cc = c < Cin ? c : Cin - 4;
-        ra[j] = *reinterpret_cast<const f32x4 *>(in + (size_t)ii * Cin + cc);
-        m |= (ok ? 1u : 0u) << j;
-    }
-#pragma unroll
-    for (int j = 0; j < NW; ++j) rw[j] = *reinterpret_cast<const f32x4 *>(slab + (size_t)(tid + j * 256) * 4);
-    okmask = m;
-}
-
-template <int COUT, int TM, int NA, int NW>
-__device__ __forceinline__ void srf_pk_store(float *s_a, float *s_w, const f32x4 (&ra)[NA], const f32x4 (&rw)[NW],
-                                             unsigned okmask)
-{
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const int tid = threadIdx.x;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int e = tid + j * 256;
-        const int r = e >> 3, q = e & 7;
-        const f32x4 v = ((okmask >> j) & 1u) ? ra[j] : zero;
-        const int swz = (r >> 1) & 7;
-        const int off = 2 * (q & 1);
-        const f32x2 ev = {v[0], v[2]}, od = {v[1], v[3]};
-        *reinterpret_cast<f32x2 *>(s_a + r * 32 + (((q >> 1)) ^ swz) * 4 + off) = ev;
-        *reinterpret_cast<f32x2 *>(s_a + r * 32 + ((4 + (q >> 1)) ^ swz) * 4 + off) = od;
-    }
-#pragma unroll
-    for (int j = 0; j < NW; ++j) *reinterpret_cast<f32x4 *>(s_w + (size_t)(tid + j * 256) * 4) = rw[j];
-}
-
-template <int COUT, int TM, int WR, int WC>
-__global__ __launch_bounds__(256) void srf_spconv_packed_k(const float *__restrict__ in, int Cin,
-                                                         const float *__restrict__ Wp, int K,
-                                                         const int *__restrict__ nbr, int nbr_stride, int A_out,
-                                                         const float *__restrict__ alpha, const float *__restrict__ beta,
-                                                         const float *__restrict__ residual, int relu,
-                                                         float *__restrict__ out, const int *__restrict__ rows_dev)
-{
-    static_assert(WR * WC == 4 && TM == WR * 32, "one 32-row tile per wave row");
-    constexpr int CT = COUT / WC / 32;
-    constexpr int NA = TM * 8 / 256;
-    constexpr int NW = COUT * 8 / 256;
-    constexpr bool NBR_LDS = COUT < 128;
-    __shared__ int s_nbr[NBR_LDS ? SRF_KMAX * TM : 1];
-    __shared__ int s_any[SRF_KMAX];
-    __shared__ int s_klist[SRF_KMAX + 1];
-    __shared__ __attribute__((aligned(16))) float s_a[2][TM * 32];
-    __shared__ __attribute__((aligned(16))) float s_w[2][COUT * 32];
-
-    if (rows_dev) {  // static-shape levels: rows >= *rows_dev are padding; their tiles do nothing
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
-    // tiles of LIVE rows only, dealt XCD-contiguously over the first n_tiles workgroups (a capacity-sized launch must not
-    // leave whole XCDs with nothing but padding)
-    const int n_tiles = (A_out + TM - 1) / TM;
-    if ((int)blockIdx.x >= n_tiles) return;
-    const int row0 = srf_xcd_tile(blockIdx.x, n_tiles) * TM;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave / WC, wc = wave % WC;
-    const int rows_left = A_out - row0;
-    if (tid < SRF_KMAX) s_any[tid] = 0;
-    __syncthreads();
-    for (int t = tid; t < K * TM; t += 256) {
-        const int k = t / TM, r = t % TM;
-        const int v = r < rows_left ? nbr[(size_t)k * nbr_stride + row0 + r] : -1;
-        if (NBR_LDS) s_nbr[t] = v;
-        if (v >= 0) s_any[k] = 1;  // benign race: every writer stores 1
-    }
-    __syncthreads();
-    if (tid < 64) {  // compact the used offsets with one ballot (K <= 27 < 64) instead of a serial loop on one lane
-        const bool used = tid < K && s_any[tid];
-        const unsigned long long m = __ballot(used);
-        if (used) s_klist[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-        if (tid == 0) s_klist[SRF_KMAX] = __popcll(m);
-    }
-    __syncthreads();
-    const int nchunk = (Cin + SRF_KC - 1) / SRF_KC;
-    const int T = s_klist[SRF_KMAX] * nchunk;
-    const size_t slab_floats = (size_t)COUT * 32;
-
-    f32x16 acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[ct][j] = 0.0f;
-
-    f32x4 ra[NA], rw[NW];
-    unsigned okmask = 0;
-    const int kh = lane >> 5;
-    const int arow = wr * 32 + (lane & 31);
-    const int a_swz = (arow >> 1) & 7;
-    if (T > 0) {
-        const int k0 = s_klist[0];
-        srf_pk_load<COUT, TM, NA, NW>(in, Cin, Wp + (size_t)k0 * nchunk * slab_floats,
-                                      NBR_LDS ? s_nbr + k0 * TM : nbr + (size_t)k0 * nbr_stride + row0,
-                                      NBR_LDS ? TM : rows_left, 0, ra, rw, okmask);
-        srf_pk_store<COUT, TM, NA, NW>(s_a[0], s_w[0], ra, rw, okmask);
-    }
-    __syncthreads();
-    int tk = 0, tc = 0;
-    for (int t = 0; t < T; ++t) {
-        const int buf = t & 1;
-        if (++tc == nchunk) {
-            tc = 0;
-            ++tk;
-        }
-        const bool more = t + 1 < T;
-        if (more) {
-            const int kn = s_klist[tk];
-            srf_pk_load<COUT, TM, NA, NW>(in, Cin, Wp + ((size_t)kn * nchunk + tc) * slab_floats,
-                                          NBR_LDS ? s_nbr + kn * TM : nbr + (size_t)kn * nbr_stride + row0,
-                                          NBR_LDS ? TM : rows_left, tc * SRF_KC, ra, rw, okmask);
-        }
-        // operand fragments of this step: 4 + 4*CT ds_read_b128, then the MFMAs run without further LDS waits
-        f32x4 af[4], bf[CT][4];
-        const float *pa = s_a[buf] + arow * 32;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) af[g] = *reinterpret_cast<const f32x4 *>(pa + (((kh << 2) + g) ^ a_swz) * 4);
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const int col = (wc * CT + ct) * 32 + (lane & 31);
-            const float *pb = s_w[buf] + col * 32;
-            const int b_swz = (col >> 1) & 7;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) bf[ct][g] = *reinterpret_cast<const f32x4 *>(pb + (((kh << 2) + g) ^ b_swz) * 4);
-        }
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[j >> 2][j & 3], bf[ct][j >> 2][j & 3], acc[ct], 0, 0, 0);
-        if (more) srf_pk_store<COUT, TM, NA, NW>(s_a[buf ^ 1], s_w[buf ^ 1], ra, rw, okmask);
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const int col = (wc * CT + ct) * 32 + (lane & 31);
-        const float al = alpha ? alpha[col] : 1.0f;
-        const float be = alpha ? beta[col] : 0.0f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int row = row0 + wr * 32 + (j & 3) + 8 * (j >> 2) + 4 * kh;
-            if (row < A_out) {
-                float v = acc[ct][j];
-                if (alpha) v = __fmaf_rn(v, al, be);
-                if (residual) v = __fadd_rn(v, residual[(size_t)row * COUT + col]);
-                if (relu) v = v > 0.0f ? v : 0.0f;
-                out[(size_t)row * COUT + col] = v;
-            }
-        }
-    }
-}
-
-// =====================================================================================================================
-// COUT = 128, Cin in {64, 128}: the B operand never touches LDS.  Weights are packed so that every lane finds the 16
-// values it feeds to the 16 MFMAs of a 32-channel chunk as four consecutive float4 (one coalesced 1 KB load per wave
-// and group), and are fetched global(L2) -> registers one chunk ahead by the wave that uses them: no slab copy, no LDS
-// traffic for B and one barrier per kernel offset (64 MFMAs per wave and row tile) instead of one per chunk.  LDS holds
-// only the gathered input rows of one offset (double buffered) and the neighbour tile.  Same accumulation order as every
-// other kernel here (offset ascending, channel ascending): bit-identical results.
-//   direct layout: Wd[k][chunk][wc = col/32][g][lane][i] = W[k][chunk*32 + 2*(4g+i) + (lane>>5)][wc*32 + (lane&31)]
-// =====================================================================================================================
-template <int NCH, int NWC = 4>
-__device__ __forceinline__ void srf_dir_load_b(f32x4 (&b)[4], const float *__restrict__ Wd, int k, int chunk, int wc, int lane)
-{
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-        b[g] = *reinterpret_cast<const f32x4 *>(Wd + (((((size_t)k * NCH + chunk) * NWC + wc) * 4 + g) * 64 + lane) * 4);
-}
-
-template <int TM, int NCH, int NA>
-__device__ __forceinline__ void srf_dir_gather(const float *__restrict__ in, const int *s_nbr_k, f32x4 (&ra)[NA], unsigned &okmask)
-{
-    const int tid = threadIdx.x;
-    unsigned m = 0;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int e = tid + j * 256;
-        const int r = e / (8 * NCH), q = e % (8 * NCH);
-        const int i = s_nbr_k[r];
-        ra[j] = *reinterpret_cast<const f32x4 *>(in + (size_t)(i >= 0 ? i : 0) * (32 * NCH) + q * 4);
-        m |= (i >= 0 ? 1u : 0u) << j;
-    }
-    okmask = m;
-}
-
-template <int TM, int NCH, int NA>
-__device__ __forceinline__ void srf_dir_store(float *s_a, const f32x4 (&ra)[NA], unsigned okmask)
-{
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const int tid = threadIdx.x;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int e = tid + j * 256;
-        const int r = e / (8 * NCH), qq = e % (8 * NCH);
-        const int ch = qq >> 3, q = qq & 7;
-        const f32x4 v = ((okmask >> j) & 1u) ? ra[j] : zero;
-        const int swz = (r >> 1) & 7;
-        const int off = 2 * (q & 1);
-        const f32x2 ev = {v[0], v[2]}, od = {v[1], v[3]};
-        float *img = s_a + ch * (TM * 32) + r * 32;
-        *reinterpret_cast<f32x2 *>(img + ((q >> 1) ^ swz) * 4 + off) = ev;
-        *reinterpret_cast<f32x2 *>(img + ((4 + (q >> 1)) ^ swz) * 4 + off) = od;
-    }
-}
-
-template <int TM, int NCH, int NBUF>
-__global__ __launch_bounds__(256) void srf_spconv_direct_k(const float *__restrict__ in, const float *__restrict__ Wd, int K,
-                                                         const int *__restrict__ nbr, int nbr_stride, int A_out,
-                                                         const float *__restrict__ alpha, const float *__restrict__ beta,
-                                                         const float *__restrict__ residual, int relu,
-                                                         float *__restrict__ out, const int *__restrict__ rows_dev)
-{
-    constexpr int COUT = 128, RT = TM / 32, NA = TM * 8 * NCH / 256;
-    __shared__ int s_nbr[SRF_KMAX * TM];
-    __shared__ int s_any[SRF_KMAX];
-    __shared__ int s_klist[SRF_KMAX + 1];
-    __shared__ __attribute__((aligned(16))) float s_a[NBUF][NCH * TM * 32];
-
-    if (rows_dev) {  // static-shape levels: rows >= *rows_dev are padding; their tiles do nothing
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
-    // tiles of LIVE rows only, dealt XCD-contiguously over the first n_tiles workgroups (a capacity-sized launch must not
-    // leave whole XCDs with nothing but padding)
-    const int n_tiles = (A_out + TM - 1) / TM;
-    if ((int)blockIdx.x >= n_tiles) return;
-    const int row0 = srf_xcd_tile(blockIdx.x, n_tiles) * TM;
-    const int tid = threadIdx.x, lane = tid & 63, wc = tid >> 6;
-    srf_load_nbr_tile<TM>(nbr, nbr_stride, K, row0, A_out, s_nbr, s_any);
-    if (tid < 64) {  // compact the used offsets with one ballot (K <= 27 < 64) instead of a serial loop on one lane
-        const bool used = tid < K && s_any[tid];
-        const unsigned long long m = __ballot(used);
-        if (used) s_klist[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-        if (tid == 0) s_klist[SRF_KMAX] = __popcll(m);
-    }
-    __syncthreads();
-    const int ntap = s_klist[SRF_KMAX];
-
-    f32x16 acc[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[rt][j] = 0.0f;
-
-    const int kh = lane >> 5;
-    // B fragments are fetched PD chunks ahead into one register slot per chunk position (PD = 2 for the 4-chunk layers:
-    // a weight line that was evicted from L2 by the gathers takes longer than one chunk of MFMAs to arrive)
-    constexpr int PD = NCH >= 4 ? 2 : 1, NS = NCH >= 4 ? NCH : 2;
-    f32x4 ra[NA], bq[NS][4];
-    unsigned okmask = 0;
-    if (ntap > 0) {
-        const int k0 = s_klist[0];
-        srf_dir_load_b<NCH>(bq[0], Wd, k0, 0, wc, lane);
-        if (PD == 2) srf_dir_load_b<NCH>(bq[1], Wd, k0, 1, wc, lane);
-        srf_dir_gather<TM, NCH, NA>(in, s_nbr + k0 * TM, ra, okmask);
-        srf_dir_store<TM, NCH, NA>(s_a[0], ra, okmask);
-    }
-    __syncthreads();
-    for (int tk = 0; tk < ntap; ++tk) {
-        const int buf = NBUF == 2 ? (tk & 1) : 0;
-        const int kc = s_klist[tk];
-        const bool more = tk + 1 < ntap;
-        const int kn = more ? s_klist[tk + 1] : kc;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            // B fragments of the next chunk (of this offset or the first of the next one); NCH is even, so the
-            // register pair alternates consistently across offsets
-            if (PD == 2) {
-                if (c + 2 < NCH) srf_dir_load_b<NCH>(bq[c + 2], Wd, kc, c + 2, wc, lane);
-                else srf_dir_load_b<NCH>(bq[c + 2 - NCH], Wd, kn, c + 2 - NCH, wc, lane);  // harmless re-read on the last offset
-            } else {
-                if (c + 1 < NCH) srf_dir_load_b<NCH>(bq[(c + 1) & 1], Wd, kc, c + 1, wc, lane);
-                else srf_dir_load_b<NCH>(bq[(c + 1) & 1], Wd, kn, 0, wc, lane);
-            }
-            // the gather of the next offset goes out AFTER the last B load this offset still has to wait for: vmcnt
-            // retires in order, so an earlier gather (an L2 miss more often than not) would be waited for at every
-            // chunk; here it has two chunks of MFMAs to land and only the LDS store below waits for it
-            if (c == NCH - 2 && more) srf_dir_gather<TM, NCH, NA>(in, s_nbr + kn * TM, ra, okmask);
-            f32x4 af[RT][4];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                const int arow = rt * 32 + (lane & 31);
-                const float *pa = s_a[buf] + c * (TM * 32) + arow * 32;
-                const int a_swz = (arow >> 1) & 7;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) af[rt][g] = *reinterpret_cast<const f32x4 *>(pa + (((kh << 2) + g) ^ a_swz) * 4);
-            }
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[rt][j >> 2][j & 3], bq[PD == 2 ? c : (c & 1)][j >> 2][j & 3], acc[rt], 0, 0, 0);
-        }
-        if (NBUF == 1) __syncthreads();  // single buffer: every wave is done reading before the rows are replaced
-        if (more) srf_dir_store<TM, NCH, NA>(s_a[NBUF == 2 ? (buf ^ 1) : 0], ra, okmask);
-        __syncthreads();
-    }
-
-    const int col = wc * 32 + (lane & 31);
-    const float al = alpha ? alpha[col] : 1.0f;
-    const float be = alpha ? beta[col] : 0.0f;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int row = row0 + rt * 32 + (j & 3) + 8 * (j >> 2) + 4 * kh;
-            if (row < A_out) {
-                float v = acc[rt][j];
-                if (alpha) v = __fmaf_rn(v, al, be);
-                if (residual) v = __fadd_rn(v, residual[(size_t)row * COUT + col]);
-                if (relu) v = v > 0.0f ? v : 0.0f;
-                out[(size_t)row * COUT + col] = v;
-            }
-        }
-}
-
-// COUT = 64, Cin = 64 with the same LDS-free B operand: 64-row tiles, waves = 2 row halves x 2 column halves, each a
-// 32 x 32 accumulator.  Against srf_spconv_packed_k<64, 64, 2, 2> (weight slab through LDS, a barrier per 32-channel chunk =
-// per 16 MFMAs) there is one barrier per kernel offset (32 MFMAs per wave) and half the LDS traffic.
-template <int NCH>
-__global__ __launch_bounds__(256) void srf_spconv_direct64_k(const float *__restrict__ in, const float *__restrict__ Wd, int K,
-                                                           const int *__restrict__ nbr, int nbr_stride, int A_out,
-                                                           const float *__restrict__ alpha, const float *__restrict__ beta,
-                                                           const float *__restrict__ residual, int relu,
-                                                           float *__restrict__ out, const int *__restrict__ rows_dev)
-{
-    constexpr int COUT = 64, TM = 64, NA = TM * 8 * NCH / 256;
-    static_assert(NCH == 2, "register slots below alternate over two chunks");
-    __shared__ int s_nbr[SRF_KMAX * TM];
-    __shared__ int s_any[SRF_KMAX];
-    __shared__ int s_klist[SRF_KMAX + 1];
-    __shared__ __attribute__((aligned(16))) float s_a[2][NCH * TM * 32];
-
-    if (rows_dev) {  // static-shape levels: rows >= *rows_dev are padding; their tiles do nothing
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
-    const int n_tiles = (A_out + TM - 1) / TM;
-    if ((int)blockIdx.x >= n_tiles) return;
-    const int row0 = srf_xcd_tile(blockIdx.x, n_tiles) * TM;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wc = wave & 1, wr = wave >> 1;
-    srf_load_nbr_tile<TM>(nbr, nbr_stride, K, row0, A_out, s_nbr, s_any);
-    if (tid < 64) {
-        const bool used = tid < K && s_any[tid];
-        const unsigned long long m = __ballot(used);
-        if (used) s_klist[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-        if (tid == 0) s_klist[SRF_KMAX] = __popcll(m);
-    }
-    __syncthreads();
-    const int ntap = s_klist[SRF_KMAX];
-
-    f32x16 acc;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-    const int kh = lane >> 5;
-    f32x4 ra[NA], bq[2][4];
-    unsigned okmask = 0;
-    if (ntap > 0) {
-        const int k0 = s_klist[0];
-        srf_dir_load_b<NCH, 2>(bq[0], Wd, k0, 0, wc, lane);
-        srf_dir_gather<TM, NCH, NA>(in, s_nbr + k0 * TM, ra, okmask);
-        srf_dir_store<TM, NCH, NA>(s_a[0], ra, okmask);
-    }
-    __syncthreads();
-    const int arow = wr * 32 + (lane & 31);
-    const int a_swz = (arow >> 1) & 7;
-    for (int tk = 0; tk < ntap; ++tk) {
-        const int buf = tk & 1;
-        const int kc = s_klist[tk];
-        const bool more = tk + 1 < ntap;
-        const int kn = more ? s_klist[tk + 1] : kc;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            // B fragments of the next chunk (of this offset, or the first of the next one) into the other register slot
-            if (c + 1 < NCH) srf_dir_load_b<NCH, 2>(bq[(c + 1) & 1], Wd, kc, c + 1, wc, lane);
-            else srf_dir_load_b<NCH, 2>(bq[(c + 1) & 1], Wd, kn, 0, wc, lane);  // harmless re-read on the last offset
-            // the gather of the next offset goes out after the B load this chunk still waits for (vmcnt retires in order)
-            if (c == NCH - 2 && more) srf_dir_gather<TM, NCH, NA>(in, s_nbr + kn * TM, ra, okmask);
-            f32x4 af[4];
-            const float *pa = s_a[buf] + c * (TM * 32) + arow * 32;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) af[g] = *reinterpret_cast<const f32x4 *>(pa + (((kh << 2) + g) ^ a_swz) * 4);
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[j >> 2][j & 3], bq[c & 1][j >> 2][j & 3], acc, 0, 0, 0);
-        }
-        if (more) srf_dir_store<TM, NCH, NA>(s_a[buf ^ 1], ra, okmask);
-        __syncthreads();
-    }
-
-    const int col = wc * 32 + (lane & 31);
-    const float al = alpha ? alpha[col] : 1.0f;
-    const float be = alpha ? beta[col] : 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int row = row0 + wr * 32 + (j & 3) + 8 * (j >> 2) + 4 * kh;
-        if (row < A_out) {
-            float v = acc[j];
-            if (alpha) v = __fmaf_rn(v, al, be);
-            if (residual) v = __fadd_rn(v, residual[(size_t)row * COUT + col]);
-            if (relu) v = v > 0.0f ? v : 0.0f;
-            out[(size_t)row * COUT + col] = v;
-        }
-    }
-}
-
-// =====================================================================================================================
-// COUT = 128, Cin in {64, 128} and COUT = Cin = 64, compacted offsets ("gs": gather rows, scatter into an LDS-resident output
-// tile).  (COUT = 64: a wave owns one 16-column MFMA tile instead of two, the output tile is half as wide and up to 120 rows
-// tall; on the 64-channel level of a nuScenes sweep only 40 % of the (row, offset) pairs exist, and the output-stationary
-// srf_spconv_direct64_k spent 60 % of its MFMAs on zeros: 159 -> 107 us per layer.)
-// In the output-stationary kernels above a 32-row tile spends one full MFMA pass on every kernel offset any of its rows
-// uses, although only 16-20 of the 27 neighbours of a row exist: 40 % of the issued MFMAs multiply zeros (59 % useful at
-// the 128-channel level of a nuScenes sweep, 73 % on a Waymo sweep).  Here a workgroup owns up to 88 output rows whose
-// accumulators live in LDS.  For every offset k the rows that HAVE a neighbour at k are compacted (one ballot per 64 rows)
-// and processed in groups of 16 on v_mfma_f32_16x16x4_f32: the group's accumulators are read from the output tile (row =
-// the group's output slot), run through the channel-ascending MFMA chain and written back, so every output element still
-// sees exactly the chain (offset ascending, channel ascending) of the oracle -- minus the terms that were exact zeros:
-// results stay bit-identical.  86 % of the issued MFMAs are useful on the nuScenes sweep (90 % Waymo); the kernel issues
-// 70 % of the MFMA cycles of srf_spconv_direct_k (profiles/r01_pmc_spconv128_gs_traffic.json).
-// B operands go global(L2) -> registers in MFMA order as in the direct kernel, once per offset and tile (not once per
-// group), one offset ahead in a second register set; the gathered rows of the next group are fetched during the MFMAs of
-// the current one (double-buffered LDS).  A wave owns 32 output channels of the tile, so no other wave touches its
-// accumulators: one barrier per group (the A hand-over) suffices.
-//   gs layout: Wg[k][chunk][wc = col/32][g][lane][i], idx = 4g + i, = W[k][chunk*32 + 4*(idx&7) + (lane>>4)]
-//                                                                      [wc*32 + 16*(idx>>3) + (lane&15)]
-// LDS: output tile (88 + 1 spare row for the padding slots of last groups) x 132 x 4 = 47 KB, A 2 x (NCH x 2 KB), row lists 27 x 96 x 5 B = 13 KB -> 76 KB, two workgroups
-// per CU (224 VGPRs).  Which rows a workgroup owns: srf_spconv_tiles_build below (ranges of equal cost), or equal-height
-// tiles when the caller passes no ranges.
-// Measured (MI355X, nuScenes level 4, 35k rows, 556k pairs): 257 us vs 342 us for srf_spconv_direct_k; 514 vs 582 us on a
-// 66k-row level with 19.5 pairs per row.  A workgroup spends ~45 % of a group's time issuing MFMAs and the two
-// workgroups of a CU do not interleave perfectly (MFMA pipe busy 64 %): the remaining distance to the MFMA roofline.
-// =====================================================================================================================
-#define SRF_GS_TMAX 88   /* most output rows of a tile: 2 workgroups per CU still fit in LDS */
-#define SRF_GS_LS 96     /* stride of the per-offset row lists (TMAX rounded up to whole groups) */
-#define SRF_GS_OS 132    /* output-tile row stride in floats: rows 4 apart land 16 banks apart */
-#define SRF_GS_CHS (16 * 32 + 8) /* chunk stride of the A image: the four chunks of a row start 8 banks apart */
+// ---- compacted-offset kernel (srf_spconv_gsp_k below): tile height, co-resident workgroups -----------------------------
+#define SRF_GS_TMAX 88   /* most output rows of a COUT = 128 tile: 2 workgroups per CU still fit in LDS */
 #define SRF_GS_SLOTS 512 /* co-resident workgroups: 256 CUs x 2 */
 
 // Tile height.  A tile is ~80 groups of MFMAs (~200 us): with a fixed height the last partial round of tiles would leave
@@ -858,21 +342,8 @@ __host__ __device__ static inline int srf_gs_tile_rows(int A)
     return tm < 16 ? 16 : tm;
 }
 
-static bool srf_gs_enabled()
-{
-    static const bool on = [] {
-        const char *e = getenv("SRF_SPCONV_DIRECT");  // developer switch: keep the previous (direct) kernel for A/B timing
-        return !(e && e[0] == '1');
-    }();
-    return on;
-}
-static bool srf_gsp_enabled();
-static bool srf_gs_layout(int Cin, int Cout)
-{
-    // (32 -> 64, the strided convolution into the 64-channel level: only the pipelined kernel srf_spconv_gsp_k has a one-chunk form)
-    return srf_gs_enabled() && ((Cout == 128 && (Cin == 64 || Cin == 128)) || (Cout == 64 && (Cin == 64 || (Cin == 32 && srf_gsp_enabled()))));
-}
-
+// gs layout: Wg[k][chunk][wc = col/32][g][lane][i], idx = 4g + i, = W[k][chunk*32 + 4*(idx&7) + (lane>>4)][wc*32 + 16*(idx>>3) + (lane&15)]
+// (a lane's B operands of a chunk in MFMA issue order: each f32x4 of a wave is one coalesced 1 KB load)
 __global__ __launch_bounds__(256) void srf_pack_weights_gs_k(const float *__restrict__ W, int K, int Cin, int Cout, int nchunk,
                                                            float *__restrict__ P)
 {
@@ -888,133 +359,6 @@ __global__ __launch_bounds__(256) void srf_pack_weights_gs_k(const float *__rest
     const int col = wc * 32 + 16 * (idx >> 3) + (lane & 15);
     const int c = chunk * 32 + 4 * (idx & 7) + (lane >> 4);
     P[t] = c < Cin ? W[((size_t)k * Cin + c) * Cout + col] : 0.0f;
-}
-
-// rows of one group, global -> registers.  Padding entries of a last group read row 0 and accumulate into a spare row of
-// the output tile that is never stored: any finite-or-not value will do, no zero fill and no predicates are needed
-template <int NCH, int NA>
-__device__ __forceinline__ void srf_gs_gather(const float *__restrict__ in, const int *s_rows, f32x4 (&ra)[NA])
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int e = tid + j * 256;
-        const int r = e / (8 * NCH), q = e % (8 * NCH);
-        const int i = s_rows[r];  // padding entries of a last group name row 0
-        ra[j] = *reinterpret_cast<const f32x4 *>(in + (size_t)i * (32 * NCH) + q * 4);
-    }
-}
-
-// A image of one group: [chunk][row 0..15][32], channel 4q + j of a chunk at position j*8 + q (lane (row, j) of the
-// 16x16x4 MFMA reads its eight steps as two b128), 16-byte units XOR-swizzled by (row >> 1) & 7
-template <int NCH, int NA, int CHS = SRF_GS_CHS>
-__device__ __forceinline__ void srf_gs_store(float *s_a, const f32x4 (&ra)[NA])
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        const int e = tid + j * 256;
-        const int r = e / (8 * NCH), qq = e % (8 * NCH);
-        const int ch = qq >> 3, q = qq & 7;
-        const int swz = (r >> 1) & 7;
-        float *img = s_a + ch * CHS + r * 32 + (q & 3);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) img[((jj * 2 + (q >> 2)) ^ swz) << 2] = ra[j][jj];
-    }
-}
-
-// B operands of one (offset, chunk) for this wave.  COUT = 128: the wave owns 32 columns (two 16-column MFMA tiles, four
-// f32x4); COUT = 64: 16 columns (tile `wave & 1` of column block `wave >> 1`, two f32x4 of the same packed image)
-template <int NCH, int COUT>
-__device__ __forceinline__ void srf_gs_load_b(f32x4 (&b)[COUT / 32], const float *__restrict__ Wg, int k, int chunk, int wave, int lane)
-{
-    constexpr int NWC = COUT / 32;
-    const int wc = COUT == 128 ? wave : (wave >> 1), g0 = COUT == 128 ? 0 : 2 * (wave & 1);
-#pragma unroll
-    for (int g = 0; g < COUT / 32; ++g)
-        b[g] = *reinterpret_cast<const f32x4 *>(Wg + (((((size_t)k * NCH + chunk) * NWC + wc) * 4 + g0 + g) * 64 + lane) * 4);
-}
-
-// GP = groups of 16 rows per step (one gather / barrier per step).  COUT = 64 runs GP = 2: a wave's share of a group is
-// only 16 MFMAs (512 cycles), less than the L2 latency of the next gather, so a step carries two groups (two independent
-// accumulator chains) and the tile needs a third fewer steps.
-template <int NCH, int NA, int COUT, int LS, int OS, int TMAX, int GP>
-__device__ __forceinline__ void srf_gs_offset(const float *__restrict__ in, const float *__restrict__ Wg, int kc, int kn, bool more_k,
-                                              const int *s_in, const unsigned char *s_slot, const int *s_cnt, float *s_out,
-                                              float *s_a, int &buf, f32x4 (&bc)[NCH][COUT / 32], f32x4 (&bn)[NCH][COUT / 32],
-                                              f32x4 (&ra)[NA])
-{
-    constexpr int NT = COUT / 64;  // 16-column MFMA tiles per wave
-    constexpr int RS = 16 * GP, CHS = RS * 32 + 8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int colb = COUT == 128 ? wave * 32 : wave * 16;
-    const int n = s_cnt[kc];
-    const int ng = (n + RS - 1) / RS;
-    const int ar = lane & 15, aj = lane >> 4;
-    const int a_swz = (ar >> 1) & 7;
-    for (int g = 0; g < ng; ++g) {
-        const bool last = g + 1 == ng;
-        const bool has_next = !last || more_k;
-        if (last && more_k) {  // B of the next offset, one whole step of MFMAs ahead, into the other register set
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) srf_gs_load_b<NCH, COUT>(bn[c], Wg, kn, c, wave, lane);
-        }
-        if (has_next) srf_gs_gather<NCH, NA>(in, last ? s_in + kn * LS : s_in + kc * LS + (g + 1) * RS, ra);
-        // all A fragments of the step first (ds_read_b128 in flight together, one exposed LDS latency per step instead of
-        // one per chunk), then the accumulators of its rows out of the output tile
-        f32x4 af[GP][NCH][2];
-        f32x4 acc[GP][NT];
-        int oaddr[GP][4];
-#pragma unroll
-        for (int gp = 0; gp < GP; ++gp) {
-            const float *abase = s_a + buf * (NCH * CHS) + (gp * 16 + ar) * 32;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                af[gp][c][0] = *reinterpret_cast<const f32x4 *>(abase + c * CHS + (((aj << 1) ^ a_swz) << 2));
-                af[gp][c][1] = *reinterpret_cast<const f32x4 *>(abase + c * CHS + ((((aj << 1) + 1) ^ a_swz) << 2));
-            }
-        }
-#pragma unroll
-        for (int gp = 0; gp < GP; ++gp) {
-            // output slots of the group's 16 rows; padding rows of a last step name the spare row TMAX
-            const unsigned sl4 = *reinterpret_cast<const unsigned *>(s_slot + kc * LS + (g * GP + gp) * 16 + aj * 4);
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                oaddr[gp][jj] = (int)((sl4 >> (8 * jj)) & 255u) * OS + colb + ar;
-#pragma unroll
-                for (int cb = 0; cb < NT; ++cb) acc[gp][cb][jj] = s_out[oaddr[gp][jj] + cb * 16];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);  // keep the reads above the MFMA block
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-#pragma unroll
-                for (int gp = 0; gp < GP; ++gp) {
-                    const float a = af[gp][c][s >> 2][s & 3];
-                    acc[gp][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bc[c][s >> 2][s & 3], acc[gp][0], 0, 0, 0);
-                    if (NT == 2)
-                        acc[gp][NT - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bc[c][COUT / 32 - 2 + (s >> 2)][s & 3], acc[gp][NT - 1], 0, 0, 0);
-                }
-            }
-        }
-        // a padding slot (spare row TMAX) may appear in both groups of a step: both write garbage there, never read back
-#pragma unroll
-        for (int gp = 0; gp < GP; ++gp)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-#pragma unroll
-                for (int cb = 0; cb < NT; ++cb) s_out[oaddr[gp][jj] + cb * 16] = acc[gp][cb][jj];
-            }
-        // every load issued in this step has landed before the next one starts.  Stated explicitly (s_waitcnt vmcnt(0)):
-        // the compiler cannot tie "B was prefetched" to "the gather was waited for" across the two branches and would
-        // otherwise guard the next step's MFMAs with vmcnt waits that also catch that step's own fresh loads
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        if (has_next) srf_gs_store<NCH, NA, CHS>(s_a + (buf ^ 1) * (NCH * CHS), ra);
-        __syncthreads();
-        buf ^= 1;
-    }
 }
 
 // ---- work-balanced row ranges ------------------------------------------------------------------------------------------
@@ -1185,182 +529,31 @@ extern "C" int srf_spconv_tiles_build(const int *nbr, int nbr_stride, int K, int
     return SRF_OK;
 }
 
-template <int NCH, int COUT>
-__global__ __launch_bounds__(256, 2) void srf_spconv_gs_k(const float *__restrict__ in, const float *__restrict__ Wg, int K,
-                                                        const int *__restrict__ nbr, int nbr_stride, int A_out,
-                                                        const float *__restrict__ alpha, const float *__restrict__ beta,
-                                                        const float *__restrict__ residual, int relu,
-                                                        float *__restrict__ out, const int *__restrict__ rows_dev,
-                                                        const int *__restrict__ tiles)
-{
-    // COUT = 64 (Cin = 64): a wave owns one 16-column MFMA tile, the output tile is half as wide and may be taller
-    // groups of 16 rows per step (srf_gs_offset).  COUT = 64, nuScenes level 3 (59.6k rows, 10.9 pairs per row): 107 us with 1,
-    // 123 us with 2; 64-row tiles walked by two workgroups per range (four per CU) 118 us; B fetched a whole offset ahead 113 us.
-    // Ablations of the 107 us: without MFMAs 70, without the gathers 99, without barriers 100, prologue + epilogue alone 14.
-    // Three workgroups per CU (88-row tiles, 768 ranges, 46 KB of LDS each): 105 us -- occupancy is not what holds it.
-    // Round 3: starting the workgroup in the odd wave slots of a CU (HW_ID) 1-4 k cycles late, so that the two co-resident
-    // workgroups begin out of phase: no change (108 / 262 us with and without, both shapes) -- they do not run in lock-step.
-    constexpr int GP = 1;
-    constexpr int NA = 16 * GP * 8 * NCH / 256, NKW = (SRF_KMAX + 3) / 4, CHS = 16 * GP * 32 + 8;
-    constexpr int TMAX = COUT == 128 ? SRF_GS_TMAX : 120, LS = COUT == 128 ? SRF_GS_LS : 128, OS = COUT + 4;
-    constexpr int SPLIT = 1;  // workgroups per range of the row cut (2 with 64-row tiles was slower for COUT = 64: 118 vs 107 us)
-    static_assert(COUT == 128 || COUT == 64, "column tiling of the waves");
-    static_assert(TMAX <= 128 && TMAX <= LS && LS % (16 * GP) == 0, "two ballot segments of 64 rows; whole groups per list");
-    static_assert(NA >= 1, "a group is at least one f32x4 per thread");
-    __shared__ int s_in[SRF_KMAX * LS];                 // per offset: input rows of the outputs that have this neighbour
-    __shared__ __attribute__((aligned(4))) unsigned char s_slot[SRF_KMAX * LS];  // ... and their slot in the output tile
-    __shared__ int s_cnt[SRF_KMAX];
-    __shared__ int s_klist[SRF_KMAX + 1];
-    __shared__ __attribute__((aligned(16))) float s_out[(TMAX + 1) * OS];  // + the spare row of padding slots
-    __shared__ __attribute__((aligned(16))) float s_a[2 * NCH * CHS];
-
-    const int A_cap = A_out;
-    if (rows_dev) {  // static-shape levels: rows >= *rows_dev are padding; their tiles do nothing
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // this workgroup's rows: a work-balanced range of the rulebook (walked in equal sub-tiles), or one equal-height tile
-    int range0, range1;
-    if (tiles) {
-        const int T = srf_gs_ranges(A_cap);
-        if ((int)blockIdx.x >= T * SPLIT) return;
-        const int ts = srf_xcd_tile(blockIdx.x, T * SPLIT);
-        const int t = ts / SPLIT, part = ts - t * SPLIT;
-        range0 = tiles[t];
-        range1 = tiles[t + 1];
-        range1 = range1 < A_out ? range1 : A_out;
-        if (SPLIT > 1 && range1 > range0) {  // this workgroup's share of the range: whole multiples of 8 rows
-            const int per = (((range1 - range0 + SPLIT - 1) / SPLIT) + 7) & ~7;
-            range0 += part * per;
-            range1 = range0 + per < range1 ? range0 + per : range1;
-        }
-    } else {
-        const int tm = srf_gs_tile_rows(A_out);
-        const int n_tiles = (A_out + tm - 1) / tm;
-        if ((int)blockIdx.x >= n_tiles) return;
-        range0 = srf_xcd_tile(blockIdx.x, n_tiles) * tm;
-        range1 = range0 + tm < A_out ? range0 + tm : A_out;
-    }
-    if (range1 <= range0) return;
-    const int nsub = (range1 - range0 + TMAX - 1) / TMAX;
-    const int TM = (((range1 - range0 + nsub - 1) / nsub) + 7) & ~7;  // <= TMAX (a multiple of 8)
-    for (int row0 = range0; row0 < range1; row0 += TM) {
-    const int row_end = row0 + TM < range1 ? row0 + TM : range1;  // rows of this sub-tile: [row0, row_end)
-    // An opaque zero: the address arithmetic of the prologue / epilogue below is invariant across sub-tiles, and hoisted
-    // above this loop it stays live through the main loop, where every register is taken -- the compiler then spills it
-    // (11 MB of scratch write-back per launch).  Tied to this value it is recomputed per sub-tile instead.
-    int zero = 0;
-    asm volatile("" : "+s"(zero));
-    for (int e = tid; e < TM * OS / 4; e += 256) reinterpret_cast<f32x4 *>(s_out)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // compaction: the wave's offsets (wave, wave + 4, ...), rows in two segments of 64; all loads in flight together
-    int nv[NKW][2];
-#pragma unroll
-    for (int i = 0; i < NKW; ++i)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int k = wave + 4 * i, r = h * 64 + lane;
-            nv[i][h] = (k < K && row0 + r < row_end) ? nbr[(size_t)(k + zero) * nbr_stride + row0 + r] : -1;
-        }
-#pragma unroll
-    for (int i = 0; i < NKW; ++i) {
-        const int k = wave + 4 * i;
-        if (k >= SRF_KMAX) break;
-        int *lin = s_in + (k + zero) * LS;
-        unsigned char *lsl = s_slot + (k + zero) * LS;
-        lin[lane] = 0;  // padding of the last group: input row 0 into the spare output row (same wave: ordered before the
-        lsl[lane] = (unsigned char)TMAX;  // compacted stores below)
-        if (lane < LS - 64) {
-            lin[64 + lane] = 0;
-            lsl[64 + lane] = (unsigned char)TMAX;
-        }
-        int base = 0;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int v = nv[i][h];
-            const unsigned long long m = __ballot(v >= 0);
-            if (v >= 0) {
-                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-                lin[pos] = v;
-                lsl[pos] = (unsigned char)(h * 64 + lane);
-            }
-            base += __popcll(m);
-        }
-        if (lane == 0) s_cnt[k] = base;
-    }
-    __syncthreads();
-    if (tid < 64) {
-        const bool used = tid < K && s_cnt[tid] > 0;
-        const unsigned long long m = __ballot(used);
-        if (used) s_klist[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-        if (tid == 0) s_klist[SRF_KMAX] = __popcll(m);
-    }
-    __syncthreads();
-    const int ntap = s_klist[SRF_KMAX];
-
-    f32x4 b0[NCH][COUT / 32], b1[NCH][COUT / 32], ra[NA];
-    int buf = 0;
-    if (ntap > 0) {
-        const int k0 = s_klist[0];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) srf_gs_load_b<NCH, COUT>(b0[c], Wg, k0, c, wave, lane);
-        srf_gs_gather<NCH, NA>(in, s_in + k0 * LS, ra);
-        srf_gs_store<NCH, NA, CHS>(s_a, ra);
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing is in flight when the first group starts (see srf_gs_offset)
-    __syncthreads();
-    for (int tk = 0; tk < ntap; tk += 2) {  // two offsets per trip: the B register sets swap roles without moves
-        {
-            const bool more = tk + 1 < ntap;
-            const int kc = s_klist[tk], kn = more ? s_klist[tk + 1] : kc;
-            srf_gs_offset<NCH, NA, COUT, LS, OS, TMAX, GP>(in, Wg, kc, kn, more, s_in, s_slot, s_cnt, s_out, s_a, buf, b0, b1, ra);
-        }
-        if (tk + 1 < ntap) {
-            const bool more = tk + 2 < ntap;
-            const int kc = s_klist[tk + 1], kn = more ? s_klist[tk + 2] : kc;
-            srf_gs_offset<NCH, NA, COUT, LS, OS, TMAX, GP>(in, Wg, kc, kn, more, s_in, s_slot, s_cnt, s_out, s_a, buf, b1, b0, ra);
-        }
-    }
-
-    // epilogue: every output row once, BN / residual / ReLU in registers, 512 B per row and store
-    constexpr int CQ = COUT / 4;  // float4 per output row
-    const int c4 = ((tid & (CQ - 1)) + zero) * 4;
-    f32x4 al = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
-    if (alpha) {
-        al = *reinterpret_cast<const f32x4 *>(alpha + c4);
-        be = *reinterpret_cast<const f32x4 *>(beta + c4);
-    }
-    for (int r = tid / CQ; r < TM; r += 256 / CQ) {
-        const int row = row0 + r;
-        if (row >= row_end) break;
-        f32x4 v = *reinterpret_cast<const f32x4 *>(s_out + r * OS + c4);
-        f32x4 rs = {0.f, 0.f, 0.f, 0.f};
-        if (residual) rs = *reinterpret_cast<const f32x4 *>(residual + (size_t)row * COUT + c4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float x = v[j];
-            if (alpha) x = __fmaf_rn(x, al[j], be[j]);
-            if (residual) x = __fadd_rn(x, rs[j]);
-            if (relu) x = x > 0.0f ? x : 0.0f;
-            v[j] = x;
-        }
-        *reinterpret_cast<f32x4 *>(out + (size_t)row * COUT + c4) = v;
-    }
-    __syncthreads();  // the output tile and the row lists are rebuilt by the next sub-tile
-    }
-}
-
 // =====================================================================================================================
-// srf_spconv_gsp_k: the compacted-offset kernel above with its step SOFTWARE-PIPELINED (round 5).
-// In srf_spconv_gs_k a step (one group of 16 compacted rows) is a serial chain in every wave: read the A fragments and the
-// group's accumulators from LDS (0.71 us of exposed LDS latency and address arithmetic in the in-kernel stamps), 64 MFMAs
-// (0.92 us), accumulators back (0.18), wait for the gather + store it (0.22), barrier: the MFMA pipe sees 45 % of a wave's time
-// and the two workgroups of a CU interleave only partly (62 % busy).  Same arithmetic here -- the same (offset, channel)-
-// ascending chain per output, bit-identical results -- but every wave's MFMA block is the only thing it waits for:
+// srf_spconv_gsp_k: the packed kernel of the layers with COUT = 128 (Cin = 64 / 128: the SubM layers of the last level, the
+// strided 64 -> 128, `conv_out`) and COUT = 64 (Cin = 32 / 64), any K.  Compacted offsets ("gs": gather rows, scatter into an
+// LDS-resident output tile):
+//   * only 16-20 of the 27 neighbours of a row exist, so an output-stationary tile, which runs one MFMA pass per offset any of its
+//     rows uses, spends ~40 % of its MFMAs on zeros.  Here a workgroup owns up to TMAX output rows (SRF_GS_TMAX = 88 for
+//     COUT = 128, 128 for COUT = 64) whose accumulators live in LDS.  For every offset k the rows that HAVE a neighbour at k are
+//     compacted (one ballot per 64 rows) and processed in groups of 16 on v_mfma_f32_16x16x4_f32: the group's accumulators are read
+//     from the output tile (row = the group's output slot), run through the channel-ascending MFMA chain and written back;
+//   * every output element therefore sees exactly the chain (offset ascending, channel ascending, one fma per term) of
+//     oracle/srf_oracle.c:orc_spconv_fwd, minus terms that are exact zeros: results are bit-identical to srf_spconv_fwd and to the
+//     oracle;
+//   * a wave owns 32 (COUT = 128) or 16 (COUT = 64) output channels of the tile, so no other wave touches its accumulators.  Its B
+//     operands (gs layout, srf_pack_weights_gs_k) go global(L2) -> registers once per offset and tile, one offset ahead in a second
+//     register set;
+//   * A image of a group of 16 rows: [chunk][row 0..15][32], channel 4q + j of a chunk at position j*8 + q (lane (row, j) of the
+//     16x16x4 MFMA reads its eight steps as two b128), 16-byte units XOR-swizzled by (row >> 1) & 7;
+//   * LDS: the output tile ((TMAX + 1 spare row for padding slots) x (COUT + 4) floats), two A images, the flat step list below:
+//     58 KB (32 -> 64) to 76 KB (128 -> 128) -> two workgroups per CU (__launch_bounds__(256, 2), SRF_GS_SLOTS);
+//   * which rows a workgroup owns: one range of srf_spconv_tiles_build (equal cost), or one equal-height tile (srf_gs_tile_rows)
+//     when the caller passes no ranges; either is walked in sub-tiles of at most TMAX rows.
+// The step is SOFTWARE-PIPELINED, so that every wave's MFMA block is the only thing it waits for:
 //   * the rows of ALL offsets of a sub-tile form ONE flat list of steps (per offset padded to whole groups of 16; s_pin holds
 //     the byte offset of the input row, s_pslot the output slot): step i's rows are entries 16 i .. 16 i + 15 whatever its
-//     offset, so looking two steps ahead is plain address arithmetic (the per-offset lists of the kernel above needed the
-//     offset after next for that);
+//     offset, so looking two steps ahead is plain address arithmetic;
 //   * step i issues, in this order: the chunk-0 fragments of A[i]; the LDS stores of A[i + 1] (gathered during step i - 1:
 //     landed long ago, no wait); the gather of step i + 2; then per 32-channel chunk the fragment reads of the NEXT chunk
 //     followed by the chunk's MFMAs (fragments double-buffered per chunk: 16 registers instead of 32), the output slots of
@@ -1369,21 +562,13 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gs_k(const float *__restric
 //     barrier.  LDS instructions issued between the MFMAs of the own wave cost ~1 cycle per MFMA; what stays exposed per
 //     step is one LDS latency behind the barrier and the accumulator round trip;
 //   * address arithmetic per step: rows are gathered through a buffer descriptor (32-bit offset row + quad: one add per
-//     load, padding entries are out-of-range offsets that read zeros without touching memory), the store addresses of the A
-//     image are precomputed per thread: ~20 vector instructions per step (they take MFMA issue time on this chip);
+//     load, padding entries are out-of-range offsets that read zeros without touching memory; hence inputs below 2 GiB), the
+//     store addresses of the A image are precomputed per thread: ~20 vector instructions per step (they take MFMA issue time
+//     on this chip);
 //   * the last step of an offset is a separate instantiation (LAST) that also fetches the next offset's B operands into the
 //     other register set right behind the gather: no branch inside a step, the compiler's vmcnt bookkeeping stays exact.
 // The flat lists carry two dummy steps behind the real ones (zeros into the spare row), so nothing in a step is conditional.
 // =====================================================================================================================
-
-static bool srf_gsp_enabled()
-{
-    static const bool on = [] {
-        const char *e = getenv("SRF_SPCONV_GSP");  // developer switch: 0 keeps srf_spconv_gs_k (A/B timing, parity of the two forms)
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
 
 typedef __attribute__((address_space(3))) float srf_lds_float;
 typedef __attribute__((address_space(3))) f32x4 srf_lds_f32x4;
@@ -1644,7 +829,10 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
     const int TM = (((range1 - range0 + nsub - 1) / nsub) + 7) & ~7;
     for (int row0 = range0; row0 < range1; row0 += TM) {
     const int row_end = row0 + TM < range1 ? row0 + TM : range1;
-    int zero = 0;   // opaque: keeps the prologue's address arithmetic from being hoisted above the sub-tile loop and spilled (see srf_spconv_gs_k)
+    // An opaque zero: the address arithmetic of the prologue / epilogue is invariant across sub-tiles, and hoisted above this loop
+    // it would stay live through the main loop, where every register is taken, and be spilled.  Tied to this value it is recomputed
+    // per sub-tile instead.
+    int zero = 0;
     asm volatile("" : "+s"(zero));
     long long tp0 = 0, tl0 = 0, te0 = 0;
     if (ABL == 5) tp0 = __builtin_amdgcn_s_memtime();
@@ -1878,17 +1066,17 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
 
 // =====================================================================================================================
 // srf_spconv_w32_k: the 32-output-channel layers (SubM 32 -> 32 x 4 and the strided 16 -> 32 of the nuScenes encoder,
-// sparse_encoder_custom.py:109-140 through spconv's SubMConv3d / SparseConv3d) -- 2 GFLOP per frame that took 0.33 ms: the
-// tile kernel above walks its 27 offsets as gather -> LDS -> barrier -> 16 MFMAs with one step of lookahead, i.e. at the
-// latency of a gather per step (2.4 us) whatever the arithmetic.  Here nothing is shared but the weights:
+// sparse_encoder_custom.py:109-140 through spconv's SubMConv3d / SparseConv3d).  A tile kernel that walks the 27 offsets as
+// gather -> LDS -> barrier -> 16 MFMAs runs at the latency of a gather per step whatever the arithmetic.  Here nothing is
+// shared but the weights:
 //   * a workgroup = 8 waves x 32 output rows; all 27 x Cin x 32 weights sit in LDS (110 KB at Cin = 32), copied once;
 //   * every wave gathers ITS 32 rows straight into the MFMA's A layout -- lane (row, half) loads half of the neighbour's
 //     channels with Cin / 8 buffer_load_dwordx4 (a missing neighbour is an out-of-range offset and reads as zero), then
 //     v_permlane32_swap hands the odd channels to lanes 32-63 and the even ones to lanes 0-31 (the f32 32x32x2 MFMA takes
 //     channel 2 s from lanes 0-31 and 2 s + 1 from lanes 32-63) -- three offsets in flight, no barrier, no LDS round trip;
 //   * offsets none of the wave's rows has are skipped (one ballot per offset).
-// Every output is the same chain as before (offset ascending, channel ascending, zero terms added as +0): bit-identical to
-// the tile kernel and the oracle.
+// Every output is the chain (offset ascending, channel ascending, zero terms added as +0) of oracle/srf_oracle.c:orc_spconv_fwd:
+// bit-identical to srf_spconv_fwd and the oracle.
 // =====================================================================================================================
 // ---------------------------------------------------------------------------------------------------------------------
 // Row order for the 32-channel layers (srf_spconv_w32_k): a wave multiplies EVERY offset that any of its 32 rows has -- 0.77 of the
@@ -2125,145 +1313,83 @@ extern "C" int srf_spconv_fwd_packed(const float *in, int A_in, int Cin, const f
 {
     if (A_in < 0 || A_out < 0 || Cin <= 0 || Cin > 512 || K <= 0 || K > SRF_KMAX || nbr_stride < A_out) return SRF_EINVAL;
     if ((alpha == nullptr) != (beta == nullptr)) return SRF_EINVAL;
+    const SrfPackedLayout layout = srf_packed_layout(K, Cin, Cout);
+    if (layout == SRF_PACKED_NONE) return SRF_EUNSUPPORTED;
     if (A_out == 0) return SRF_OK;
     if (!in || !W_packed || !nbr || !out) return SRF_EINVAL;
-    if ((Cin & 3) || A_in == 0) return SRF_EUNSUPPORTED;
+    // both kernels gather through a buffer descriptor: 32-bit byte offsets into the input
+    if (A_in == 0 || (long long)A_in * Cin * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-#define SRF_ARGS in, Cin, W_packed, K, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev
-    switch (Cout) {
-    case 32:
-        // the weights of these shapes are packed for srf_spconv_w32_k alone (srf_spconv_pack_weights picks the layout from (K, Cin, Cout)):
-        // an input beyond its 32-bit descriptor range (>= 16 M rows) must not fall through to a kernel that reads the tile layout
-        if (srf_w32_layout(K, Cin, Cout) && (long long)A_in * Cin * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
-        if (srf_w32_layout(K, Cin, Cout)) {
-            int dev = 0;
-            SRF_HIP_TRY(hipGetDevice(&dev));
-            static bool attr_set[64] = {false};
-            if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-            if (!attr_set[dev]) {
-                SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_spconv_w32_k<32>, hipFuncAttributeMaxDynamicSharedMemorySize, SRF_KMAX * 32 * 32 * 4));
-                SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_spconv_w32_k<16>, hipFuncAttributeMaxDynamicSharedMemorySize, SRF_KMAX * 16 * 32 * 4));
-                attr_set[dev] = true;
-            }
-            // `tiles` of a 32-channel layer = the plan of srf_spconv_order_build (NULL: rows in their own order)
-            const unsigned grid32 = tiles ? (unsigned)(srf_ord_pad(A_out) / 256) : (unsigned)srf_ceil_div(A_out, 256);
-            if (Cin == 32)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_w32_k<32>), dim3(grid32), dim3(512), SRF_KMAX * 32 * 32 * 4, st, in,
-                                   A_in, W_packed, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_w32_k<16>), dim3(grid32), dim3(512), SRF_KMAX * 16 * 32 * 4, st, in,
-                                   A_in, W_packed, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-            break;
+    if (layout == SRF_PACKED_W32) {
+        int dev = 0;
+        SRF_HIP_TRY(hipGetDevice(&dev));
+        static bool attr_set[64] = {false};
+        if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
+        if (!attr_set[dev]) {
+            SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_spconv_w32_k<32>, hipFuncAttributeMaxDynamicSharedMemorySize, SRF_KMAX * 32 * 32 * 4));
+            SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_spconv_w32_k<16>, hipFuncAttributeMaxDynamicSharedMemorySize, SRF_KMAX * 16 * 32 * 4));
+            attr_set[dev] = true;
         }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_packed_k<32, 128, 4, 1>), dim3(srf_ceil_div(A_out, 128)), dim3(256),
-                           0, st, SRF_ARGS);
-        break;
-    case 64:
-        if (srf_gs_layout(Cin, Cout)) {
-            const dim3 grid(tiles ? srf_gs_ranges(A_out) : SRF_GS_SLOTS * srf_gs_rounds(A_out));
+        // `tiles` of a 32-channel layer = the plan of srf_spconv_order_build (NULL: rows in their own order)
+        const unsigned grid32 = tiles ? (unsigned)(srf_ord_pad(A_out) / 256) : (unsigned)srf_ceil_div(A_out, 256);
+        if (Cin == 32)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_w32_k<32>), dim3(grid32), dim3(512), SRF_KMAX * 32 * 32 * 4, st, in,
+                               A_in, W_packed, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_w32_k<16>), dim3(grid32), dim3(512), SRF_KMAX * 16 * 32 * 4, st, in,
+                               A_in, W_packed, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
+        SRF_LAUNCH_CHECK();
+        return SRF_OK;
+    }
+    // SRF_PACKED_GS.  Grid: >= the tiles of any live row count <= A_out / the ranges srf_spconv_tiles_build cut for this capacity
+    const dim3 grid(tiles ? srf_gs_ranges(A_out) : SRF_GS_SLOTS * srf_gs_rounds(A_out));
+#define SRF_GSP_LAUNCH(NCH, COUT) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<NCH, COUT>), grid, dim3(256), 0, st, in, A_in, W_packed, K, \
+                                                     nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev, tiles)
+    if (Cout == 64) {
 #ifdef SRF_DEV
-            if (Cin == 64 && srf_gsp_enabled() && (long long)A_in * Cin * 4 < (1ll << 31) && (getenv("SRF_GSP_ABL") || getenv("SRF_GSP_GP2"))) {
-                const bool stamp = getenv("SRF_GSP_ABL") && atoi(getenv("SRF_GSP_ABL")) == 5, gp2 = getenv("SRF_GSP_GP2") != nullptr;
+        if (Cin == 64 && (getenv("SRF_GSP_ABL") || getenv("SRF_GSP_GP2"))) {
+            const bool stamp = getenv("SRF_GSP_ABL") && atoi(getenv("SRF_GSP_ABL")) == 5, gp2 = getenv("SRF_GSP_GP2") != nullptr;
 #define SRF_GSP_DEV64(A, G) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<2, 64, A, G>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride, \
                                                A_out, alpha, beta, residual, relu, out, rows_dev, tiles)
-                if (stamp && gp2) SRF_GSP_DEV64(5, 2);
-                else if (stamp) SRF_GSP_DEV64(5, 1);
-                else if (gp2) SRF_GSP_DEV64(0, 2);
-                else SRF_GSP_DEV64(0, 1);
+            if (stamp && gp2) SRF_GSP_DEV64(5, 2);
+            else if (stamp) SRF_GSP_DEV64(5, 1);
+            else if (gp2) SRF_GSP_DEV64(0, 2);
+            else SRF_GSP_DEV64(0, 1);
 #undef SRF_GSP_DEV64
-                break;
-            }
+            SRF_LAUNCH_CHECK();
+            return SRF_OK;
+        }
 #endif
-            if (Cin == 32) {   // only the pipelined kernel has a one-chunk form (the weights are packed for it: srf_gs_layout)
-                if ((long long)A_in * Cin * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<1, 64>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride, A_out,
-                                   alpha, beta, residual, relu, out, rows_dev, tiles);
-            } else if (srf_gsp_enabled() && (long long)A_in * Cin * 4 < (1ll << 31))
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<2, 64>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride, A_out,
-                                   alpha, beta, residual, relu, out, rows_dev, tiles);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gs_k<2, 64>), grid, dim3(256), 0, st, in, W_packed, K, nbr, nbr_stride, A_out,
-                                   alpha, beta, residual, relu, out, rows_dev, tiles);
-            break;
-        }
-        if (srf_direct_layout(Cin, Cout)) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_direct64_k<2>), dim3(srf_ceil_div(A_out, 64)), dim3(256), 0, st, in, W_packed,
-                               K, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev);
-            break;
-        }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_packed_k<64, 64, 2, 2>), dim3(srf_ceil_div(A_out, 64)), dim3(256), 0,
-                           st, SRF_ARGS);
-        break;
-    case 128: {
-        if (srf_gs_layout(Cin, Cout)) {
-            // >= the tiles of any live row count <= A_out / the ranges srf_spconv_tiles_build cut for this capacity
-            const dim3 grid(tiles ? srf_gs_ranges(A_out) : SRF_GS_SLOTS * srf_gs_rounds(A_out));
-            if (srf_gsp_enabled() && (long long)A_in * Cin * 4 < (1ll << 31)) {
+        if (Cin == 32) SRF_GSP_LAUNCH(1, 64);
+        else SRF_GSP_LAUNCH(2, 64);
+    } else {
 #ifdef SRF_DEV
-                if (Cin == 128) {   // SRF_GSP_ABL = ablation (wrong outputs), SRF_GSP_PADLDS = extra LDS bytes (one workgroup per CU from 4000 on)
-                    const char *e = getenv("SRF_GSP_ABL"), *pl = getenv("SRF_GSP_PADLDS");
-                    const int abl = e ? atoi(e) : 0, pad = pl ? atoi(pl) : 0;
+        if (Cin == 128) {   // SRF_GSP_ABL = ablation (wrong outputs), SRF_GSP_PADLDS = extra LDS bytes (one workgroup per CU from 4000 on)
+            const char *e = getenv("SRF_GSP_ABL"), *pl = getenv("SRF_GSP_PADLDS");
+            const int abl = e ? atoi(e) : 0, pad = pl ? atoi(pl) : 0;
 #define SRF_GSP_DEV(A) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<4, 128, A>), grid, dim3(256), pad, st, in, A_in, W_packed, K, nbr, nbr_stride, \
                                           A_out, alpha, beta, residual, relu, out, rows_dev, tiles)
-                    if (abl == 1) SRF_GSP_DEV(1);
-                    else if (abl == 2) SRF_GSP_DEV(2);
-                    else if (abl == 3) SRF_GSP_DEV(3);
-                    else if (abl == 4) SRF_GSP_DEV(4);
-                    else if (abl == 5) SRF_GSP_DEV(5);
-                    else SRF_GSP_DEV(0);
+            if (abl == 1) SRF_GSP_DEV(1);
+            else if (abl == 2) SRF_GSP_DEV(2);
+            else if (abl == 3) SRF_GSP_DEV(3);
+            else if (abl == 4) SRF_GSP_DEV(4);
+            else if (abl == 5) SRF_GSP_DEV(5);
+            else SRF_GSP_DEV(0);
 #undef SRF_GSP_DEV
-                    break;
-                }
-#endif
-#ifdef SRF_DEV
-                if (Cin == 64 && getenv("SRF_GSP_ABL") && atoi(getenv("SRF_GSP_ABL")) == 5) {
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<2, 128, 5>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride,
-                                       A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-                    break;
-                }
-#endif
-                if (Cin == 128)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<4, 128>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride,
-                                       A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<2, 128>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride,
-                                       A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-                break;
-            }
-            if (Cin == 128)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gs_k<4, 128>), grid, dim3(256), 0, st, in, W_packed, K, nbr, nbr_stride,
-                                   A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gs_k<2, 128>), grid, dim3(256), 0, st, in, W_packed, K, nbr, nbr_stride,
-                                   A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-            break;
+            SRF_LAUNCH_CHECK();
+            return SRF_OK;
         }
-        if (srf_direct_layout(Cin, Cout)) {
-#define SRF_DARGS in, W_packed, K, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev
-            if (Cin == 128)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_direct_k<32, 4, 2>), dim3(srf_ceil_div(A_out, 32)), dim3(256), 0, st,
-                                   SRF_DARGS);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_direct_k<32, 2, 2>), dim3(srf_ceil_div(A_out, 32)), dim3(256), 0, st,
-                                   SRF_DARGS);
-#undef SRF_DARGS
-            break;
+        if (Cin == 64 && getenv("SRF_GSP_ABL") && atoi(getenv("SRF_GSP_ABL")) == 5) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<2, 128, 5>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride,
+                               A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
+            SRF_LAUNCH_CHECK();
+            return SRF_OK;
         }
-        // 64-row tiles halve the W-slab traffic, 32-row tiles balance better when there are only a few tiles per CU:
-        // pick the one whose busiest CU (tiles dealt evenly over 256 CUs) carries fewer 32-row units
-        const int units64 = 2 * srf_ceil_div(srf_ceil_div(A_out, 64), 256), units32 = srf_ceil_div(srf_ceil_div(A_out, 32), 256);
-        if (units32 < units64)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_packed_k<128, 32, 1, 4>), dim3(srf_ceil_div(A_out, 32)), dim3(256), 0,
-                               st, SRF_ARGS);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_packed_k<128, 64, 2, 2>), dim3(srf_ceil_div(A_out, 64)), dim3(256), 0,
-                               st, SRF_ARGS);
-        break;
+#endif
+        if (Cin == 128) SRF_GSP_LAUNCH(4, 128);
+        else SRF_GSP_LAUNCH(2, 128);
     }
-    default:
-        return SRF_EUNSUPPORTED;
-    }
-#undef SRF_ARGS
+#undef SRF_GSP_LAUNCH
     SRF_LAUNCH_CHECK();
     return SRF_OK;
 }
@@ -2491,15 +1617,6 @@ __global__ __launch_bounds__(256) void srf_spconv_c16l_k(const float *__restrict
 #ifndef SRF_C16L_MIN_ROWS
 #define SRF_C16L_MIN_ROWS 60000   /* measured (MI355X): 26k rows 14.1 -> 14.7 us (every wave resident at once either way), 99k rows 47.9 -> 35.1 us */
 #endif
-static bool srf_c16l_enabled()
-{
-    static const bool on = [] {
-        const char *e = getenv("SRF_SPCONV_C16L");   // developer switch: 0 = the register-weight form (A/B timing; identical bits)
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
 extern "C" int srf_spconv_fwd(const float *in, int A_in, int Cin, const float *W, int K, const int *nbr, int nbr_stride,
                               int A_out, int Cout, const float *alpha, const float *beta, const float *residual,
                               int relu, float *out, const int *rows_dev, srf_stream_t stream)
@@ -2515,7 +1632,7 @@ extern "C" int srf_spconv_fwd(const float *in, int A_in, int Cin, const float *W
     case 16:
         if (Cin <= 16 && K == SRF_KMAX && A_in > 0) {  // register-resident weights, LDS-free gather
             // many rows (Waymo's first level): the LDS-weight form, five waves per SIMD; few rows: every wave is resident at once anyway
-            const bool lds_w = srf_c16l_enabled() && A_out >= SRF_C16L_MIN_ROWS;
+            const bool lds_w = A_out >= SRF_C16L_MIN_ROWS;
             if (Cin <= 8) {
                 if (lds_w) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_c16l_k<2>), dim3(srf_ceil_div(A_out, 64)), dim3(256), 0, st, SRF_ARGS);
                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_c16_k<2>), dim3(srf_ceil_div(A_out, 64)), dim3(256), 0, st, SRF_ARGS);

@@ -348,12 +348,21 @@ def rulebook_strided_bitmap(indices, level, ksize, stride, pad, out_capacity=Non
 KERNEL_TIMING = None
 
 
+def spconv_packed_supported(K, Cin, Cout):
+    """True for the layer shapes with a packed-weight kernel (include/srfdet3d.h); a host call, no GPU work."""
+    return _lib.lib().srf_spconv_packed_weight_bytes(K, Cin, Cout) > 0
+
+
 def pack_spconv_weights(weight):
-    """(K,Cin,Cout) -> the LDS operand image srf_spconv_fwd_packed streams (once per layer; weights are constants)."""
+    """(K,Cin,Cout) -> the operand layout srf_spconv_fwd_packed streams (once per layer; weights are constants), or None
+    for a shape without a packed form."""
     weight = _dev(weight, "weight", torch.float32)
     K, Cin, Cout = weight.shape
     L = _lib.lib()
-    packed = _empty((L.srf_spconv_packed_weight_bytes(K, Cin, Cout) // 4,), torch.float32, weight.device)
+    nbytes = L.srf_spconv_packed_weight_bytes(K, Cin, Cout)
+    if nbytes == 0:
+        return None
+    packed = _empty((nbytes // 4,), torch.float32, weight.device)
     check(L.srf_spconv_pack_weights(_ptr(weight), K, Cin, Cout, _ptr(packed), _stream()), "spconv_pack_weights")
     return packed
 
@@ -408,8 +417,9 @@ def spconv_tiles(nbr, rows_dev=None):
 def spconv_fwd(feats, weight, nbr, alpha=None, beta=None, residual=None, relu=False, pair_counts=None, packed=None,
                rows_dev=None, tiles=None, subm=False):
     """feats (A_in,Cin); weight (K,Cin,Cout); nbr (K,A_out) (row stride nbr.stride(0)) -> (A_out,Cout).
-    `packed` = pack_spconv_weights(weight) selects the packed-weight kernel (Cout >= 32, Cin % 4 == 0);
-    `tiles` = spconv_tiles(nbr) lets its 128-channel variant balance the workgroups by pair count."""
+    `packed` = pack_spconv_weights(weight) selects the packed-weight kernel for inputs below 2 GiB (larger ones and
+    packed=None run srf_spconv_fwd, with the same bits); `tiles` = spconv_tiles(nbr) lets its 64- / 128-channel variants
+    balance the workgroups by pair count."""
     if torch.is_grad_enabled() and (feats.requires_grad or weight.requires_grad or (residual is not None and residual.requires_grad)
                                     or (alpha is not None and alpha.requires_grad) or (beta is not None and beta.requires_grad)):
         # a gradient is wanted: plain convolution through the autograd Function (srf_spconv_bwd_data / _bwd_weight), the
@@ -437,7 +447,7 @@ def spconv_fwd(feats, weight, nbr, alpha=None, beta=None, residual=None, relu=Fa
     if timing is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    if packed is not None and Cout >= 32 and Cin % 4 == 0 and feats.shape[0] > 0:
+    if packed is not None and 0 < feats.shape[0] * Cin * 4 < 2 ** 31:   # the packed kernels address the input with 32-bit offsets
         check(_lib.lib().srf_spconv_fwd_packed(_ptr(feats), feats.shape[0], Cin, _ptr(packed), K, _ptr(nbr),
                                                nbr.stride(0) if A_out > 0 else 0, A_out, Cout, _ptr(alpha), _ptr(beta),
                                                _ptr(residual), int(bool(relu)), _ptr(out), _ptr(rows_dev),

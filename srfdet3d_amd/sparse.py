@@ -187,10 +187,11 @@ class _SparseConv(SparseModule):
         An index-only tensor (`x.features is None`) gets the layer's rulebook (and row ranges) built and cached and comes back
         index-only: the encoder runs that dry pass on a second stream, ahead of the convolutions (middle_encoders.py)."""
         nbr, counts, out_idx, oshape, rows_dev = self._rulebook(x)
-        use_packed = not self.training and self.out_channels >= 32 and self.in_channels % 4 == 0
+        K = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
+        use_packed = not self.training and ops.spconv_packed_supported(K, self.in_channels, self.out_channels)
         tiles = None
         if (use_packed and ops.spconv_tiles_wanted(self.in_channels, self.out_channels) and nbr.shape[1] > 0
-                and (self.subm or self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2] == 27)):
+                and (self.subm or K == 27)):
             # balanced row ranges, one set per rulebook: shared by the SubM layers of a level; a 27-offset strided conv gains more
             # from them than they cost (64 -> 128 on the nuScenes encoder: 92 -> 76 us, its steps 36 +- 37 -> 35 +- 19 per workgroup;
             # the three small launches of the cut run on the index stream of the graph, ahead of the convolutions); conv_out (3
@@ -209,7 +210,6 @@ class _SparseConv(SparseModule):
                     tiles = x.indice_dict[tkey] = ops.spconv_tiles(nbr, rows_dev)
         if x.features is None:
             return SparseConvTensor(None, out_idx, oshape, x.batch_size, x.indice_dict, rows_dev)
-        K = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
         w = self.weight.view(K, self.in_channels, self.out_channels)
         alpha = beta = None
         if bn is not None:

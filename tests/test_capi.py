@@ -46,6 +46,14 @@ def test_host_side_helpers():
     assert L.srf_spconv_fwd(None, 0, 16, None, 27, None, 0, 10, 24, None, None, None, 0, None, None, None) == -1
     assert L.srf_roi_extract(None, 0, 128, None, 0, 7, 2, 56.0, None, 0, 0, 0, 0, None, None) == -1
     assert L.srf_spconv_fwd_packed(None, 0, 128, None, 27, None, 0, 10, 128, None, None, None, 0, None, None, None, None) == -1
+    # packed weights exist for exactly these (K, Cin, Cout) (include/srfdet3d.h); 0 bytes = no packed form
+    host = ctypes.create_string_buffer(16)
+    for K, cin, cout in ((27, 16, 32), (27, 32, 32), (27, 32, 64), (27, 64, 64), (27, 64, 128), (27, 128, 128), (3, 128, 128)):
+        assert L.srf_spconv_packed_weight_bytes(K, cin, cout) > 0, (K, cin, cout)
+    for K, cin, cout in ((27, 48, 64), (27, 16, 64), (27, 32, 128), (3, 32, 32), (27, 16, 16), (27, 5, 16)):
+        assert L.srf_spconv_packed_weight_bytes(K, cin, cout) == 0, (K, cin, cout)
+        assert L.srf_spconv_pack_weights(host, K, cin, cout, host, None) == -3    # refused before any launch
+    assert L.srf_spconv_fwd_packed(None, 10, 48, None, 27, None, 10, 10, 64, None, None, None, 0, None, None, None, None) == -3
     assert L.srf_spconv_tiles_count(35000) == 512 and L.srf_spconv_tiles_count(100) == 3 and L.srf_spconv_tiles_count(0) == 1
     assert L.srf_spconv_tiles_workspace_bytes(35000) >= 35000 * 4
     assert L.srf_spconv_tiles_build(None, 0, 27, 10, None, None, None, None) == -1

@@ -95,6 +95,25 @@ def test_models_build_with_reference_key_names(name, np_, n_params_m):
         assert sum(p.numel() for p in model.bbox_head.head_series_lidar[0].parameters()) == 12757387
 
 
+def test_sparse_encoders_have_packed_kernels_for_wide_layers():
+    """every sparse convolution with Cout >= 32 of every reference config's SparseEncoderCustom has a packed-weight kernel
+    (srf_spconv_fwd_packed): no inference workload runs the unpacked 32- / 64- / 128-channel forms."""
+    from srfdet3d_amd import ops
+    from srfdet3d_amd.compat.registry import build_middle_encoder
+    from srfdet3d_amd.sparse import _SparseConv
+    shapes = set()
+    for name in sorted(NAMES):
+        enc = workloads.model_cfg(name).get("pts_middle_encoder")
+        if enc is None or enc["type"] != "SparseEncoderCustom":
+            continue
+        for m in build_middle_encoder(enc).modules():
+            if isinstance(m, _SparseConv) and m.out_channels >= 32:
+                K = m.kernel_size[0] * m.kernel_size[1] * m.kernel_size[2]
+                assert ops.spconv_packed_supported(K, m.in_channels, m.out_channels), (name, K, m.in_channels, m.out_channels)
+                shapes.add((K, m.in_channels, m.out_channels))
+    assert {(27, 16, 32), (27, 32, 32), (27, 64, 64), (27, 128, 128), (3, 128, 128)} <= shapes, shapes
+
+
 def test_lc_head_builds_with_fusion_stage():
     m = workloads.model_cfg("srfdet_voxel_nusc_LC")
     hc = dict(m.bbox_head)

@@ -79,7 +79,8 @@ def test_rulebook_empty_and_single(dev):
 
 
 @pytest.mark.parametrize("cin,cout,K", [(5, 16, 27), (16, 16, 27), (16, 32, 27), (32, 32, 27), (32, 64, 27),
-                                         (64, 64, 27), (64, 128, 27), (128, 128, 27), (128, 128, 3), (4, 16, 27)])
+                                         (64, 64, 27), (64, 128, 27), (128, 128, 27), (128, 128, 3), (4, 16, 27),
+                                         (48, 64, 27)])
 def test_spconv_fwd_exact(dev, cin, cout, K):
     rng = np.random.default_rng(cin * 1000 + cout)
     idx = _level1(n=6000)
@@ -105,8 +106,10 @@ def test_spconv_fwd_exact(dev, cin, cout, K):
         # exact: both sides are the same f32 fma chain (k ascending, c ascending); == treats +0/-0 alike
         assert np.array_equal(got, ref), f"max abs diff {np.abs(got - ref).max()}"
         if cout >= 32 and cin % 4 == 0:  # packed-weight kernel: same chain, different operand staging
+            packed = ops.pack_spconv_weights(tt(W))
+            assert (packed is None) == ((cin, cout) == (48, 64))   # a shape without a packed form runs srf_spconv_fwd
             got = ops.spconv_fwd(tt(feats), tt(W), tt(nbr), tt(alpha) if use_bn else None, tt(beta) if use_bn else None,
-                                 tt(res) if use_res else None, relu, packed=ops.pack_spconv_weights(tt(W))).cpu().numpy()
+                                 tt(res) if use_res else None, relu, packed=packed).cpu().numpy()
             assert np.array_equal(got, ref), f"packed: max abs diff {np.abs(got - ref).max()}"
             if ops.spconv_tiles_wanted(cin, cout):  # the same kernel walking work-balanced row ranges / a mask-sorted row order
                 tiles = ops.spconv_order(tt(nbr)) if ops.spconv_order_wanted(cin, cout) else ops.spconv_tiles(tt(nbr))
@@ -114,6 +117,30 @@ def test_spconv_fwd_exact(dev, cin, cout, K):
                                      tt(res) if use_res else None, relu, packed=ops.pack_spconv_weights(tt(W)),
                                      tiles=tiles).cpu().numpy()
                 assert np.array_equal(got, ref), f"packed+tiles: max abs diff {np.abs(got - ref).max()}"
+
+
+@pytest.mark.parametrize("C,rows", [(128, 2 ** 22 + 1024), (32, 2 ** 24 + 1024)])
+def test_spconv_packed_input_of_2gib_runs_unpacked(dev, C, rows):
+    """an input of 2 GiB or more is beyond the 32-bit buffer offsets of the packed kernels: spconv_fwd(..., packed=) runs
+    srf_spconv_fwd on it, with the oracle's bits.  The rulebook points into the top rows of the input."""
+    rng = np.random.default_rng(C)
+    idx = _level1(n=3000)
+    nbr, _ = O.rulebook_subm(idx, SHAPE1, [3, 3, 3])
+    A = nbr.shape[1]
+    top = rows - A
+    feats = rng.standard_normal((A, C)).astype(np.float32)
+    W = (rng.standard_normal((27, C, C)) / np.sqrt(C * 3)).astype(np.float32)
+    ref = O.spconv_fwd(feats, W, nbr)
+    big = torch.zeros((rows, C), dtype=torch.float32, device=dev)
+    assert big.numel() * 4 >= 2 ** 31
+    big[top:] = torch.from_numpy(feats).to(dev)
+    t_nbr = torch.from_numpy(np.where(nbr >= 0, nbr + top, -1).astype(np.int32)).to(dev)
+    t_W = torch.from_numpy(W).to(dev)
+    packed = ops.pack_spconv_weights(t_W)
+    assert packed is not None
+    got = ops.spconv_fwd(big, t_W, t_nbr, packed=packed).cpu().numpy()
+    del big
+    assert np.array_equal(got, ref), f"max abs diff {np.abs(got - ref).max()}"
 
 
 @pytest.mark.parametrize("n,live", [(6000, None), (6000, 4100), (40, None), (3000, 0)])

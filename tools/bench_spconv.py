@@ -40,7 +40,12 @@ def main():
             W = (torch.randn(27, C, C, generator=g) * 0.05).to(dev)
             al, be = torch.rand(C, generator=g).to(dev) + 0.5, torch.randn(C, generator=g).to(dev)
             pk = ops.pack_spconv_weights(W) if (C >= 32 and not a.unpacked) else None
-            tiles = ops.spconv_tiles(nbr) if (pk is not None and ops.spconv_tiles_wanted(C, C) and not a.no_tiles) else None
+            tiles = None
+            if pk is not None and not a.no_tiles:
+                if C == 32:   # the 32-channel kernel reads `tiles` as a row-order plan, taken as the encoder takes it (sparse.py)
+                    tiles = ops.spconv_order(nbr) if ops.spconv_order_wanted(C, C, rows=A) else None
+                elif ops.spconv_tiles_wanted(C, C):
+                    tiles = ops.spconv_tiles(nbr)
             for _ in range(3):
                 ops.spconv_fwd(f, W, nbr, al, be, f, True, packed=pk, tiles=tiles)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -66,9 +66,9 @@ TARGETS = {
                 "included (srf_densify_bev); per frame", 3),
     "roi": (["tools/prof_lidar_frame.py", "3"], ("srf_roi_extract_k",),
             "multi-level RoIAlign gather (K7), 5 stages x 200 RoIs on the channels-last BEV pyramid; per frame", 3),
-    "spconv128": (["tools/bench_spconv.py", "--levels", "4", "--reps", "8"], ("srf_spconv_gs_k<4, 128>", "srf_spconv_gsp_k<4, 128"),
+    "spconv128": (["tools/bench_spconv.py", "--levels", "4", "--reps", "8"], ("srf_spconv_gsp_k<4, 128",),
                   "SubM 128->128 on the 5x184x184 level of frame 2000 (A=34992), BN + residual + ReLU epilogue"),
-    "spconv64": (["tools/bench_spconv.py", "--levels", "3", "--reps", "8"], ("srf_spconv_gs_k<2, 64>", "srf_spconv_gsp_k<2, 64"),
+    "spconv64": (["tools/bench_spconv.py", "--levels", "3", "--reps", "8"], ("srf_spconv_gsp_k<2, 64",),
                  "SubM 64->64 on the 11x368x368 level of frame 2000, BN + residual + ReLU epilogue"),
 }
 
