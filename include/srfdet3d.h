@@ -116,6 +116,57 @@ int srf_image_prepare(const unsigned char *images, int V, int H, int W, const fl
                       const float *std /*host[3]*/, int to_rgb, int Hp, int Wp, float *out, srf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f-5  train-time augmentation: the 3-D transforms of the reference's train pipelines (GlobalRotScaleTrans,
+ * RandomFlip3D, PointsRangeFilter, ObjectRangeFilter, ObjectNameFilter; mmdet3d 1.0.0rc6 LiDARPoints /
+ * LiDARInstance3DBoxes semantics, e.g. configs/nus/srfdet_voxel_nusc_L.py train_pipeline) and GridMask
+ * (mmdet3d_plugin/models/utils/grid_mask.py:72-128, applied at srfdet.py:189-190).
+ * Random draws and sin / cos / arctan2 stay with the caller (host, float32); the device does correctly rounded
+ * + - * / floor in the reference's order only.
+ *
+ * steps: bitmask, applied in this order; a clear bit skips the step (it is not applied as an identity):
+ *   1 rotate     xyz <- xyz @ [[c, s, 0], [-s, c, 0], [0, 0, 1]] (products rounded one by one, summed left to
+ *                right, zero terms kept)
+ *   2 scale      xyz *= scale
+ *   4 translate  xyz += t
+ *   8 h-flip     y = -y
+ *  16 v-flip     x = -x
+ * aug: host[7] = sin, cos, yaw_add, scale, tx, ty, tz (may be NULL when steps == 0).
+ *
+ * srf_points_augment: points (n, nf >= 3); the steps on channels 0-2, channels >= 3 copied unchanged; then, when
+ * pc_range (host[6]) is given, the PointsRangeFilter test of srf_points_filter (strict inequalities).  The kept
+ * points are written in their original order to out_points (room for n rows); out_index (may be NULL) receives
+ * their source rows; *num_out (device int) their count.  workspace: srf_points_augment_workspace_bytes(n).
+ *
+ * srf_boxes_augment: boxes (n, box_dim = 7 | 9) [x, y, z, dx, dy, dz, yaw (, vx, vy)] with int64 labels (n):
+ *   rotate     centre as above, yaw += yaw_add, [vx, vy] @ rot_mat_T[:2, :2];
+ *   scale      columns 0-5 and 7- *= scale;
+ *   translate  columns 0-2 += t;
+ *   h-flip     y, vy negated, yaw = -yaw;
+ *   v-flip     x, vx negated, yaw = -yaw + float32(pi);
+ * then ObjectRangeFilter when bev_range (host[4] = xmin, ymin, xmax, ymax) is given (kept iff x > xmin && y > ymin &&
+ * x < xmax && y < ymax, then yaw <- yaw - floor(yaw / P + 0.5) * P with P = float32(2 pi)), and ObjectNameFilter when
+ * num_classes > 0 (kept iff 0 <= label < num_classes).  Kept boxes and labels are compacted in their original order
+ * (out_boxes room for n rows, out_labels n); out_index (may be NULL) receives their source rows; *num_out (device
+ * int) their count.  workspace: srf_boxes_augment_workspace_bytes(n).
+ *
+ * srf_grid_mask: out = in * mask over `planes` planes of H x W float32 (out of place; in is not changed).  With
+ * hh = int(1.5 H), row y is in a stripe iff use_h && q = y + (hh - H) / 2 - st_h satisfies q >= 0, q / d < hh / d and
+ * q % d < l (columns alike with W, st_w, use_w).  mode 1: mask = row or column in a stripe; mode 0: its negation.
+ * A multiplication, so -0.0 and NaN come out as the reference's `x * mask`.  2 <= d, 1 <= l < d, 0 <= st_h, st_w < d.
+ * ------------------------------------------------------------------------------------------------------- */
+size_t srf_points_augment_workspace_bytes(int n);
+int srf_points_augment(const float *points, int n, int nf, int steps, const float *aug /*host[7]*/,
+                       const float *pc_range /*host[6] or NULL*/, float *out_points, int *out_index, int *num_out,
+                       void *workspace, srf_stream_t stream);
+size_t srf_boxes_augment_workspace_bytes(int n);
+int srf_boxes_augment(const float *boxes, const long long *labels, int n, int box_dim, int steps,
+                      const float *aug /*host[7]*/, const float *bev_range /*host[4] or NULL*/, int num_classes,
+                      float *out_boxes, long long *out_labels, int *out_index, int *num_out, void *workspace,
+                      srf_stream_t stream);
+int srf_grid_mask(const float *in, int planes, int H, int W, int d, int l, int st_h, int st_w, int use_h, int use_w,
+                  int mode, float *out, srf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * K2  dynamic voxelization.
  * Replaces mmcv.ops.Voxelization(max_num_points=-1).forward as called from SRFDet.voxelize,
  * mmdet3d_plugin/models/detectors/srfdet.py:233-247.

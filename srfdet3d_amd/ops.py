@@ -79,6 +79,67 @@ def points_filter(points, pc_range=None, close_radius=0.0, static=False, with_in
     return (out[:M], index[:M]) if with_index else out[:M]
 
 
+# srf_points_augment / srf_boxes_augment step bits (include/srfdet3d.h f-5), applied in this order
+AUG_ROTATE, AUG_SCALE, AUG_TRANSLATE, AUG_FLIP_H, AUG_FLIP_V = 1, 2, 4, 8, 16
+
+
+def points_augment(points, steps, aug=None, pc_range=None, with_index=False):
+    """GlobalRotScaleTrans / RandomFlip3D steps on channels 0-2 (`steps`: AUG_* bits; a clear bit skips the step) and, with
+    pc_range, the PointsRangeFilter test, as one order-preserving compaction -> kept points (M, nf) [, their source rows].
+    aug = (sin, cos, yaw_add, scale, tx, ty, tz), float32 values computed on the host.  One D2H sync for M."""
+    points = _dev(points, "points", torch.float32)
+    n, nf = points.shape
+    L = _lib.lib()
+    dev = points.device
+    out = _empty((max(n, 1), nf), torch.float32, dev)
+    index = _empty((max(n, 1),), torch.int32, dev) if with_index else None
+    num = _empty((1,), torch.int32, dev)
+    ws = _empty((max(L.srf_points_augment_workspace_bytes(n), 4),), torch.uint8, dev)
+    check(L.srf_points_augment(_ptr(points), n, nf, int(steps), hf(aug) if aug is not None else None,
+                               hf(pc_range) if pc_range is not None else None, _ptr(out), _ptr(index), _ptr(num), _ptr(ws),
+                               _stream()), "points_augment")
+    M = int(num.item())
+    return (out[:M], index[:M]) if with_index else out[:M]
+
+
+def boxes_augment(boxes, labels, steps, aug=None, bev_range=None, num_classes=0, with_index=False):
+    """The box half of `points_augment` on (n, 7 | 9) LiDAR boxes and their int64 labels, then ObjectRangeFilter (bev_range =
+    (xmin, ymin, xmax, ymax), followed by limit_yaw) and ObjectNameFilter (num_classes > 0: 0 <= label < num_classes), one
+    order-preserving compaction of boxes and labels -> (boxes (M, box_dim), labels (M,) [, source rows]).  One D2H sync."""
+    boxes = _dev(boxes, "boxes", torch.float32)
+    labels = _dev(labels, "labels", torch.int64)
+    n, box_dim = boxes.shape
+    if labels.shape != (n,):
+        raise RuntimeError(f"srfdet3d_amd: `labels` must have shape ({n},), got {tuple(labels.shape)}")
+    L = _lib.lib()
+    dev = boxes.device
+    out = _empty((max(n, 1), box_dim), torch.float32, dev)
+    out_labels = _empty((max(n, 1),), torch.int64, dev)
+    index = _empty((max(n, 1),), torch.int32, dev) if with_index else None
+    num = _empty((1,), torch.int32, dev)
+    ws = _empty((max(L.srf_boxes_augment_workspace_bytes(n), 4),), torch.uint8, dev)
+    check(L.srf_boxes_augment(_ptr(boxes), _ptr(labels), n, box_dim, int(steps), hf(aug) if aug is not None else None,
+                              hf(bev_range) if bev_range is not None else None, int(num_classes), _ptr(out), _ptr(out_labels),
+                              _ptr(index), _ptr(num), _ptr(ws), _stream()), "boxes_augment")
+    M = int(num.item())
+    res = (out[:M], out_labels[:M])
+    return res + (index[:M],) if with_index else res
+
+
+def grid_mask(x, d, l, st_h, st_w, use_h=True, use_w=True, mode=1):
+    """GridMask's `x * mask` out of place on a (..., H, W) float32 tensor: the stripe mask of grid_mask.py:72-128 (rotate 0,
+    no offset) evaluated per pixel, never materialised.  x itself is not changed."""
+    x = _dev(x, "x", torch.float32)
+    if x.dim() < 2:
+        raise RuntimeError("srfdet3d_amd: grid_mask expects (..., H, W)")
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    planes = x.numel() // (H * W) if H * W else 0
+    out = torch.empty_like(x)
+    check(_lib.lib().srf_grid_mask(_ptr(x), planes, H, W, int(d), int(l), int(st_h), int(st_w), int(bool(use_h)),
+                                   int(bool(use_w)), int(mode), _ptr(out), _stream()), "grid_mask")
+    return out
+
+
 def image_prepare(images_u8, mean, std, to_rgb=False, size_divisor=32, size=None):
     """(V, H, W, 3) uint8 decoded views -> (V, 3, Hp, Wp) float32: NormalizeMultiviewImage + PadMultiViewImage + the
     HWC -> CHW transpose of the format bundle in one pass.  Padding to `size` (Hp, Wp) or up to a multiple of

@@ -10,6 +10,7 @@ from ..compat.cnn import BaseModule
 from ..compat.registry import (DETECTORS, build_backbone, build_head, build_middle_encoder, build_neck,
                                build_voxel_encoder)
 from ..voxel_layer import Voxelization
+from .grid_mask import GridMask
 from .voxel_encoders import HardSimpleVFE
 
 
@@ -25,7 +26,8 @@ class SRFDet(BaseModule):
         if use_img:
             self.img_backbone = build_backbone(img_backbone) if img_backbone is not None else None
             self.img_neck = build_neck(img_neck) if img_neck is not None else None
-            self.grid_mask = None  # train-time augmentation only; identity in eval (grid_mask.py:89)
+            # train-time augmentation (srfdet.py:47-48); applied only when use_grid_mask and only in training
+            self.grid_mask = GridMask(True, True, rotate=1, offset=False, ratio=0.5, mode=1, prob=0.7)
         if pts_voxel_layer:
             self.pts_voxel_layer = Voxelization(**pts_voxel_layer)
             self.pts_voxel_layer_cfg = pts_voxel_layer
@@ -194,12 +196,16 @@ class SRFDet(BaseModule):
         return img_feats, point_feats
 
     def extract_img_feat(self, img, img_metas):
-        """(B, N, 3, H, W) -> list of (B, N, C, h, w) per pyramid level (srfdet.py:175-202)."""
+        """(B, N, 3, H, W) -> list of (B, N, C, h, w) per pyramid level (srfdet.py:175-202).  With use_grid_mask, training
+        batches go through GridMask first (srfdet.py:189-190); eval never calls it (the reference's GridMask draws one
+        np.random.rand() in eval too and then returns its input unchanged)."""
         B = img.size(0)
         for meta in img_metas:
             meta.update(input_shape=img.shape[-2:])
         if img.dim() == 5:
             img = img.reshape(-1, *img.shape[2:])
+        if self.use_grid_mask and self.training:
+            img = self.grid_mask(img)
         with torch.autocast(img.device.type, dtype=self.img_autocast_dtype, enabled=self.img_autocast_dtype is not None):
             feats = self.img_backbone(img)
             if isinstance(feats, dict):
