@@ -5,8 +5,8 @@ encoders), SparseConvTensor.dense(), DynamicScatter mean / max, and a LiDAR-only
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+from spconv_ref import conv_ref_autograd, dense_grads as _dense_grads
 from srfdet3d_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -15,23 +15,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def dev():
     return torch.device("cuda:0")
-
-
-def _dense_grads(idx, shape, feats, W, gout_rows, out_idx, out_shape, stride, pad, ksize):
-    """float64 reference: conv3d on the densified grid; the loss is sum(out[active outputs] * gout_rows)."""
-    B = int(idx[:, 0].max()) + 1
-    cin, cout = W.shape[1], W.shape[2]
-    f = torch.from_numpy(feats).double().requires_grad_(True)
-    w = torch.from_numpy(W).double().requires_grad_(True)
-    i = torch.from_numpy(idx).long()
-    # channels-last dense grid so that an active site is one row: (B, D, H, W, C) -> (B, C, D, H, W)
-    dense = torch.zeros(B, *shape, cin, dtype=torch.float64).index_put((i[:, 0], i[:, 1], i[:, 2], i[:, 3]), f).permute(0, 4, 1, 2, 3)
-    w5 = w.view(*ksize, cin, cout).permute(4, 3, 0, 1, 2)
-    full = F.conv3d(dense, w5, stride=stride, padding=pad)
-    o = torch.from_numpy(out_idx).long()
-    out = full[o[:, 0], :, o[:, 1], o[:, 2], o[:, 3]]
-    (out * torch.from_numpy(gout_rows).double()).sum().backward()
-    return out.detach().numpy(), f.grad.numpy(), w.grad.numpy()
 
 
 @pytest.mark.parametrize("cin,cout", [(5, 16), (4, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128)])
@@ -87,16 +70,27 @@ def test_fused_epilogue_route_is_differentiable(dev):
     A = len(idx)
     f = torch.from_numpy(rng.standard_normal((A, 32)).astype(np.float32)).to(dev)
     w = torch.from_numpy((rng.standard_normal((27, 32, 32)) * 0.1).astype(np.float32)).to(dev)
-    alpha = torch.rand(32, device=dev) + 0.5
-    beta = torch.randn(32, device=dev)
-    res = torch.randn(A, 32, device=dev)
+    alpha = torch.from_numpy(rng.uniform(0.5, 1.5, 32).astype(np.float32)).to(dev)
+    beta = torch.from_numpy(rng.standard_normal(32).astype(np.float32)).to(dev)
+    res = torch.from_numpy(rng.standard_normal((A, 32)).astype(np.float32)).to(dev)
     with torch.no_grad():
         want = ops.spconv_fwd(f, w, nbr, alpha, beta, res, True, subm=True)
-    f2, w2 = f.clone().requires_grad_(True), w.clone().requires_grad_(True)
-    got = ops.spconv_fwd(f2, w2, nbr, alpha, beta, res, True, subm=True)
+    f2, w2, r2 = f.clone().requires_grad_(True), w.clone().requires_grad_(True), res.clone().requires_grad_(True)
+    got = ops.spconv_fwd(f2, w2, nbr, alpha, beta, r2, True, subm=True)
     torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-5)
-    got.sum().backward()
+    gout = torch.from_numpy(rng.standard_normal((A, 32)).astype(np.float32)).to(dev)
+    (got * gout).sum().backward()
     assert f2.grad is not None and w2.grad is not None and torch.isfinite(w2.grad).all() and w2.grad.abs().sum() > 0
+    # the same alpha / beta / residual / ReLU composition in float64 autograd on the rulebook reference.  The ReLU mask is the
+    # kernel's: an element whose pre-activation lies within float32 rounding of zero may fall on either side, and only such
+    # elements may disagree with float64's own sign
+    f64, w64, r64 = (t.double().requires_grad_(True) for t in (f, w, res))
+    pre = conv_ref_autograd(nbr, f64, w64) * alpha.double() + beta.double() + r64
+    mask = got.detach() > 0
+    assert (pre.detach().abs()[mask != (pre.detach() > 0)] <= 1e-5).all()
+    (pre * mask * gout.double()).sum().backward()
+    for name, a, b in (("d_feats", f2.grad, f64.grad), ("d_W", w2.grad, w64.grad), ("d_residual", r2.grad, r64.grad)):
+        assert (a.double() - b).abs().max() <= 1e-5 * b.abs().max(), name
 
 
 def test_densify_and_scatter_gradients(dev):
