@@ -167,6 +167,54 @@ int srf_grid_mask(const float *in, int planes, int H, int W, int d, int l, int s
                   int mode, float *out, srf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f-6  GT-database sampling and per-object noise of the LiDAR-only train pipelines (mmdet3d 1.0.0rc6 ObjectSample /
+ * DataBaseSampler and ObjectNoise / noise_per_object_v3_, e.g. configs/kitti/srfdet_voxel_kitti_L.py train_pipeline).
+ * The caller draws every random number and computes the box geometry on the host in float32: BEV corners (4 x [x, y],
+ * clockwise as center_to_corner_box2d) and surface planes (6 x [a, b, c, d] as surface_equ_3d of corner_to_surfaces_3d).
+ * The device does correctly rounded float32 + - * and compares in the reference's order, and float64 + where the
+ * reference adds float64 noise.
+ *
+ * srf_points_in_boxes: out_box[i] = the first box b (box_mask[b] != 0 when box_mask is given) with
+ * ((x a + y b) + z c) + d < 0 for all six planes of b, else -1; points (n, nf >= 3), planes (m, 6, 4).  num_outside
+ * (device int, may be NULL) receives the count of -1s.  m <= 512, else SRF_EUNSUPPORTED.
+ *
+ * srf_box_collision_matrix: out[i * K + j] = box_collision_test(boxes[i], qboxes[j]) (uint8): the axis-aligned hulls
+ * overlap (strictly) and either two edges cross or all corners of one box lie strictly inside the other.
+ *
+ * srf_box_collision_accept: the greedy rejection of DataBaseSampler.sample_all.  fixed (n_fixed, 4, 2) = the GT boxes'
+ * corners, cand (n_cand, 4, 2) the candidates' grouped by class, class c = [class_offsets[c], class_offsets[c + 1])
+ * (device int[num_classes + 1]), classes in sampling order.  Candidate i is rejected iff it collides (as `boxes`) with a
+ * fixed box, an accepted candidate of an earlier class, or a not-rejected candidate of its own class other than itself,
+ * the later ones included; accept[i] = 1 / 0.  One workgroup; n_fixed + n_cand <= 2048, else SRF_EUNSUPPORTED.
+ *
+ * srf_object_sample_merge: out rows [0, s) = sampled (s, nf) with columns 0-2 + the centre (obj_centres (k, 3)) of
+ * their object o (rows [obj_offsets[o], obj_offsets[o + 1]); obj_offsets device int[k + 1], obj_offsets[0] = 0), then
+ * the points (n, nf) with point_box[i] < 0 (srf_points_in_boxes of the accepted boxes) in their order; *num_out
+ * (device int) = s + their count.  out has room for s + n rows.  workspace: srf_object_sample_merge_workspace_bytes.
+ *
+ * srf_object_noise: m boxes (m, box_dim = 7 | 9), num_try tries each: rot_sc (m, num_try, 2) = float32 sin, cos of
+ * the float64 angles rot (m, num_try), loc (m, num_try, 3) float64 translations; corners (m, 4, 2) and planes
+ * (m, 6, 4) of the unmoved boxes.  Box i (in order) takes its first try whose moved BEV corners (float32 rotation about
+ * its centre, then float32(float64 corner + (float64 centre + loc))) collide with no other box's current corners;
+ * chosen[i] = that try or -1.  Then every point inside a box (the first one by index, original planes) becomes
+ * float32(float64(rotate(p - centre) + centre) + loc) (a box with chosen -1 uses angle 0 and loc 0), the others are
+ * copied; out_boxes: xyz = float32(float64 xyz + loc), yaw = float32(float64 yaw + rot).  m <= 512, else
+ * SRF_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------------- */
+int srf_points_in_boxes(const float *points, int n, int nf, const float *planes, int m, const int *box_mask, int *out_box,
+                        int *num_outside, srf_stream_t stream);
+int srf_box_collision_matrix(const float *boxes, int N, const float *qboxes, int K, unsigned char *out, srf_stream_t stream);
+int srf_box_collision_accept(const float *fixed, int n_fixed, const float *cand, int n_cand, const int *class_offsets,
+                             int num_classes, int *accept, srf_stream_t stream);
+size_t srf_object_sample_merge_workspace_bytes(int n, int s);
+int srf_object_sample_merge(const float *points, int n, int nf, const int *point_box, const float *sampled, int s,
+                            const int *obj_offsets, const float *obj_centres, int k, float *out, int *num_out, void *workspace,
+                            srf_stream_t stream);
+int srf_object_noise(const float *points, int n, int nf, const float *boxes, int m, int box_dim, const float *corners,
+                     const float *planes, const float *rot_sc, const double *rot, const double *loc, int num_try,
+                     float *out_points, float *out_boxes, int *chosen, srf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * K2  dynamic voxelization.
  * Replaces mmcv.ops.Voxelization(max_num_points=-1).forward as called from SRFDet.voxelize,
  * mmdet3d_plugin/models/detectors/srfdet.py:233-247.

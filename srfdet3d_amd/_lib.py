@@ -40,6 +40,12 @@ SIGNATURES = {
     "srf_boxes_augment_workspace_bytes": (c_size_t, [c_int]),
     "srf_boxes_augment": (c_int, [_P, _P, c_int, c_int, c_int, _HF, _HF, c_int, _P, _P, _P, _P, _P, _P]),
     "srf_grid_mask": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "srf_points_in_boxes": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
+    "srf_box_collision_matrix": (c_int, [_P, c_int, _P, c_int, _P, _P]),
+    "srf_box_collision_accept": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, _P]),
+    "srf_object_sample_merge_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "srf_object_sample_merge": (c_int, [_P, c_int, c_int, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, _P]),
+    "srf_object_noise": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
     "srf_dynamic_voxelize": (c_int, [_P, c_int, c_int, _HF, _HF, _HI, _P, _P]),
     "srf_hard_voxelize_workspace_bytes": (c_size_t, [c_int, c_int]),
     "srf_hard_voxelize": (c_int, [_P, c_int, c_int, _HF, _HF, _HI, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P,

@@ -59,6 +59,7 @@ NORM_LAYERS = Registry("norm_layer")
 CONV_LAYERS = Registry("conv_layer")
 ACTIVATION_LAYERS = Registry("activation_layer")
 PIPELINES = Registry("pipeline")
+OBJECTSAMPLERS = Registry("object_sampler")
 
 
 def build_voxel_encoder(cfg):

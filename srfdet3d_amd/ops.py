@@ -140,6 +140,98 @@ def grid_mask(x, d, l, st_h, st_w, use_h=True, use_w=True, mode=1):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- GT sampling / object noise
+def points_in_boxes(points, planes, box_mask=None, num_outside=None):
+    """First box per point whose six surface planes (m, 6, 4) [a, b, c, d] all give ((x a + y b) + z c) + d < 0, else -1
+    -> int32 (n,).  box_mask (m,) int32: boxes with 0 are skipped.  num_outside: a device int32 (1,) that receives the count
+    of -1s.  No host sync."""
+    points = _dev(points, "points", torch.float32)
+    planes = _dev(planes, "planes", torch.float32)
+    n, nf = points.shape
+    m = planes.shape[0]
+    if planes.shape[1:] != (6, 4):
+        raise RuntimeError(f"srfdet3d_amd: `planes` must be (m, 6, 4), got {tuple(planes.shape)}")
+    mask = _dev(box_mask, "box_mask", torch.int32) if box_mask is not None else None
+    if num_outside is not None and (num_outside.dtype != torch.int32 or not num_outside.is_cuda or num_outside.numel() < 1):
+        raise RuntimeError("srfdet3d_amd: `num_outside` must be a device int32 tensor")
+    out = _empty((max(n, 1),), torch.int32, points.device)
+    check(_lib.lib().srf_points_in_boxes(_ptr(points), n, nf, _ptr(planes), m, _ptr(mask), _ptr(out), _ptr(num_outside), _stream()),
+          "points_in_boxes")
+    return out[:n]
+
+
+def box_collision_matrix(boxes, qboxes):
+    """box_collision_test of every (boxes[i], qboxes[j]) pair of BEV corners (N, 4, 2) x (K, 4, 2) -> bool (N, K)."""
+    boxes = _dev(boxes, "boxes", torch.float32)
+    qboxes = _dev(qboxes, "qboxes", torch.float32)
+    N, K = boxes.shape[0], qboxes.shape[0]
+    out = _empty((N, K), torch.uint8, boxes.device)
+    check(_lib.lib().srf_box_collision_matrix(_ptr(boxes), N, _ptr(qboxes), K, _ptr(out), _stream()), "box_collision_matrix")
+    return out.bool()
+
+
+def box_collision_accept(fixed, cand, class_offsets, out=None):
+    """The greedy rejection of DataBaseSampler.sample_all: fixed (n_fixed, 4, 2) and candidate (n_cand, 4, 2) BEV corners, the
+    candidates grouped by class at class_offsets (device int32, num_classes + 1) -> int32 accept flags (n_cand,), written to
+    `out` when given.  No host sync."""
+    fixed = _dev(fixed, "fixed", torch.float32)
+    cand = _dev(cand, "cand", torch.float32)
+    off = _dev(class_offsets, "class_offsets", torch.int32)
+    nc = cand.shape[0]
+    if out is None:
+        out = _empty((nc,), torch.int32, cand.device)
+    check(_lib.lib().srf_box_collision_accept(_ptr(fixed), fixed.shape[0], _ptr(cand), nc, _ptr(off), off.numel() - 1, _ptr(out),
+                                              _stream()), "box_collision_accept")
+    return out
+
+
+def object_sample_merge(points, point_box, sampled, obj_offsets, obj_centres, total):
+    """cat([sampled rows + the centre of their object, points with point_box < 0]) -> (total, nf).  `total` (= s + the count
+    of points in no box) is the caller's: it read it back together with the accept flags, so there is no sync here."""
+    points = _dev(points, "points", torch.float32)
+    point_box = _dev(point_box, "point_box", torch.int32)
+    sampled = _dev(sampled, "sampled", torch.float32)
+    off = _dev(obj_offsets, "obj_offsets", torch.int32)
+    ctr = _dev(obj_centres, "obj_centres", torch.float32)
+    n, nf = points.shape
+    s = sampled.shape[0]
+    if sampled.shape[1] != nf:
+        raise RuntimeError(f"srfdet3d_amd: sampled points have {sampled.shape[1]} features, the sweep {nf}")
+    L = _lib.lib()
+    dev = points.device
+    out = _empty((max(n + s, 1), nf), torch.float32, dev)
+    num = _empty((1,), torch.int32, dev)
+    ws = _empty((max(L.srf_object_sample_merge_workspace_bytes(n, s), 4),), torch.uint8, dev)
+    check(L.srf_object_sample_merge(_ptr(points), n, nf, _ptr(point_box), _ptr(sampled), s, _ptr(off), _ptr(ctr), ctr.shape[0],
+                                    _ptr(out), _ptr(num), _ptr(ws), _stream()), "object_sample_merge")
+    return out[:total]
+
+
+def object_noise(points, boxes, corners, planes, rot_sc, rot, loc):
+    """noise_per_box + points_transform_ + box3d_transform_ (srf_object_noise) -> (points (n, nf), boxes (m, box_dim),
+    chosen try per box int32 (m,), -1 where none fits).  Out of place, no host sync."""
+    points = _dev(points, "points", torch.float32)
+    boxes = _dev(boxes, "boxes", torch.float32)
+    corners = _dev(corners, "corners", torch.float32)
+    planes = _dev(planes, "planes", torch.float32)
+    rot_sc = _dev(rot_sc, "rot_sc", torch.float32)
+    rot = _dev(rot, "rot", torch.float64)
+    loc = _dev(loc, "loc", torch.float64)
+    n, nf = points.shape
+    m, box_dim = boxes.shape
+    num_try = rot.shape[1] if rot.dim() == 2 else 0
+    if corners.shape != (m, 4, 2) or planes.shape != (m, 6, 4) or rot.shape != (m, num_try) or \
+            rot_sc.shape != (m, num_try, 2) or loc.shape != (m, num_try, 3):
+        raise RuntimeError("srfdet3d_amd: object_noise: corners / planes / rot_sc / rot / loc do not match the boxes")
+    out_p = torch.empty_like(points)
+    out_b = torch.empty_like(boxes)
+    chosen = _empty((max(m, 1),), torch.int32, points.device)
+    check(_lib.lib().srf_object_noise(_ptr(points), n, nf, _ptr(boxes), m, box_dim, _ptr(corners), _ptr(planes), _ptr(rot_sc),
+                                      _ptr(rot), _ptr(loc), max(num_try, 1), _ptr(out_p), _ptr(out_b), _ptr(chosen), _stream()),
+          "object_noise")
+    return out_p, out_b, chosen[:m]
+
+
 def image_prepare(images_u8, mean, std, to_rgb=False, size_divisor=32, size=None):
     """(V, H, W, 3) uint8 decoded views -> (V, 3, Hp, Wp) float32: NormalizeMultiviewImage + PadMultiViewImage + the
     HWC -> CHW transpose of the format bundle in one pass.  Padding to `size` (Hp, Wp) or up to a multiple of
