@@ -35,9 +35,6 @@ typedef void *srf_stream_t;
 #define SRF_EHIP_BASE (-1000) /* -(1000 + hipError_t) */
 
 int srf_abi_version(void);
-/* 0 = the production library; 1 = the developer build (-DSRF_DEV: kernels for timing ablations whose outputs are wrong by
- * design).  A loader must refuse flavour 1 as the product library. */
-int srf_build_flavour(void);
 const char *srf_error_string(int code);
 /* Number of HIP devices visible, or a negative error.  Used by the Python loader to fail loudly. */
 int srf_device_count(void);
@@ -685,13 +682,6 @@ int srf_nhwc_affine_relu_bwd2(const float *gy, long long gy_ld, const float *gy2
 int srf_bn_eval_fold(const float *gamma, const float *beta, const float *mean, const float *var, float eps, int C, float *out /*3 C*/,
                      srf_stream_t stream);
 int srf_bn_eval_grads(const float *sums /*2 C*/, const float *fold /*3 C*/, const float *mean, int C, float *out /*2 C*/, srf_stream_t stream);
-/* srf_ese_apply: the end of VoVNet's eSEModule (vovnet.py:165-177) applied to an OSA block's concat output (:225-228) in one launch:
- * gate[n][c] = hsigmoid(fc(mean[n])) (the bits of srf_ese_gate) and y = x * gate (+ residual = the block's identity input), the bits of
- * srf_nhwc_affine with a per-sample scale.  x / residual / y: (N * HW) pixel rows of x_ld / r_ld / y_ld floats; W (C x C), bias (C) the
- * fc = 1x1 conv; gate_out (N x C) optional.  C % 64 == 0, C <= 1024. */
-int srf_ese_apply(const float *x, long long x_ld, int N, long long HW, int C, const float *mean, const float *W, const float *bias,
-                  const float *residual /*or NULL*/, long long r_ld, float *y, long long y_ld, float *gate_out /*or NULL*/,
-                  srf_stream_t stream);
 int srf_nhwc_pool_sum(const float *x, long long x_ld, int B, int n_cam, int H, int W, int C, int Ho, int Wo, float *out, int out_ld,
                       srf_stream_t stream);
 int srf_dpg_mix(const float *wl, const float *wi /*or NULL*/, int B, int E, int P, const float *boxes_w, int D, const float *feats_w,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/srfdet3d.h"
 
@@ -21,6 +22,20 @@
 
 static inline int srf_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t srf_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Developer A/B knobs.  Each one chooses between kernel forms that produce IDENTICAL bits; the launchers read them once per
+// process (into function-local statics), so the parity tests run each setting in its own interpreter (tests/forms.py).
+//   SRF_WINO_TWL     Winograd F(2x2) tile-block shape: 1 / 2 / 3 = 32 x 2 / 16 x 4 / 8 x 8 tiles (conv.hip)
+//   SRF_WINO_HALF    Winograd F(2x2): 0 = full blocks only; 1 = a last channel block of <= 32 channels as half blocks;
+//                    3 = the second half of the work items as two half blocks each (conv.hip)
+//   SRF_GEMM_TAIL    0 = no 64 x 64 tiles behind the last, partly filled round of 128 x 128 tiles of the 1x1 GEMM (conv.hip)
+//   SRF_W43_NB       Winograd F(4x4) multiply: 1 = 32-channel halves, 2 = 64-channel blocks (wino43.hip)
+//   SRF_W43_SLAB_TB  Winograd F(4x4): tile blocks per slab (wino43.hip)
+static inline long long srf_knob(const char *name, long long dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoll(e) : dflt;
+}
 
 // ---------------------------------------------------------------------------------------------
 // open-addressing coordinate table: keys[cap] (uint32 linearised coordinate, EMPTY = 0xFFFFFFFF)

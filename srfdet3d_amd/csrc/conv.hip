@@ -33,7 +33,6 @@
 // differs from a direct convolution by a few f32 roundings (tested against torch at 2e-4 of the map's max, the bar of the
 // SECOND / FPN tests).
 #include "common.hpp"
-#include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -52,7 +51,6 @@ struct WinoArgs {
     int cb0, ncb;       // channel blocks of this launch: cb0 .. cb0 + ncb - 1 (half-block form: in units of 32 channels)
     int nfull;          // srf_wino3x3_mixed_k: workgroups of the full form (the half-block ones follow)
     int ntail;          // srf_wino3x3_mixed_k: full work items nfull .. nfull + ntail - 1 run as two half-block workgroups each
-    long long *stamps;  // developer timing hook (srf_dev_set_stamp_buffer): 4 s_memtime values per workgroup, else NULL
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -143,7 +141,7 @@ __device__ __forceinline__ float4 wn_fma(float s, float4 a, float4 b)   // s a +
 // tiles and 32 MFMAs per chunk and wave instead of 64 (the all-zero channel half is not multiplied); the waves of the
 // upper frequency half hand their 8 accumulator tiles (the frequency rows 2 and 3 of M) to the lower half through LDS,
 // which then runs the SAME output transform in the same order of operations as the full kernel: identical bits.
-template <int DBG, int TWL, bool HALFB>
+template <int TWL, bool HALFB>
 __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cbi /* HALFB: index of a 32-channel half */, const int sp)
 {
     constexpr int TW = 1 << TWL, TH = 64 >> TWL;       // tiles per block row / column
@@ -160,8 +158,6 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
     const int per_img = a.rowBlocks * a.colBlocks;
     const int n = sp / per_img;
     const int rb = (sp - n * per_img) / a.colBlocks, cbk = sp - n * per_img - rb * a.colBlocks;
-    long long st0 = 0, st1 = 0, st2 = 0;
-    if (DBG & 8) st0 = __builtin_amdgcn_s_memtime();
 
     // ---- loader role: the (2 TH + 2) x (2 TW + 2) pixel patch of the block, 8 channels per chunk = NPIX float4, <= NL per
     // thread.  Buffer loads: the descriptor covers image n; a pixel outside the image gets an offset beyond the range and the
@@ -186,7 +182,7 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
     const float4 z4_ = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 gr_0 = z4_, gr_1 = z4_, gr_2 = z4_, gr_3 = z4_;
 #define WN_GL(J)                                                                                    \
-    if (!(DBG & 1) && (J) < NL) {                                                                   \
+    if ((J) < NL) {                                                                                 \
         auto v_ = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)goff[J], soff_, 0);             \
         gr_##J = *reinterpret_cast<float4 *>(&v_);                                                  \
     }
@@ -242,12 +238,12 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
 #define WN_LOAD_U_LO(CH)                                              \
     do {                                                              \
         const int u_soff_ = (CH) * u_chunk_bytes;                     \
-        if (!(DBG & 2)) { WN_UL(0, 0) WN_UL(1, 1) WN_UL(2, 2) WN_UL(3, 3) } \
+        WN_UL(0, 0) WN_UL(1, 1) WN_UL(2, 2) WN_UL(3, 3)               \
     } while (0)
 #define WN_LOAD_U_HI(CH)                                              \
     do {                                                              \
         const int u_soff_ = (CH) * u_chunk_bytes;                     \
-        if (!(DBG & 2)) { WN_UL(4, 4) WN_UL(5, 5) WN_UL(6, 6) WN_UL(7, 7) } \
+        WN_UL(4, 4) WN_UL(5, 5) WN_UL(6, 6) WN_UL(7, 7)               \
     } while (0)
 #define WN_STORE_U_LO(WB)                                             \
     do {                                                              \
@@ -303,10 +299,8 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
         f32x4 pa0_ = fa[SET][0], pa1_ = fa[SET][1], pb0_ = fb[SET][0], pb1_ = fb[SET][1];       \
         asm volatile("" : "+v"(pa0_), "+v"(pa1_), "+v"(pb0_), "+v"(pb1_));                      \
         f32x16 c0_ = (FIRST) ? wn_zero16() : acc[(G) * 2], c1_ = (FIRST) ? wn_zero16() : acc[(G) * 2 + 1]; \
-        if (!(DBG & 4)) {                                                                       \
-            WN_MFMA4(c0_, pa0_, pb0_);                                                          \
-            WN_MFMA4(c1_, pa1_, pb1_);                                                          \
-        }                                                                                       \
+        WN_MFMA4(c0_, pa0_, pb0_);                                                              \
+        WN_MFMA4(c1_, pa1_, pb1_);                                                              \
         asm volatile("" : "+a"(c0_), "+a"(c1_));                                                \
         acc[(G) * 2] = c0_;                                                                     \
         acc[(G) * 2 + 1] = c1_;                                                                 \
@@ -316,7 +310,7 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
         f32x4 pa_ = fa[SET][E], pb_ = fb[SET][E];                                               \
         asm volatile("" : "+v"(pa_), "+v"(pb_));                                                \
         f32x16 c_ = (FIRST) ? wn_zero16() : acc[(G) * 2 + (E)];                                 \
-        if (!(DBG & 4)) WN_MFMA4(c_, pa_, pb_);                                                 \
+        WN_MFMA4(c_, pa_, pb_);                                                                 \
         asm volatile("" : "+a"(c_));                                                            \
         acc[(G) * 2 + (E)] = c_;                                                                \
     } while (0)
@@ -350,7 +344,6 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
     WN_STAGE1();
     __syncthreads();
     WN_READ_GROUP(0, 0, 0);
-    if (DBG & 8) st1 = __builtin_amdgcn_s_memtime();
 
     // Iteration c: multiplies chunk c (8 groups of 2 frequencies = 8 MFMAs each; group g + 1 is read while group g
     // multiplies); writes the patch of chunk c + 2 (registers -> RAW) and loads the one of chunk c + 3; finishes the
@@ -454,7 +447,6 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
     }
 
     // ---- epilogue: A^T m A, affine, ReLU, store ----
-    if (DBG & 8) st2 = __builtin_amdgcn_s_memtime();
     // HALFB: frequency rows 2 and 3 of M (the accumulator tiles of the waves with fh = 1) change hands through LDS:
     // X[th][f 8][register 16][lane 64] floats = 64 KB over the V / U images, which nobody reads any more
     float *xch = reinterpret_cast<float *>(s_w) + th * (8 * 16 * 64) + lane;
@@ -516,14 +508,6 @@ __device__ __forceinline__ void srf_wino3x3_body(const WinoArgs &a, const int cb
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o11), yrsrc, (int)(row_ok && x1 && y1 ? o00_ + row_b + px_b : OOB), 0, 0);
         }
     }
-    if ((DBG & 8) && a.stamps && tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        long long *o = a.stamps + (size_t)blockIdx.x * 4;
-        o[0] = st0;
-        o[1] = st1;
-        o[2] = st2;
-        o[3] = __builtin_amdgcn_s_memtime();
-    }
 }
 
 // work item -> (channel block, spatial block): items b and b + 8 share an XCD (round-robin dispatch), so the channel blocks of
@@ -535,12 +519,12 @@ __device__ __forceinline__ void srf_wino_decode(unsigned item, int cb0, int ncb,
     sp = (jq / ncb) * 8 + xcd;
 }
 
-template <int DBG, int TWL, bool HALFB = false>
+template <int TWL, bool HALFB = false>
 __global__ __launch_bounds__(256, 1) void srf_wino3x3_k(WinoArgs a)
 {
     int cbi, sp;
     srf_wino_decode(blockIdx.x, a.cb0, a.ncb, cbi, sp);
-    srf_wino3x3_body<DBG, TWL, HALFB>(a, cbi, sp);
+    srf_wino3x3_body<TWL, HALFB>(a, cbi, sp);
 }
 
 // One launch, full and half-block workgroups: the first a.nfull workgroups are full ones (work items 0 .. nfull - 1 over the
@@ -554,7 +538,7 @@ __global__ __launch_bounds__(256, 1) void srf_wino3x3_mixed_k(WinoArgs a)
     int cbi, sp;
     if (blockIdx.x < (unsigned)a.nfull) {
         srf_wino_decode(blockIdx.x, 0, a.ncb, cbi, sp);
-        srf_wino3x3_body<0, TWL, false>(a, cbi, sp);
+        srf_wino3x3_body<TWL, false>(a, cbi, sp);
         return;
     }
     const unsigned h = blockIdx.x - (unsigned)a.nfull;
@@ -564,7 +548,7 @@ __global__ __launch_bounds__(256, 1) void srf_wino3x3_mixed_k(WinoArgs a)
     } else {
         srf_wino_decode(h - 2u * (unsigned)a.ntail, a.cb0, 1, cbi, sp);
     }
-    srf_wino3x3_body<0, TWL, true>(a, cbi, sp);
+    srf_wino3x3_body<TWL, true>(a, cbi, sp);
 }
 
 // =====================================================================================================================
@@ -635,7 +619,6 @@ __global__ __launch_bounds__(256) void srf_conv1x1_nhwc_pack_k(const float *__re
 //   <2, 2>: 128 x 128, 64 accumulator registers per wave, 32 KB of LDS (one stage + register prefetch) -> several
 //           workgroups per CU: the waves of different workgroups fill each other's barrier / staging gaps (an f32 MFMA
 //           overlaps with another wave's vector and LDS instructions, not with its own wave's);
-//   <4, 4>: 256 x 256, 16 accumulators per wave, one workgroup per CU (kept for A/B timing: SRF_GEMM_BIG=1).
 template <int RM, int RN, bool CONV>
 __device__ __forceinline__ void srf_gemm_body(const GemmArgs &a, const unsigned bid)
 {
@@ -884,21 +867,6 @@ __global__ __launch_bounds__(256, 3) void srf_conv1x1_nhwc_mixed_k(GemmArgs big,
     else srf_gemm_body<1, 1, false>(tail, blockIdx.x - nbig);
 }
 
-#ifdef SRF_DEV
-// developer build only (python -m srfdet3d_amd.build --dev): device buffer of 4 * gridDim.x int64 for SRF_WINO_DBG=8; the
-// production library has neither this symbol nor the ablation kernels
-static long long *g_wino_stamps = nullptr;
-extern "C" void srf_dev_set_stamp_buffer(long long *p) { g_wino_stamps = p; }
-#endif
-
-// Developer A/B knobs choose between forms that produce IDENTICAL bits (tile-block shape, half-block / tail mixes); they are
-// read once per process -- the parity tests run each setting in its own interpreter.
-static int srf_knob(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 static int srf_cu_count(int dev)
 {
     static int cus[64] = {0};
@@ -972,61 +940,35 @@ extern "C" int srf_wino3x3(const float *x, int N, int H, int W, int Cin, long lo
     if (srf_wino3x3_packed_weight_bytes(Cout, Cin) >= ((size_t)1 << 31)) return SRF_EUNSUPPORTED;  // buffer-descriptor range of U
     a.nspatial = (int)nspatial;
     a.relu = relu;
-#ifdef SRF_DEV
-    a.stamps = g_wino_stamps;
-#else
-    a.stamps = nullptr;
-#endif
     const long long blocks = ((nspatial + 7) / 8) * 8 * a.coutBlocks;
     int dev = 0;
     SRF_HIP_TRY(hipGetDevice(&dev));
     static bool attr_set[64] = {false};
     if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-#ifdef SRF_DEV
-    static const int dbg = srf_knob("SRF_WINO_DBG", 0);  // timing ablations: skip loads / MFMAs, stamps (WRONG outputs by design)
-#endif
     if (!attr_set[dev]) {
-#define WN_ATTR(D, L, HB) SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_k<D, L, HB>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES))
-        WN_ATTR(0, 1, false);
-        WN_ATTR(0, 2, false);
-        WN_ATTR(0, 3, false);
-        WN_ATTR(0, 1, true);
-        WN_ATTR(0, 2, true);
-        WN_ATTR(0, 3, true);
+#define WN_ATTR(L, HB) SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_k<L, HB>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES))
+        WN_ATTR(1, false);
+        WN_ATTR(2, false);
+        WN_ATTR(3, false);
+        WN_ATTR(1, true);
+        WN_ATTR(2, true);
+        WN_ATTR(3, true);
         SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_mixed_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES));
         SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_mixed_k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES));
         SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_mixed_k<3>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES));
-#ifdef SRF_DEV
-        WN_ATTR(1, 3, false);
-        WN_ATTR(4, 3, false);
-        WN_ATTR(8, 3, false);
-#endif
 #undef WN_ATTR
         attr_set[dev] = true;
     }
     const dim3 blk(256);
     a.cb0 = 0;
     a.ncb = a.coutBlocks;
-#ifdef SRF_DEV
-    if (dbg == 1 || dbg == 4 || dbg == 8) {   // ablation builds exist for the 8 x 8 shape only
-        a.rowBlocks = srf_ceil_div(tilesY, 8);
-        a.colBlocks = srf_ceil_div(tilesX, 8);
-        a.nspatial = N * a.rowBlocks * a.colBlocks;
-        const dim3 gd((unsigned)(((a.nspatial + 7) / 8) * 8 * a.coutBlocks));
-        if (dbg == 1) hipLaunchKernelGGL((srf_wino3x3_k<1, 3>), gd, blk, WN_LDS_BYTES, (hipStream_t)stream, a);
-        else if (dbg == 4) hipLaunchKernelGGL((srf_wino3x3_k<4, 3>), gd, blk, WN_LDS_BYTES, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((srf_wino3x3_k<8, 3>), gd, blk, WN_LDS_BYTES, (hipStream_t)stream, a);
-        SRF_LAUNCH_CHECK();
-        return SRF_OK;
-    }
-#endif
     // A last channel block with at most 32 real channels (Cout = 160, 224, ...) can run on the half-block kernel, whose
     // workgroups take ~0.62 of a full one, as a launch of its own.  Worth it when it saves rounds of 256 workgroups
     // (SRF_WINO_HALF=0 / 1 forces the choice: developer A/B knob).
     const long long sp8 = ((nspatial + 7) / 8) * 8;
     const int rem = Cout - (a.coutBlocks - 1) * 64;
     static const int force_half = srf_knob("SRF_WINO_HALF", -1);
-    bool split = false, all_half = false;
+    bool split = false;
     const int cus = srf_cu_count(dev);
     double rounds_best = (double)srf_ceil_div(sp8 * a.coutBlocks, cus);   // rounds of full workgroups
     if (rem <= 32) {
@@ -1037,18 +979,11 @@ extern "C" int srf_wino3x3(const float *x, int N, int H, int W, int Cin, long lo
         split = force_half < 0 ? then < rounds_best : force_half == 1;
         if (split) rounds_best = then;
     }
-    // Every block as two half-block workgroups (32 channels each, the waves split the frequencies): measured, not faster
-    // anywhere -- a launch of half blocks only runs at ~0.7 of the full form's rate (the input transform is done twice), so a
-    // shorter last round does not pay it back (SECOND 128 -> 128 @ 184 x 184: 96 -> 104 us).  Kept behind SRF_WINO_HALF=2: the
-    // parity test runs it against the full form.
-    const int nhb = srf_ceil_div(Cout, 32);
-    all_half = force_half == 2;
-    if (all_half) split = false;
 #define WN_LAUNCH(HB, GRID)                                                                                                    \
     do {                                                                                                                       \
-        if (twl == 3) hipLaunchKernelGGL((srf_wino3x3_k<0, 3, HB>), dim3((unsigned)(GRID)), blk, WN_LDS_BYTES, (hipStream_t)stream, a);      \
-        else if (twl == 2) hipLaunchKernelGGL((srf_wino3x3_k<0, 2, HB>), dim3((unsigned)(GRID)), blk, WN_LDS_BYTES, (hipStream_t)stream, a); \
-        else hipLaunchKernelGGL((srf_wino3x3_k<0, 1, HB>), dim3((unsigned)(GRID)), blk, WN_LDS_BYTES, (hipStream_t)stream, a);               \
+        if (twl == 3) hipLaunchKernelGGL((srf_wino3x3_k<3, HB>), dim3((unsigned)(GRID)), blk, WN_LDS_BYTES, (hipStream_t)stream, a);         \
+        else if (twl == 2) hipLaunchKernelGGL((srf_wino3x3_k<2, HB>), dim3((unsigned)(GRID)), blk, WN_LDS_BYTES, (hipStream_t)stream, a);    \
+        else hipLaunchKernelGGL((srf_wino3x3_k<1, HB>), dim3((unsigned)(GRID)), blk, WN_LDS_BYTES, (hipStream_t)stream, a);                  \
     } while (0)
     a.nfull = 0;
     a.ntail = 0;
@@ -1062,8 +997,8 @@ extern "C" int srf_wino3x3(const float *x, int N, int H, int W, int Cin, long lo
     // a partly filled last round of full workgroups (SECOND 128 -> 128 @ 184 x 184: 288 work items on 256 CUs) as half-block
     // workgroups in the same launch, when they all fit beside each other (SRF_WINO_HALF=3 forces it on half of the items)
     const long long items = sp8 * a.coutBlocks, tail_items = items % cus;
-    const bool tail = !split && !all_half && (force_half < 0 ? (items > cus && tail_items > 0 && 2 * tail_items <= cus) : force_half == 3);
-    if (split && !all_half && a.coutBlocks > 1) {
+    const bool tail = !split && (force_half < 0 ? (items > cus && tail_items > 0 && 2 * tail_items <= cus) : force_half == 3);
+    if (split && a.coutBlocks > 1) {
         a.cb0 = 2 * (a.coutBlocks - 1);
         a.ncb = a.coutBlocks - 1;
         a.nfull = (int)(sp8 * a.ncb);
@@ -1072,10 +1007,6 @@ extern "C" int srf_wino3x3(const float *x, int N, int H, int W, int Cin, long lo
         a.cb0 = 2 * (a.coutBlocks - 1);
         a.ncb = 1;
         WN_LAUNCH(true, sp8);
-    } else if (all_half) {
-        a.cb0 = 0;
-        a.ncb = nhb;
-        WN_LAUNCH(true, sp8 * nhb);
     } else if (tail) {
         a.cb0 = -1;
         a.ncb = a.coutBlocks;
@@ -1149,18 +1080,10 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
     int dev = 0;
     SRF_HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-    static bool attr_set[64] = {false};
-    constexpr int LDS_BIG = (8 * 256 + 8 * 256) * 16, LDS_STD = (8 * 128 + 8 * 128) * 16;
-    if (!attr_set[dev]) {
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_conv1x1_nhwc_k<4, 4, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BIG));
-        attr_set[dev] = true;
-    }
-    static const int big = srf_knob("SRF_GEMM_BIG", 0);
-    int TM = (big && !colsum) ? 256 : 128, ncs = (big && !colsum) ? 1 : 2;
-    // below ~0.8 rounds of 128 x 128 tiles at three per CU the 64 x 64 tiles win (stage 5 of VoVNet: 544 tiles, 417 -> 386 us);
-    // SRF_GEMM_SMALL overrides the threshold (developer A/B knob)
-    static const int small_thr = srf_knob("SRF_GEMM_SMALL", 640);
-    if (srf_ceil_div(M, 128) * srf_ceil_div(Cout, 128) < small_thr) TM = 64, ncs = 4;  // small problem: 64 x 64 tiles
+    constexpr int LDS_STD = (8 * 128 + 8 * 128) * 16;
+    int TM = 128, ncs = 2;
+    // below ~0.8 rounds of 128 x 128 tiles at three per CU the 64 x 64 tiles win (stage 5 of VoVNet: 544 tiles, 417 -> 386 us)
+    if (srf_ceil_div(M, 128) * srf_ceil_div(Cout, 128) < 640) TM = 64, ncs = 4;  // small problem: 64 x 64 tiles
     a.row0 = 0;
     a.slot0 = 0;
     const long long nimg = colsum ? M / HW : 1;
@@ -1176,16 +1099,12 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
     }
     // tail of the last, partly filled round of 128 x 128 tiles as 64 x 64 tiles (SRF_GEMM_TAIL=0 turns it off; developer A/B knob)
     static const int tail_on = srf_knob("SRF_GEMM_TAIL", 1);
-    static const double tail_frac = getenv("SRF_GEMM_TAIL_FRAC") ? atof(getenv("SRF_GEMM_TAIL_FRAC")) : 1.0;
-    static const int tail_extra = srf_knob("SRF_GEMM_TAIL_EXTRA", 0);
     if (TM == 128 && tail_on) {
         const int cus = srf_cu_count(dev);
         const long long slots_cu = 3ll * cus, nct = srf_ceil_div(Cout, 128);
         const long long tiles = a.mblocks * nct;
-        long long full = tiles / slots_cu;
-        const double frac = (double)(tiles - full * slots_cu) / (double)slots_cu;
-        if (full > tail_extra) full -= tail_extra;
-        if (full >= 1 && frac > 0.0 && frac <= tail_frac) {
+        const long long full = tiles / slots_cu;
+        if (full >= 1 && tiles % slots_cu != 0) {
             // row blocks (per image) the big tiles keep: whole rounds, a multiple of 8 blocks in total where that is possible
             const long long keep = (full * slots_cu) / (nct * nimg);   // per image
             GemmArgs t = a;
@@ -1214,9 +1133,7 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
     }
     const long long blocks = ((a.mblocks + 7) / 8) * 8 * srf_ceil_div(Cout, 256 / ncs);
     if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    if (TM == 256)
-        hipLaunchKernelGGL((srf_conv1x1_nhwc_k<4, 4, 1, false>), dim3((unsigned)blocks), dim3(256), LDS_BIG, stream, a);
-    else if (TM == 64)
+    if (TM == 64)
         hipLaunchKernelGGL((srf_conv1x1_nhwc_k<1, 1, 4, false>), dim3((unsigned)blocks), dim3(256), (8 * 64 + 8 * 64) * 16, stream, a);
     else
         hipLaunchKernelGGL((srf_conv1x1_nhwc_k<2, 2, 3, false>), dim3((unsigned)blocks), dim3(256), LDS_STD, stream, a);

@@ -15,7 +15,6 @@
 // LDS per workgroup (COUT = 128): nbr tile 27*64*4 = 6.9 KB, A chunk 64*33*4 = 8.4 KB, W chunk 32*128*4 = 16 KB
 // -> 5 workgroups per CU; latency is hidden by occupancy rather than by an explicit pipeline.
 #include "common.hpp"
-#include <cstdlib>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -368,7 +367,7 @@ __global__ __launch_bounds__(256) void srf_pack_weights_gs_k(const float *__rest
 // [t*P/T, (t+1)*P/T) -- once per rulebook (the four SubM layers of a level share it).  A workgroup walks its range in
 // sub-tiles of at most SRF_GS_TMAX rows.
 #define SRF_TB_ROWS 256
-#define SRF_GS_ROW_COST 8 /* cost of a row = its pairs + 8: the constant carries the row's share of the per-sub-tile work (list
+#define SRF_GS_ROW_BASE 8 /* cost of a row = its pairs + 8: the constant carries the row's share of the per-sub-tile work (list
                              build, epilogue: ~20 k cycles per sub-tile against ~270 cycles per pair in the step loop of
                              srf_spconv_gsp_k) and keeps sparse ranges from growing taller than a tile, which costs a second
                              sub-tile (+35 k cycles).  Round 1's kernel, whose steps were twice as long, was fitted with 12.
@@ -492,16 +491,7 @@ __global__ __launch_bounds__(256) void srf_gs_cut_k(const int *__restrict__ loca
 
 extern "C" int srf_spconv_tiles_count(int A_out) { return A_out <= 0 ? 1 : srf_gs_ranges(A_out); }
 
-static int srf_gs_row_cost_value()
-{
-    static const int row_cost = [] {
-        const char *e = getenv("SRF_GS_ROW_COST");   // developer switch (A/B timing of the cost model)
-        return e ? atoi(e) : SRF_GS_ROW_COST;
-    }();
-    return row_cost;
-}
-
-extern "C" int srf_spconv_tiles_row_cost(void) { return srf_gs_row_cost_value(); }
+extern "C" int srf_spconv_tiles_row_cost(void) { return SRF_GS_ROW_BASE; }
 
 extern "C" size_t srf_spconv_tiles_workspace_bytes(int A_out)
 {
@@ -520,8 +510,7 @@ extern "C" int srf_spconv_tiles_build(const int *nbr, int nbr_stride, int K, int
     const int nb = (A_out + SRF_TB_ROWS - 1) / SRF_TB_ROWS;
     int *local = (int *)workspace, *blocksum = local + A_out, *blockoff = blocksum + nb + 1;
     if (nb > 0) {
-        const int row_cost = srf_gs_row_cost_value();
-        hipLaunchKernelGGL(srf_gs_rowpairs_k, dim3(nb), dim3(256), 0, st, nbr, nbr_stride, K, A_out, rows_dev, local, blocksum, row_cost);
+        hipLaunchKernelGGL(srf_gs_rowpairs_k, dim3(nb), dim3(256), 0, st, nbr, nbr_stride, K, A_out, rows_dev, local, blocksum, SRF_GS_ROW_BASE);
         hipLaunchKernelGGL(srf_gs_blockscan_k, dim3(1), dim3(256), 0, st, blocksum, nb, blockoff);
     }
     hipLaunchKernelGGL(srf_gs_cut_k, dim3(srf_ceil_div(T + 1, 256)), dim3(256), 0, st, local, blockoff, nb, A_out, rows_dev, T, tiles);
@@ -583,79 +572,53 @@ struct SrfGspLane {
     unsigned boff;         // byte offset of the lane's B fragment inside a (offset, chunk) image
 };
 
-// ABL: timing ablations of the developer build (-DSRF_DEV; wrong outputs by design): 1 = no MFMAs, 2 = no gathers / A stores,
-// 3 = no accumulator round trip through the tile, 4 = no barrier
-#ifdef SRF_DEV
-__device__ long long srf_gsp_stamps[512 * 16];   // developer build: per workgroup the cycles of a step spent before / in / behind the MFMA block and at the barrier, the step count, prologue / loop / epilogue
-extern "C" int srf_dev_gsp_stamps(long long *host, int n)
-{
-    SRF_HIP_TRY(hipDeviceSynchronize());
-    SRF_HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(srf_gsp_stamps), sizeof(long long) * (n < 512 * 16 ? n : 512 * 16)));
-    return SRF_OK;
-}
-#endif
 // what a wave carries from step to step: every address the LDS-only parts of a step use is prepared INSIDE the MFMA block before
-template <int GP>
 struct SrfGspRegs {
     unsigned f0, f1;          // fragment quads of the A image the step reads
     unsigned st[4];           // where it stores the rows of the step after it
-    unsigned gaddr[GP];       // buffer offsets of the rows it requests (step + 2)
-    unsigned oaddr[GP][4];    // tile addresses of its accumulators
+    unsigned gaddr;           // buffer offset of the row it requests (step + 2)
+    unsigned oaddr[4];        // tile addresses of its accumulators
     unsigned pin_addr;        // LDS address of the row-list entries it reads (step + 3: the request after next)
     unsigned slot_addr;       // LDS address of the slots it reads (step + 1)
     unsigned info_addr;       // LDS address of the offset flag it reads (step + 1)
 };
 
-// GP = groups of 16 rows per step.  COUT = 64 runs GP = 2: a wave owns ONE 16-column MFMA tile there, i.e. one dependent chain of 16
-// MFMAs per group (40 cycles each instead of 32) behind a fixed chain of LDS latencies (fragments -> MFMAs -> accumulators back and
-// out -> barrier); two groups per step are two independent chains and half the barriers per pair.  (The rows of an offset are padded
-// to whole steps: 27 x 16 instead of 27 x 8 padding rows per sub-tile on average.)
-template <int NCH, int COUT, int GP, bool LAST, int ABL = 0>
+// A step multiplies one group of 16 rows.  Steps of two groups (for COUT = 64, where a wave owns ONE 16-column MFMA tile: two
+// independent MFMA chains per step and half the barriers) measured slower: the rows of an offset are padded to whole steps, and
+// the padding grew by 27 %.
+template <int NCH, int COUT, bool LAST>
 __device__ __forceinline__ void srf_gsp_step(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t wrs, int kn, int &buf, const SrfGspLane &L,
-                                             SrfGspRegs<GP> &G, f32x4 (&bc)[NCH][COUT / 32], f32x4 (&bn)[NCH][COUT / 32],
-                                             f32x4 (&ra)[GP][NCH >= 2 ? NCH / 2 : 1], f32x4 (&acc)[GP][COUT / 64], long long (&stamp)[8], int &info_next)
+                                             SrfGspRegs &G, f32x4 (&bc)[NCH][COUT / 32], f32x4 (&bn)[NCH][COUT / 32],
+                                             f32x4 (&ra)[NCH >= 2 ? NCH / 2 : 1], f32x4 (&acc)[COUT / 64], int &info_next)
 {
-    constexpr int NT = COUT / 64, NB = COUT / 32, NA = NCH >= 2 ? NCH / 2 : 1, RS = 16 * GP, CHS = RS * 32 + 8, OS = COUT + 4;
+    constexpr int NT = COUT / 64, NB = COUT / 32, NA = NCH >= 2 ? NCH / 2 : 1, RS = 16, CHS = RS * 32 + 8, OS = COUT + 4;
     constexpr int TPR = NCH >= 2 ? 16 : 8;     // threads per gathered row (a quad each; rows of 128 channels: two quads each)
     constexpr unsigned ABUF = NCH * CHS * 4;   // bytes of one A buffer
     typedef const __attribute__((address_space(3))) unsigned srf_lds_u32;
     const bool gathers = TPR == 16 || threadIdx.x < 16 * TPR;   // 32-channel rows: 128 threads (two waves) carry a group of 16 rows
-    long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    if (ABL == 5) t0 = __builtin_amdgcn_s_memtime();
     // ---- LDS / memory instructions only.  In-kernel stamps (the ping-pong experiment, tools/micro/spconv_gsq_experiment.patch): a wave
     // issues NO vector instruction while the partner wave of its SIMD -- here: the CU's other workgroup -- streams f32 MFMAs, at any
     // s_setprio; a step whose first instruction is an address add therefore stands still until the partner's MFMA block is over, and
     // the two workgroups take turns instead of overlapping.  Every address below comes out of registers prepared inside this
     // wave's own previous MFMA block ----
-    f32x4 af[2][GP][2];
-#pragma unroll
-    for (int gp = 0; gp < GP; ++gp) {
-        af[0][gp][0] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f0 + gp * 2048);
-        af[0][gp][1] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f1 + gp * 2048);
-    }
-    unsigned ro[GP], sl4[GP];
-#pragma unroll
-    for (int gp = 0; gp < GP; ++gp) {
-        ro[gp] = *reinterpret_cast<srf_lds_u32 *>(G.pin_addr + gp * 64);     // list entries of step i + 3
-        sl4[gp] = *reinterpret_cast<srf_lds_u32 *>(G.slot_addr + gp * 16);   // slots of step i + 1
-    }
+    f32x4 af[2][2];
+    af[0][0] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f0);
+    af[0][1] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f1);
+    const unsigned ro = *reinterpret_cast<srf_lds_u32 *>(G.pin_addr);     // list entries of step i + 3
+    const unsigned sl4 = *reinterpret_cast<srf_lds_u32 *>(G.slot_addr);   // slots of step i + 1
     const unsigned inf = *reinterpret_cast<const __attribute__((address_space(3))) unsigned char *>(G.info_addr);  // ... and its offset flag
-    if (ABL != 2 && gathers) {
+    if (gathers) {
         // A[i + 1]: rows gathered during step i - 1, into the buffer the previous step read
 #pragma unroll
-        for (int gp = 0; gp < GP; ++gp)
+        for (int j = 0; j < NA; ++j)
 #pragma unroll
-            for (int j = 0; j < NA; ++j)
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<srf_lds_float *>(G.st[jj] + gp * 2048 + j * (2 * CHS * 4)) = ra[gp][j][jj];
+            for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<srf_lds_float *>(G.st[jj] + j * (2 * CHS * 4)) = ra[j][jj];
         // rows of step i + 2 (dummy steps behind the last one: out-of-range offsets, zeros)
 #pragma unroll
-        for (int gp = 0; gp < GP; ++gp)
-#pragma unroll
-            for (int j = 0; j < NA; ++j) {
-                auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)G.gaddr[gp] + j * 256, 0, 0);
-                ra[gp][j] = *reinterpret_cast<f32x4 *>(&v);
-            }
+        for (int j = 0; j < NA; ++j) {
+            auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)G.gaddr + j * 256, 0, 0);
+            ra[j] = *reinterpret_cast<f32x4 *>(&v);
+        }
     }
     if (LAST) {   // B of the next offset into the other register set, a whole step ahead (through a descriptor: not an invariant
                   // load the compiler may sink to its first use behind the barrier)
@@ -668,32 +631,21 @@ __device__ __forceinline__ void srf_gsp_step(__amdgpu_buffer_rsrc_t rs, __amdgpu
                 bn[c][g] = *reinterpret_cast<f32x4 *>(&v);
             }
     }
-    unsigned oaddr_n[GP][4];
-    if (ABL == 5) t1 = __builtin_amdgcn_s_memtime();
+    unsigned oaddr_n[4];
     __builtin_amdgcn_sched_barrier(0);
     // ---- the MFMA block: fragments of the next chunk requested a chunk ahead; the vector instructions of the step in its last chunk ----
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         if (c + 1 < NCH) {
-#pragma unroll
-            for (int gp = 0; gp < GP; ++gp) {
-                af[(c + 1) & 1][gp][0] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f0 + gp * 2048 + (c + 1) * (CHS * 4));
-                af[(c + 1) & 1][gp][1] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f1 + gp * 2048 + (c + 1) * (CHS * 4));
-            }
+            af[(c + 1) & 1][0] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f0 + (c + 1) * (CHS * 4));
+            af[(c + 1) & 1][1] = *reinterpret_cast<const srf_lds_f32x4 *>(G.f1 + (c + 1) * (CHS * 4));
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-#pragma unroll
-            for (int gp = 0; gp < GP; ++gp) {
-                const float a = af[c & 1][gp][s >> 2][s & 3];
-                if (ABL == 1) {   // keep the operands alive, issue nothing
-                    asm volatile("" ::"v"(a), "v"(bc[c][s >> 2][s & 3]), "v"(bc[c][NB - 2 + (s >> 2)][s & 3]));
-                    continue;
-                }
-                acc[gp][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bc[c][s >> 2][s & 3], acc[gp][0], 0, 0, 0);
-                if (NT == 2) acc[gp][NT - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bc[c][NB - 2 + (s >> 2)][s & 3], acc[gp][NT - 1], 0, 0, 0);
-            }
+            const float a = af[c & 1][s >> 2][s & 3];
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bc[c][s >> 2][s & 3], acc[0], 0, 0, 0);
+            if (NT == 2) acc[NT - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bc[c][NB - 2 + (s >> 2)][s & 3], acc[NT - 1], 0, 0, 0);
             if (c == NCH - 1 && s == 3) {
                 // (all fragment reads of the step are issued: the address registers are free to move on)
                 __builtin_amdgcn_sched_barrier(0);
@@ -706,15 +658,12 @@ __device__ __forceinline__ void srf_gsp_step(__amdgpu_buffer_rsrc_t rs, __amdgpu
                 G.f1 += d;
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) G.st[jj] -= d;
+                unsigned ro_here = ro, sl_here = sl4;
+                asm volatile("" : "+v"(ro_here), "+v"(sl_here));
 #pragma unroll
-                for (int gp = 0; gp < GP; ++gp) {
-                    unsigned ro_here = ro[gp], sl_here = sl4[gp];
-                    asm volatile("" : "+v"(ro_here), "+v"(sl_here));
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) oaddr_n[gp][jj] = ((sl_here >> (8 * jj)) & 255u) * (unsigned)(OS * 4) + L.colbase;
-                    G.gaddr[gp] = ro_here + L.goff;
-                    asm volatile("" : "+v"(G.gaddr[gp]), "+v"(oaddr_n[gp][0]), "+v"(oaddr_n[gp][1]), "+v"(oaddr_n[gp][2]), "+v"(oaddr_n[gp][3]));
-                }
+                for (int jj = 0; jj < 4; ++jj) oaddr_n[jj] = ((sl_here >> (8 * jj)) & 255u) * (unsigned)(OS * 4) + L.colbase;
+                G.gaddr = ro_here + L.goff;
+                asm volatile("" : "+v"(G.gaddr), "+v"(oaddr_n[0]), "+v"(oaddr_n[1]), "+v"(oaddr_n[2]), "+v"(oaddr_n[3]));
                 G.pin_addr += RS * 4;
                 G.slot_addr += RS;
                 G.info_addr += 1;
@@ -725,56 +674,30 @@ __device__ __forceinline__ void srf_gsp_step(__amdgpu_buffer_rsrc_t rs, __amdgpu
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (ABL == 5) t2 = __builtin_amdgcn_s_memtime();
-    if (ABL == 3) {
-#pragma unroll
-        for (int gp = 0; gp < GP; ++gp)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) G.oaddr[gp][jj] = oaddr_n[gp][jj];
-        __syncthreads();
-        return;
-    }
     // ---- LDS only again: accumulators of step i back into the tile, those of step i + 1 out of it (in-order LDS: shared rows are
     // read after they were written); plain ds_read_b32 into the accumulator registers themselves (the compiler pairs them as
     // ds_read2 and then shuffles registers behind a wait), awaited before the barrier together with the stores ----
 #pragma unroll
-    for (int gp = 0; gp < GP; ++gp)
+    for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-            for (int cb = 0; cb < NT; ++cb) *reinterpret_cast<srf_lds_float *>(G.oaddr[gp][jj] + cb * 64) = acc[gp][cb][jj];
+        for (int cb = 0; cb < NT; ++cb) *reinterpret_cast<srf_lds_float *>(G.oaddr[jj] + cb * 64) = acc[cb][jj];
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int gp = 0; gp < GP; ++gp)
+    for (int cb = 0; cb < NT; ++cb)
 #pragma unroll
-        for (int cb = 0; cb < NT; ++cb)
+        for (int jj = 0; jj < 4; ++jj) {
+            float t;
+            if (cb == 0) asm volatile("ds_read_b32 %0, %1" : "=v"(t) : "v"(oaddr_n[jj]) : "memory");
+            else asm volatile("ds_read_b32 %0, %1 offset:64" : "=v"(t) : "v"(oaddr_n[jj]) : "memory");
+            acc[cb][jj] = t;
+        }
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                float t;
-                if (cb == 0) asm volatile("ds_read_b32 %0, %1" : "=v"(t) : "v"(oaddr_n[gp][jj]) : "memory");
-                else asm volatile("ds_read_b32 %0, %1 offset:64" : "=v"(t) : "v"(oaddr_n[gp][jj]) : "memory");
-                acc[gp][cb][jj] = t;
-            }
-#pragma unroll
-    for (int gp = 0; gp < GP; ++gp)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) G.oaddr[gp][jj] = oaddr_n[gp][jj];   // (a renaming: the copies, if any, land in the next MFMA block)
+    for (int jj = 0; jj < 4; ++jj) G.oaddr[jj] = oaddr_n[jj];   // (a renaming: the copies, if any, land in the next MFMA block)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (ABL == 5) t3 = __builtin_amdgcn_s_memtime();
-    if (ABL != 4) __syncthreads();
-#ifdef SRF_DEV
-    if (ABL == 5) {
-        const long long t4 = __builtin_amdgcn_s_memtime();
-        stamp[0] += t1 - t0;
-        stamp[1] += t2 - t1;
-        stamp[2] += t3 - t2;
-        stamp[3] += t4 - t3;
-        stamp[4] += 1;
-    }
-#endif
+    __syncthreads();
 }
 
-template <int NCH, int COUT, int ABL = 0, int GP = 1>
+template <int NCH, int COUT>
 __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restrict__ in, int A_in, const float *__restrict__ Wg, int K,
                                                          const int *__restrict__ nbr, int nbr_stride, int A_out,
                                                          const float *__restrict__ alpha, const float *__restrict__ beta,
@@ -783,7 +706,7 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
                                                          const int *__restrict__ tiles)
 {
     constexpr int NT = COUT / 64, NB = COUT / 32;
-    constexpr int RS = 16 * GP;   // rows per step (srf_gsp_step)
+    constexpr int RS = 16;   // rows per step (srf_gsp_step)
     constexpr int NA = NCH >= 2 ? NCH / 2 : 1, TPR = NCH >= 2 ? 16 : 8, NKW = (SRF_KMAX + 3) / 4, CHS = RS * 32 + 8;
     constexpr int TMAX = COUT == 128 ? SRF_GS_TMAX : 128, OS = COUT + 4;   // (64 channels: 128 rows = the two ballot segments; 63 KB of LDS)
     constexpr int FL = ((TMAX * SRF_KMAX + SRF_KMAX * (RS - 1) + RS - 1) / RS) * RS + 2 * RS;   // every offset padded to whole steps, two dummy steps
@@ -822,9 +745,6 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
     }
     if (range1 <= range0) return;
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)((long long)A_in * (32 * NCH) * 4), 0x00020000);
-    long long stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tk0 = 0;
-    if (ABL == 5) tk0 = __builtin_amdgcn_s_memtime();
     const int nsub = (range1 - range0 + TMAX - 1) / TMAX;
     const int TM = (((range1 - range0 + nsub - 1) / nsub) + 7) & ~7;
     for (int row0 = range0; row0 < range1; row0 += TM) {
@@ -834,8 +754,6 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
     // per sub-tile instead.
     int zero = 0;
     asm volatile("" : "+s"(zero));
-    long long tp0 = 0, tl0 = 0, te0 = 0;
-    if (ABL == 5) tp0 = __builtin_amdgcn_s_memtime();
     for (int e = tid; e < TM * OS / 4; e += 256) reinterpret_cast<f32x4 *>(s_out)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
     int nv[NKW][2];
 #pragma unroll
@@ -929,8 +847,8 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
         L.boff = (unsigned)(lane * 16 + wc * 4096 + g0 * 1024 + zero);
     }
     __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Wg), 0, K * NCH * NB * 4096, 0x00020000);
-    f32x4 b0[NCH][NB], b1[NCH][NB], ra[GP][NA], acc[GP][NT];
-    SrfGspRegs<GP> G;
+    f32x4 b0[NCH][NB], b1[NCH][NB], ra[NA], acc[NT];
+    SrfGspRegs G;
     int buf = 0;
     {
         constexpr unsigned ABUF = NCH * CHS * 4;
@@ -939,16 +857,13 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
         G.f1 = L.fo1;
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) G.st[jj] = L.sto[jj] + ABUF;
+        const unsigned sl0 = *reinterpret_cast<const unsigned *>(s_pslot + aj * 4);   // slots of step 0
+        G.gaddr = s_pin[2 * RS + ((tid / TPR) & 15)] + L.goff;                        // step 0 requests the rows of step 2
 #pragma unroll
-        for (int gp = 0; gp < GP; ++gp) {
-            const unsigned sl0 = *reinterpret_cast<const unsigned *>(s_pslot + gp * 16 + aj * 4);   // slots of step 0
+        for (int jj = 0; jj < 4; ++jj) {
+            G.oaddr[jj] = ((sl0 >> (8 * jj)) & 255u) * (unsigned)(OS * 4) + L.colbase;
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                G.oaddr[gp][jj] = ((sl0 >> (8 * jj)) & 255u) * (unsigned)(OS * 4) + L.colbase;
-#pragma unroll
-                for (int cb = 0; cb < NT; ++cb) acc[gp][cb][jj] = 0.0f;   // the tile was just zeroed
-            }
-            G.gaddr[gp] = s_pin[2 * RS + gp * 16 + ((tid / TPR) & 15)] + L.goff;        // step 0 requests the rows of step 2
+            for (int cb = 0; cb < NT; ++cb) acc[cb][jj] = 0.0f;   // the tile was just zeroed
         }
         G.pin_addr = srf_lds_addr(s_pin) + (unsigned)(3 * RS + ((tid / TPR) & 15)) * 4u;   // ... and reads the list entries of step 3
         G.slot_addr = srf_lds_addr(s_pslot) + (unsigned)(RS + aj * 4);                  // ... and the slots of step 1
@@ -963,38 +878,26 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
                 auto v = __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)(L.boff + g * 1024), (k0 * NCH + c) * (NB * 4096), 0);
                 b0[c][g] = *reinterpret_cast<f32x4 *>(&v);
             }
+        const unsigned ro0 = s_pin[(tid / TPR) & 15];
 #pragma unroll
-        for (int gp = 0; gp < GP; ++gp) {
-            const unsigned ro = s_pin[gp * 16 + ((tid / TPR) & 15)];
-#pragma unroll
-            for (int j = 0; j < NA; ++j) {
-                auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(ro + L.goff + j * 256), 0, 0);
-                ra[gp][j] = *reinterpret_cast<f32x4 *>(&v);
-            }
+        for (int j = 0; j < NA; ++j) {
+            auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(ro0 + L.goff + j * 256), 0, 0);
+            ra[j] = *reinterpret_cast<f32x4 *>(&v);
         }
         if (TPR == 16 || tid < 16 * TPR) {
 #pragma unroll
-            for (int gp = 0; gp < GP; ++gp)
+            for (int j = 0; j < NA; ++j)
 #pragma unroll
-                for (int j = 0; j < NA; ++j)
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<srf_lds_float *>(L.sto[jj] + gp * 2048 + j * (2 * CHS * 4)) = ra[gp][j][jj];
+                for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<srf_lds_float *>(L.sto[jj] + j * (2 * CHS * 4)) = ra[j][jj];
         }
+        const unsigned ro1 = s_pin[RS + ((tid / TPR) & 15)];
 #pragma unroll
-        for (int gp = 0; gp < GP; ++gp) {
-            const unsigned ro = s_pin[RS + gp * 16 + ((tid / TPR) & 15)];
-#pragma unroll
-            for (int j = 0; j < NA; ++j) {
-                auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(ro + L.goff + j * 256), 0, 0);
-                ra[gp][j] = *reinterpret_cast<f32x4 *>(&v);
-            }
+        for (int j = 0; j < NA; ++j) {
+            auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(ro1 + L.goff + j * 256), 0, 0);
+            ra[j] = *reinterpret_cast<f32x4 *>(&v);
         }
     }
     __syncthreads();
-    if (ABL == 5) {
-        tl0 = __builtin_amdgcn_s_memtime();
-        stamp[5] += tl0 - tp0;
-    }
     // ONE flat loop over the steps: whether a step ends its offset (and which offset follows) is a byte of the step list, read in the
     // step's LDS section and turned into a scalar inside its MFMA block -- no vector instruction outside the MFMA blocks (a lookup
     // of the offset tables between two offsets used to cost three dependent LDS reads and their readfirstlanes, stalled like every
@@ -1003,26 +906,22 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
     for (int i = 0; i < S;) {   // two offsets per trip: the B register sets swap roles without moves
         int info_next = 0;
         for (; !(info & 1); ++i) {
-            srf_gsp_step<NCH, COUT, GP, false, ABL>(rs, wrs, 0, buf, L, G, b0, b1, ra, acc, stamp, info_next);
+            srf_gsp_step<NCH, COUT, false>(rs, wrs, 0, buf, L, G, b0, b1, ra, acc, info_next);
             info = info_next;
         }
-        srf_gsp_step<NCH, COUT, GP, true, ABL>(rs, wrs, info >> 1, buf, L, G, b0, b1, ra, acc, stamp, info_next);
+        srf_gsp_step<NCH, COUT, true>(rs, wrs, info >> 1, buf, L, G, b0, b1, ra, acc, info_next);
         info = info_next;
         if (++i >= S) break;
         for (; !(info & 1); ++i) {
-            srf_gsp_step<NCH, COUT, GP, false, ABL>(rs, wrs, 0, buf, L, G, b1, b0, ra, acc, stamp, info_next);
+            srf_gsp_step<NCH, COUT, false>(rs, wrs, 0, buf, L, G, b1, b0, ra, acc, info_next);
             info = info_next;
         }
-        srf_gsp_step<NCH, COUT, GP, true, ABL>(rs, wrs, info >> 1, buf, L, G, b1, b0, ra, acc, stamp, info_next);
+        srf_gsp_step<NCH, COUT, true>(rs, wrs, info >> 1, buf, L, G, b1, b0, ra, acc, info_next);
         info = info_next;
         ++i;
     }
     // the last step's write-back went through raw LDS addresses: make the whole tile visible to the epilogue's plain reads
     __syncthreads();
-    if (ABL == 5) {
-        te0 = __builtin_amdgcn_s_memtime();
-        stamp[6] += te0 - tl0;
-    }
 
     // epilogue: every output row once, BN / residual / ReLU in registers, 512 B per row and store
     constexpr int CQ = COUT / 4;
@@ -1049,19 +948,7 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
         *reinterpret_cast<f32x4 *>(out + (size_t)row * COUT + c4) = v;
     }
     __syncthreads();
-    if (ABL == 5) {
-        stamp[7] += __builtin_amdgcn_s_memtime() - te0;
-        stamp[4] += 1000000;   // sub-tiles in the millions digit
     }
-    }
-#ifdef SRF_DEV
-    if (ABL == 5 && tid == 0 && blockIdx.x < 512) {
-        long long *dst = srf_gsp_stamps + (size_t)blockIdx.x * 16;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dst[j] = stamp[j];
-        dst[8] = __builtin_amdgcn_s_memtime() - tk0;
-    }
-#endif
 }
 
 // =====================================================================================================================
@@ -1343,53 +1230,16 @@ extern "C" int srf_spconv_fwd_packed(const float *in, int A_in, int Cin, const f
     }
     // SRF_PACKED_GS.  Grid: >= the tiles of any live row count <= A_out / the ranges srf_spconv_tiles_build cut for this capacity
     const dim3 grid(tiles ? srf_gs_ranges(A_out) : SRF_GS_SLOTS * srf_gs_rounds(A_out));
-#define SRF_GSP_LAUNCH(NCH, COUT) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<NCH, COUT>), grid, dim3(256), 0, st, in, A_in, W_packed, K, \
-                                                     nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev, tiles)
+#define GSP_LAUNCH(NCH, COUT) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<NCH, COUT>), grid, dim3(256), 0, st, in, A_in, W_packed, K, \
+                                                 nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev, tiles)
     if (Cout == 64) {
-#ifdef SRF_DEV
-        if (Cin == 64 && (getenv("SRF_GSP_ABL") || getenv("SRF_GSP_GP2"))) {
-            const bool stamp = getenv("SRF_GSP_ABL") && atoi(getenv("SRF_GSP_ABL")) == 5, gp2 = getenv("SRF_GSP_GP2") != nullptr;
-#define SRF_GSP_DEV64(A, G) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<2, 64, A, G>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride, \
-                                               A_out, alpha, beta, residual, relu, out, rows_dev, tiles)
-            if (stamp && gp2) SRF_GSP_DEV64(5, 2);
-            else if (stamp) SRF_GSP_DEV64(5, 1);
-            else if (gp2) SRF_GSP_DEV64(0, 2);
-            else SRF_GSP_DEV64(0, 1);
-#undef SRF_GSP_DEV64
-            SRF_LAUNCH_CHECK();
-            return SRF_OK;
-        }
-#endif
-        if (Cin == 32) SRF_GSP_LAUNCH(1, 64);
-        else SRF_GSP_LAUNCH(2, 64);
+        if (Cin == 32) GSP_LAUNCH(1, 64);
+        else GSP_LAUNCH(2, 64);
     } else {
-#ifdef SRF_DEV
-        if (Cin == 128) {   // SRF_GSP_ABL = ablation (wrong outputs), SRF_GSP_PADLDS = extra LDS bytes (one workgroup per CU from 4000 on)
-            const char *e = getenv("SRF_GSP_ABL"), *pl = getenv("SRF_GSP_PADLDS");
-            const int abl = e ? atoi(e) : 0, pad = pl ? atoi(pl) : 0;
-#define SRF_GSP_DEV(A) hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<4, 128, A>), grid, dim3(256), pad, st, in, A_in, W_packed, K, nbr, nbr_stride, \
-                                          A_out, alpha, beta, residual, relu, out, rows_dev, tiles)
-            if (abl == 1) SRF_GSP_DEV(1);
-            else if (abl == 2) SRF_GSP_DEV(2);
-            else if (abl == 3) SRF_GSP_DEV(3);
-            else if (abl == 4) SRF_GSP_DEV(4);
-            else if (abl == 5) SRF_GSP_DEV(5);
-            else SRF_GSP_DEV(0);
-#undef SRF_GSP_DEV
-            SRF_LAUNCH_CHECK();
-            return SRF_OK;
-        }
-        if (Cin == 64 && getenv("SRF_GSP_ABL") && atoi(getenv("SRF_GSP_ABL")) == 5) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_gsp_k<2, 128, 5>), grid, dim3(256), 0, st, in, A_in, W_packed, K, nbr, nbr_stride,
-                               A_out, alpha, beta, residual, relu, out, rows_dev, tiles);
-            SRF_LAUNCH_CHECK();
-            return SRF_OK;
-        }
-#endif
-        if (Cin == 128) SRF_GSP_LAUNCH(4, 128);
-        else SRF_GSP_LAUNCH(2, 128);
+        if (Cin == 128) GSP_LAUNCH(4, 128);
+        else GSP_LAUNCH(2, 128);
     }
-#undef SRF_GSP_LAUNCH
+#undef GSP_LAUNCH
     SRF_LAUNCH_CHECK();
     return SRF_OK;
 }

@@ -31,7 +31,6 @@
 // Deterministic: every accumulator is one k-ascending fma chain, the transforms have a fixed operation order.
 #include "common.hpp"
 #include <algorithm>
-#include <stdlib.h>
 
 typedef float w43_f32x16 __attribute__((ext_vector_type(16)));
 typedef float w43_f32x4 __attribute__((ext_vector_type(4)));
@@ -55,17 +54,7 @@ struct W43Args {
     int ntb, nchunk, ncb, relu;
     int tb0, n0;       // this launch covers the tile blocks tb0 .. ntb - 1 of the layer (a slab); V holds them from its start;
                        // x and y point at image n0, the image of the slab's first tile (32-bit offsets from there)
-#ifdef SRF_DEV
-    long long *stamps;   // developer build only: 6 s_memtime values per workgroup of srf_wino43_mm_k
-#endif
 };
-#ifdef SRF_DEV
-#define W43_STAMP(I) if (a.stamps && tid == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); a.stamps[(size_t)blockIdx.x * 6 + (I)] = __builtin_amdgcn_s_memtime(); }
-#define W43_STAMP_NW(I) if (a.stamps && tid == 0) { a.stamps[(size_t)blockIdx.x * 6 + (I)] = __builtin_amdgcn_s_memtime(); }
-#else
-#define W43_STAMP(I)
-#define W43_STAMP_NW(I)
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------
 // weights: W (Cout, Cin, 3, 3) -> U = G g G^T, G = [[1/4, 0, 0], [-1/6, -1/6, -1/6], [-1/6, 1/6, -1/6], [1/24, 1/12, 1/6],
@@ -297,10 +286,8 @@ __device__ __forceinline__ void srf_wino43_mm_body(const W43Args &a, const int t
             }                                                                                                            \
     } while (0)
 
-    W43_STAMP_NW(0);
 #pragma unroll
     for (int j = 0; j < 9; ++j) W43_LOAD(j, 0);
-    W43_STAMP(1);
     // chunk 0 .. nchunk - 2: multiply chunk c, reload every frequency's registers with chunk c + 1 right behind its MFMAs
     if (nchunk > 1) {
 #pragma unroll
@@ -325,7 +312,6 @@ __device__ __forceinline__ void srf_wino43_mm_body(const W43Args &a, const int t
     }
 
     // ---- epilogue ----
-    W43_STAMP_NW(2);
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the inline-assembly MFMAs have written their accumulators
     const w43_v2 k2_ = {2.f, 2.f}, k4_ = {4.f, 4.f}, k8_ = {8.f, 8.f};
     float *X = s_x;
@@ -362,7 +348,6 @@ __device__ __forceinline__ void srf_wino43_mm_body(const W43Args &a, const int t
 #pragma unroll
                 for (int rr = 0; rr < 8; ++rr) X[((fbase + j) * 8 + rr) * 64 + lane] = acc[j][0][ph * 8 + rr];
             __syncthreads();
-            if (ph == 0) W43_STAMP_NW(3);
             w43_v2 z[4][6];
 #pragma unroll
             for (int s = 0; s < 6; ++s) {
@@ -389,7 +374,6 @@ __device__ __forceinline__ void srf_wino43_mm_body(const W43Args &a, const int t
                     __builtin_amdgcn_raw_buffer_store_b64(bits, yr, (int)off, 0, 0);
                 }
             }
-            if (ph == 0) W43_STAMP_NW(4);
         }
     } else {
     // Exchange image X[f 36][accumulator register 16][lane 64] floats of one 32-channel half.  Writers: every wave, its 9
@@ -415,7 +399,6 @@ __device__ __forceinline__ void srf_wino43_mm_body(const W43Args &a, const int t
 #pragma unroll
             for (int r = 0; r < 16; ++r) X[((fbase + j) * 16 + r) * 64 + lane] = acc[j][p][r];
         __syncthreads();
-        if (p == 0) W43_STAMP_NW(3);
         const int co = cb * 64 + (NB == 2 ? p : h0) * 32 + co4;   // Cout % 4 == 0: a quad is all inside or all outside
         const bool co_ok = co < a.Cout;
         float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -457,10 +440,8 @@ __device__ __forceinline__ void srf_wino43_mm_body(const W43Args &a, const int t
                 __builtin_amdgcn_raw_buffer_store_b128(bits, yr, (int)off, 0, 0);
             }
         }
-        if (p == 0) W43_STAMP_NW(4);
     }
     }
-    W43_STAMP(5);
 }
 
 // work item -> (half-block index, tile block): items b and b + 8 share an XCD (round-robin dispatch), so the channel blocks of
@@ -501,7 +482,7 @@ extern "C" int srf_wino43_pack_weights(const float *W, int Cout, int Cin, float 
 
 static long long w43_slab_tb(long long ntb, int nchunk, int ncb)
 {
-    static const long long forced = getenv("SRF_W43_SLAB_TB") ? atoll(getenv("SRF_W43_SLAB_TB")) : 0;   // developer A/B knob, read once
+    static const long long forced = srf_knob("SRF_W43_SLAB_TB", 0);
     if (forced > 0) return forced < ntb ? forced : ntb;
     const long long per_tb = (long long)nchunk * 36 * W43_PIECE;
     long long fit = W43_SLAB_BYTES / per_tb;
@@ -565,9 +546,6 @@ static int w43_make_args(W43Args &a, const float *x, int N, int H, int W, int Ci
     if (a.ntiles + W43_TB >= (1ll << 31) || ntb * ((a.nchunk + 3) / 4) >= (1ll << 31) || ntb * a.ncb * 2 >= (1ll << 30)) return SRF_EUNSUPPORTED;
     if ((long long)a.nchunk * 36 * 2 * W43_PIECE >= (1ll << 31)) return SRF_EUNSUPPORTED;   // descriptor range of one U block
     a.ntb = (int)ntb;
-#ifdef SRF_DEV
-    a.stamps = nullptr;
-#endif
     return SRF_OK;
 }
 
@@ -608,7 +586,7 @@ static int w43_launch_mm(const W43Args &a, hipStream_t stream)
         attr_set[dev] = true;
     }
     const long long tb8 = (((long long)(a.ntb - a.tb0) + 7) / 8) * 8;
-    static const int force_nb = getenv("SRF_W43_NB") ? atoi(getenv("SRF_W43_NB")) : 0;   // developer A/B knob, read once
+    static const int force_nb = srf_knob("SRF_W43_NB", 0);
     // 64-channel blocks at one workgroup per CU read half the operand bytes per FLOP; 32-channel halves at two per CU hide each
     // other's prologue / epilogue, waste nothing on Cout = 160 / 224 and give small maps twice the workgroups.  Measured per
     // layer (tools/micro/wino43_bench.hip): halves win except on the large maps whose channel count is a multiple of 64.

@@ -279,12 +279,14 @@ def test_winograd_half_block_kernel_gives_the_same_bits(tmp_path):
     """A last channel block with <= 32 real channels can run on the half-block kernel (waves split the frequencies instead
     of the channels, the upper half hands its accumulators over through LDS): the output transform then performs the same
     operations in the same order, so the results are bit-identical to the one-launch form, whichever the launcher picks.
-    Forms: SRF_WINO_HALF = 0 one-launch / 1 last block as half blocks / 2 every block as two half blocks / 3 the second half of the
-    work items as two half blocks each (the form a partly filled last round takes), each on the 8 x 8, 16 x 4 and 32 x 2 tile
-    blocks (SRF_WINO_TWL).  The knobs are read once per process: one interpreter per setting (tests/forms.py)."""
+    Forms: SRF_WINO_HALF = 0 one-launch / 1 last block as half blocks / 3 the second half of the work items as two half blocks
+    each (the form a partly filled last round takes), each on the 8 x 8, 16 x 4 and 32 x 2 tile blocks (SRF_WINO_TWL).  The knobs
+    are read once per process: one interpreter per setting (tests/forms.py)."""
     from forms import run_forms
-    # every half-block form on the default tile-block shape, every tile-block shape on the one-launch and the all-half forms
-    settings = ([{"SRF_WINO_HALF": h} for h in ("0", "1", "2", "3")] + [{"SRF_WINO_HALF": h, "SRF_WINO_TWL": t} for h in ("0", "2") for t in ("1", "2", "3")])
+    # every half-block form on the default tile-block shape, every tile-block shape on the one-launch and the half-block forms:
+    # SRF_WINO_HALF=0 runs srf_wino3x3_k<TWL, false>; =1 runs srf_wino3x3_k<TWL, true> (Cout = 20, 32: one channel block) and
+    # srf_wino3x3_mixed_k<TWL> (Cout = 96, 160, 224: a last block of 32 channels behind full ones)
+    settings = ([{"SRF_WINO_HALF": h} for h in ("0", "1", "3")] + [{"SRF_WINO_HALF": h, "SRF_WINO_TWL": t} for h in ("0", "1") for t in ("1", "2", "3")])
     res = run_forms(_WINO_FORMS, settings, tmp_path)
     for other in res[1:]:
         for a, b in zip(res[0], other):

@@ -2,7 +2,6 @@
 // events and sampled outputs are compared with a float64 direct convolution on the host.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/micro/wino43_bench.hip -o tools/micro/wino43_bench.bin
 //   ./wino43_bench.bin [N H W Cin Cout]...
-#define SRF_DEV 1
 #include "../../srfdet3d_amd/csrc/wino43.hip"
 #include <algorithm>
 
@@ -113,33 +112,6 @@ static int run(int N, int H, int W, int Cin, int Cout, int reps)
     const double nslab = (double)a.ntb / (double)slab;
     tx = tx / (reps - 2) * nslab;   // scaled to the layer
     tm = tm / (reps - 2) * nslab;
-    {   // in-kernel phases (s_memtime, 100 MHz): median over workgroups
-        const long long tb8 = (((long long)a.ntb + 7) / 8) * 8;
-        const size_t nwg = (size_t)(tb8 * a.ncb);
-        long long *dst;
-        CK(hipMalloc(&dst, nwg * 6 * 8));
-        CK(hipMemset(dst, 0, nwg * 6 * 8));
-        W43Args b;
-        w43_slab_args(a, 0, std::min(w43_slab_tb(a.ntb, a.nchunk, a.ncb), (long long)a.ntb), b);
-        b.stamps = dst;
-        w43_launch_mm(b, nullptr);
-        CK(hipDeviceSynchronize());
-        std::vector<long long> st(nwg * 6);
-        CK(hipMemcpy(st.data(), dst, nwg * 6 * 8, hipMemcpyDeviceToHost));
-        std::vector<double> ph[5];
-        for (size_t w = 0; w < nwg; ++w) {
-            if (st[w * 6 + 5] == 0) continue;
-            for (int k = 0; k < 5; ++k) ph[k].push_back((double)(st[w * 6 + k + 1] - st[w * 6 + k]) * 0.01);
-        }
-        printf("    phases us (median): ");
-        const char *nm[5] = {"first loads", "loop", "exchange0", "transform+store0", "half1"};
-        for (int k = 0; k < 5; ++k) {
-            std::sort(ph[k].begin(), ph[k].end());
-            printf("%s %.2f  ", nm[k], ph[k].empty() ? 0.0 : ph[k][ph[k].size() / 2]);
-        }
-        printf("\n");
-        hipFree(dst);
-    }
     const double direct = 2.0 * 9 * Cin * Cout * (double)N * H * W;
     const double exec = 2.0 * 36 * 32.0 * a.ntb * 64.0 * a.ncb * Cin;   // MFMA FLOPs issued (padded tiles / channels included)
     const double xbytes = (double)nx * 4 + (double)srf_wino43_workspace_bytes(N, H, W, Cin, Cout) * nslab;
