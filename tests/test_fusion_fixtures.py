@@ -79,7 +79,7 @@ def test_gpu_fusion_head_stage_by_stage_matches_reference(dev):
     # free-running loop through SRFDetHead.forward (image DPG + img_convs on MIOpen included).  The stage contract
     # (1e-4) is the teacher-forced loop above; here the differences of the proposals (1e-5) and of the img_convs'
     # summation order feed a random-weight stage that amplifies them ~100x, so the first stage is only required to stay
-    # within 3e-3
+    # within 3e-3 (all five free-running stages at 1e-4 on a damped fixture: test_gpu_decoder_free.py)
     hd2, pf2, imf2, metas2 = lc_head()
     hd2 = hd2.to(dev)
     with torch.no_grad():

@@ -377,7 +377,7 @@ def test_remaining_reference_configs_run_and_graphs_agree(name, n_cam, sweep, np
             g.simple_test(img, [pts[i]], copy.deepcopy(metas))
             e = g._graphed_frame.entry if g._graphed_frame is not None else list(g._graphed_tail.entries.values())[-1]
             # five free-running random-weight stages amplify the last-bit differences between MIOpen's eager and captured
-            # algorithm choices; a broken graph is off by 1e-2 and more
+            # algorithm choices; a broken graph is off by 1e-2 and more (the 1e-4 free-running contract: test_gpu_decoder_free.py)
             torch.testing.assert_close(e["scores"], want[i][0], rtol=0, atol=2e-4)
             # boxes: all but a stray element within 1e-3 (one size entry -- exp() of a free-running delta -- of the Waymo LC
             # config moves by 1e-3..3e-3 from run to run), every element within 1e-2

@@ -2,7 +2,9 @@
 import os
 
 import numpy as np
+import pytest
 
+import detgen
 from make_fixtures import NUSC_RANGE, NUSC_VOXEL, det_boxes
 from oracle import decoder_oracle as DO
 from srfdet3d_amd import synthetic as S
@@ -64,3 +66,65 @@ def test_cpu_head_free_running_matches_reference():
     logits, boxes = pipeline.head_forward(hd, None, feats, None)
     np.testing.assert_allclose(boxes.numpy()[:2], GOLD["head.boxes"][:2], rtol=0, atol=1e-4)
     np.testing.assert_allclose(boxes.numpy()[4], GOLD["head.boxes"][4], rtol=0, atol=0.5)
+
+
+# ---- the damped, trained-like fixture (tests/golden/make_free_fixture.py): the loop as a whole, at half the contract ----
+FREE = np.load(os.path.join(os.path.dirname(__file__), "golden", "decoder_free.npz"))
+
+
+@pytest.mark.parametrize("case", list(detgen.FREE_CASES))
+def test_free_fixture_conditions_hold(case):
+    """the conditions the generator checked on the reference's run before it wrote the file, re-asserted from `meta.*`"""
+    P, bs, fusion = detgen.FREE_CASES[case]
+    m = {k.split(".", 2)[2]: FREE[k] for k in FREE.files if k.startswith(f"meta.{case}.")}
+    assert detgen.free_damping(FREE["meta.damping"]) in detgen.FREE_DAMPINGS
+    assert FREE[f"{case}.boxes"].shape == (5, bs, P, 10) and FREE[f"{case}.boxes"].dtype == np.float32
+    assert float(m["margin"]) >= 2e-4                 # no RoI near a pyramid-level boundary: a flip cannot happen
+    assert m["bev_levels"].shape == (5, 4) and (m["bev_levels"].sum(1) == bs * P).all()
+    assert (m["bev_levels"].min(1) >= 0.01 * bs * P).all()   # every stage uses all four levels
+    assert float(m["move"].min()) >= 0.1              # >= 1000 x the tolerance of movement at every hand-over
+    assert int(m["clamped"]) >= 3
+    if bs > 1:
+        assert float(m["samples_apart"]) >= 0.1
+    if fusion:
+        assert (m["img_levels"].sum(1) == 6 * bs * P).all()
+        # the seed that passed still exercises the hard camera geometry: at every stage more than 5 % of the (box, camera) pairs
+        # straddle the camera's image plane (134 of 1200 at stage 1) and more than a quarter of the image RoIs are wider than
+        # 1e4 px (676 of 1200)
+        assert (m["img_rois_crossing"] > 0.05 * 6 * bs * P).all() and (m["img_rois_wide"] > 0.25 * 6 * bs * P).all()
+        wide = [int(((r[:, 3] - r[:, 1]) > 1e4).sum()) for r in FREE[f"{case}.rois_img"]]
+        assert wide == m["img_rois_wide"].tolist()
+    assert float(m["cpu_box_diff"].max()) <= 5e-5 and float(m["cpu_decode_diff"].max()) <= 5e-5
+    # the fixture's own sensitivity: the reference against itself on inputs perturbed at rounding level (1e-6 relative on the
+    # feature maps, one float32 epsilon on the camera matrices) stays within half the contract, so the other half is the kernels'
+    assert float(m["perturbed_box_diff"].max()) <= 5e-5 and float(m["perturbed_decode_diff"].max()) <= 5e-5
+    # the stored RoIs are the ones the margin was computed from
+    margins = [detgen.level_stats(FREE[f"{case}.rois_bev"][s])[1] for s in range(5)]
+    if fusion:
+        margins += [detgen.level_stats(FREE[f"{case}.rois_img"][s])[1] for s in range(5)]
+    assert min(margins) == pytest.approx(float(m["margin"]), rel=1e-5)
+
+
+@pytest.mark.parametrize("case", list(detgen.FREE_CASES))
+def test_cpu_head_free_running_matches_reference_on_damped_fixture(case):
+    """oracle/pipeline.head_forward FREE-RUNNING over five stages against the reference's own run: boxes within 5e-5 (half
+    the 1e-4 contract, so that the GPU tests' 1e-4 is not used up by the fixture's own sensitivity), logits within half of
+    the GPU tests' logit tolerance.  This pins the oracle pipeline and the host-side stage arithmetic chained over five
+    stages, for the LiDAR head at P = 200 / 900 / bs = 2 and the fusion head.  Measured: see `meta.<case>.cpu_box_diff`."""
+    from detgen import free_metas, repo_head
+    from oracle import pipeline
+    import torch
+    P, bs, fusion = detgen.FREE_CASES[case]
+    k = int(FREE[f"meta.{case}.seed"])
+    bev, img = detgen.free_inputs(case, k)
+    hd = repo_head(case, k, detgen.free_damping(FREE["meta.damping"]))
+    logits, boxes = pipeline.head_forward(hd, [torch.from_numpy(f) for f in img] if fusion else None,
+                                          [torch.from_numpy(f) for f in bev], free_metas(bs))
+    d = np.abs(boxes.numpy() - FREE[f"{case}.boxes"]).max(axis=(1, 2, 3))
+    print(f"\n[free] cpu {case}: boxes per stage {d.tolist()}")
+    np.testing.assert_allclose(boxes.numpy(), FREE[f"{case}.boxes"], rtol=0, atol=5e-5)
+    np.testing.assert_allclose(logits.numpy(), FREE[f"{case}.logits"], rtol=5e-5, atol=1.5e-4 if fusion else 1e-4)
+    with torch.no_grad():
+        scores, dec = hd.decode(logits, boxes.clone())     # the pre-NMS pair of the reference's get_bboxes
+    np.testing.assert_allclose(dec.numpy(), FREE[f"{case}.dec_boxes"], rtol=0, atol=5e-5)
+    np.testing.assert_allclose(scores.numpy(), FREE[f"{case}.dec_scores"], rtol=0, atol=5e-5)
