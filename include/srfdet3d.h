@@ -715,10 +715,16 @@ int srf_decode_boxes(const float *logits, const float *pred, int R, int ncls, in
  * K8  rotated BEV NMS.
  * Replaces mmcv nms_rotated behind mmdet3d box3d_multiclass_nms, called at srfdet_head.py:1288-1293.
  * boxes: (n,5) [cx, cy, w, h, angle(rad)] already sorted by descending score; keep[i] = 1 if box i survives
- * greedy suppression at IoU > iou_threshold.  n <= 4096.
+ * greedy suppression at IoU > iou_threshold.  n <= 4096, else SRF_EUNSUPPORTED.  The IoU is K9's: within 1e-5 of the exact
+ * IoU of the two float32 boxes, also for (nearly) identical boxes, boxes that share edges or corners, the same rectangle
+ * written with yaw + pi or as (h, w, yaw + pi/2), thin boxes, yaw outside [-pi, pi] and centres kilometres from the origin; a
+ * box with w * h < 1e-14 has IoU 0 with every box.
  * ------------------------------------------------------------------------------------------------------- */
 /* K9 pairwise rotated BEV IoU (n x m), boxes (cx, cy, w, h, angle): mmcv box_iou_rotated under mmdet3d
- * BboxOverlaps3D, used by OTAssignerSRFDet (mmdet3d_plugin/core/bbox/assigners/ota_srfdet.py:148-150). */
+ * BboxOverlaps3D, used by OTAssignerSRFDet (mmdet3d_plugin/core/bbox/assigners/ota_srfdet.py:148-150).
+ * iou[i * m + j] is within 1e-5 of the exact IoU of boxes_a[i] and boxes_b[j] and a continuous function of the ten numbers
+ * (no in/out or parallel-edge decision: the intersection area is a boundary integral in boxes_a[i]'s frame, csrc/nms.hip);
+ * 0 when either box has w * h < 1e-14. */
 /* srf_host_pack: the one vector a frame's host side reads back -- packed detections a (na floats), [survivors, candidates] b (nb ints),
  * live row counts of the sparse levels c (nc ints) -> out (na + nb + nc floats; the integers are < 2^24, exact).  One launch. */
 int srf_host_pack(const float *a, int na, const int *b, int nb, const int *c, int nc, float *out, srf_stream_t stream);

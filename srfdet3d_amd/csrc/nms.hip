@@ -7,90 +7,70 @@
 // Two launches: a 64x64-tiled pass writes, for every box, a bit mask of the later boxes it overlaps; one wave then
 // walks the boxes in score order keeping the running "removed" set in registers (one 64-bit word per lane, so up
 // to 4096 boxes), which replaces the device->host copy + CPU loop of the third-party op.
+//
+// The IoU (srf_rotated_iou, shared by the mask kernel and srf_iou_rotated_k) is within 1e-5 of the exact IoU of the two
+// float32 boxes and a continuous function of its ten inputs: what the NMS sees is clusters of nearly identical boxes and
+// the OTA assigner a prediction lying on its ground truth, where a method built on edge-edge intersections, vertex-in-box
+// tests and an angular sort (mmcv's, and this file's before) flips on the last bit -- parallel edges give wild or no
+// intersection points, a vertex on the other box's edge is in or out by rounding -- and returned anything from 0 to 1 for
+// a true IoU of 1.  Here box b is moved into a's frame, where a is the rectangle |x| <= hx, |y| <= hy, and the area of the
+// intersection is the boundary integral of 1[|x| <= hx] clamp(y, -hy, hy) dx over b's four edges (Green's theorem): per
+// edge a clamp of its two x coordinates and a trapezoid rule over at most three pieces.  No vertex list, no in/out
+// decision, no parallel-edge case, no atan2f, no sort, no runtime-indexed array (no scratch).
 #include "common.hpp"
 
-struct P2 {
-    float x, y;
-};
-__device__ __forceinline__ float cross2(P2 a, P2 b) { return a.x * b.y - a.y * b.x; }
-__device__ __forceinline__ float dot2(P2 a, P2 b) { return a.x * b.x + a.y * b.y; }
+__device__ __forceinline__ float srf_clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
-__device__ void srf_rot_vertices(const float *b, float sx, float sy, P2 *p)
+// mean of clamp(y, -h, h) over a segment along which y runs linearly from y0 to y1: the integrand is piecewise linear with
+// kinks where y crosses -h and +h, so the trapezoid rule on the nodes {0, the two crossings clamped onto the segment, 1} is
+// exact, and an ill-conditioned crossing (y0 ~ y1) only moves a node along a stretch where the integrand is flat to O(y1 - y0)
+__device__ __forceinline__ float srf_clamped_mean(float y0, float y1, float h)
 {
-    const float cx = b[0] - sx, cy = b[1] - sy, w = b[2], h = b[3];
-    const float c = cosf(b[4]) * 0.5f, s = sinf(b[4]) * 0.5f;
-    p[0] = {cx - s * h - c * w, cy + c * h - s * w};
-    p[1] = {cx + s * h - c * w, cy - c * h - s * w};
-    p[2] = {2 * cx - p[0].x, 2 * cy - p[0].y};
-    p[3] = {2 * cx - p[1].x, 2 * cy - p[1].y};
+    const float dy = y1 - y0;
+    const float inv = fabsf(dy) > 1e-30f ? 1.0f / dy : 0.0f;
+    const float u = srf_clampf((-h - y0) * inv, 0.0f, 1.0f), v = srf_clampf((h - y0) * inv, 0.0f, 1.0f);
+    const float lo = fminf(u, v), hi = fmaxf(u, v);
+    const float g0 = srf_clampf(y0, -h, h), gl = srf_clampf(y0 + lo * dy, -h, h), gh = srf_clampf(y0 + hi * dy, -h, h),
+                g1 = srf_clampf(y1, -h, h);
+    return 0.5f * (lo * (g0 + gl) + (hi - lo) * (gl + gh) + (1.0f - hi) * (gh + g1));
+}
+
+// one edge (x0, y0) -> (x1, y1) of the other box: the integral of clamp(y, -hy, hy) dx over the part of the edge inside the
+// slab |x| <= hx.  x is monotone along the edge, so that part runs from clamp(x0) to clamp(x1).
+__device__ __forceinline__ float srf_edge_term(float x0, float y0, float x1, float y1, float hx, float hy)
+{
+    const float dx = x1 - x0, dy = y1 - y0;
+    const float c0 = srf_clampf(x0, -hx, hx), c1 = srf_clampf(x1, -hx, hx);
+    const float inv = fabsf(dx) > 1e-30f ? 1.0f / dx : 0.0f;
+    const float ta = srf_clampf((c0 - x0) * inv, 0.0f, 1.0f), tb = srf_clampf((c1 - x0) * inv, 0.0f, 1.0f);
+    return (c1 - c0) * srf_clamped_mean(y0 + ta * dy, y0 + tb * dy, hy);
 }
 
 __device__ float srf_rotated_iou(const float *a, const float *b)
 {
     const float area1 = a[2] * a[3], area2 = b[2] * b[3];
     if (area1 < 1e-14f || area2 < 1e-14f) return 0.0f;
-    const float sx = (a[0] + b[0]) * 0.5f, sy = (a[1] + b[1]) * 0.5f;  // shift to the common centre for precision
-    P2 p1[4], p2[4], v1[4], v2[4], pts[24];
-    srf_rot_vertices(a, sx, sy, p1);
-    srf_rot_vertices(b, sx, sy, p2);
-    for (int i = 0; i < 4; ++i) {
-        v1[i] = {p1[(i + 1) & 3].x - p1[i].x, p1[(i + 1) & 3].y - p1[i].y};
-        v2[i] = {p2[(i + 1) & 3].x - p2[i].x, p2[(i + 1) & 3].y - p2[i].y};
-    }
-    int n = 0;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            const float det = cross2(v2[j], v1[i]);
-            if (fabsf(det) <= 1e-14f) continue;
-            const P2 d = {p2[j].x - p1[i].x, p2[j].y - p1[i].y};
-            const float t1 = cross2(v2[j], d) / det, t2 = cross2(v1[i], d) / det;
-            if (t1 >= 0.0f && t1 <= 1.0f && t2 >= 0.0f && t2 <= 1.0f) pts[n++] = {p1[i].x + v1[i].x * t1, p1[i].y + v1[i].y * t1};
-        }
-    {  // vertices of 1 inside 2
-        const P2 AB = v2[0], DA = v2[3];
-        const float abab = dot2(AB, AB), adad = dot2(DA, DA);
-        for (int i = 0; i < 4; ++i) {
-            const P2 AP = {p1[i].x - p2[0].x, p1[i].y - p2[0].y};
-            const float apab = dot2(AP, AB), apad = -dot2(AP, DA);
-            if (apab >= 0 && apad >= 0 && apab <= abab && apad <= adad) pts[n++] = p1[i];
-        }
-    }
-    {  // vertices of 2 inside 1
-        const P2 AB = v1[0], DA = v1[3];
-        const float abab = dot2(AB, AB), adad = dot2(DA, DA);
-        for (int i = 0; i < 4; ++i) {
-            const P2 AP = {p2[i].x - p1[0].x, p2[i].y - p1[0].y};
-            const float apab = dot2(AP, AB), apad = -dot2(AP, DA);
-            if (apab >= 0 && apad >= 0 && apab <= abab && apad <= adad) pts[n++] = p2[i];
-        }
-    }
-    if (n <= 2) return 0.0f;
-    // the intersection is convex: order its points by angle about their centroid, then the shoelace formula
-    float mx = 0.f, my = 0.f;
-    for (int i = 0; i < n; ++i) {
-        mx += pts[i].x;
-        my += pts[i].y;
-    }
-    mx /= n;
-    my /= n;
-    float ang[24];
-    for (int i = 0; i < n; ++i) ang[i] = atan2f(pts[i].y - my, pts[i].x - mx);
-    for (int i = 1; i < n; ++i) {
-        const float av = ang[i];
-        const P2 pv = pts[i];
-        int j = i - 1;
-        while (j >= 0 && ang[j] > av) {
-            ang[j + 1] = ang[j];
-            pts[j + 1] = pts[j];
-            --j;
-        }
-        ang[j + 1] = av;
-        pts[j + 1] = pv;
-    }
-    float area = 0.f;
-    for (int i = 0; i < n; ++i) area += cross2(pts[i], pts[(i + 1) % n]);
-    area = fabsf(area) * 0.5f;
-    return area / (area1 + area2 - area);
+    // b in a's frame: the differences of nearby centres and angles are exact in float32 however far the pair is from the origin
+    const float ca = cosf(a[4]), sa = sinf(a[4]);
+    const float dx = b[0] - a[0], dy = b[1] - a[1];
+    const float ox = ca * dx + sa * dy, oy = ca * dy - sa * dx;
+    // the angle between them as dt + de exactly (two-sum): for yaws of several radians the rounding of the difference alone,
+    // 5e-7 rad at |dt| > 8, would move the far corners of a 12 m box by 3e-6 m
+    const float dt = b[4] - a[4];
+    const float bv = dt - b[4], av = dt - bv;
+    const float de = (b[4] - av) + (-a[4] - bv);
+    const float cd = cosf(dt), sd = sinf(dt);
+    const float c = (cd - de * sd) * 0.5f, s = (sd + de * cd) * 0.5f;
+    const float ux = c * b[2], uy = s * b[2], vx = -s * b[3], vy = c * b[3];  // b's half axes
+    const float x0 = ox - ux - vx, y0 = oy - uy - vy, x1 = ox + ux - vx, y1 = oy + uy - vy;
+    const float x2 = ox + ux + vx, y2 = oy + uy + vy, x3 = ox - ux + vx, y3 = oy - uy + vy;
+    const float hx = a[2] * 0.5f, hy = a[3] * 0.5f;
+    // area(Q and R) = | closed integral over Q's boundary of 1[|x| <= hx] clamp(y, -hy, hy) dx |  (Green's theorem; R's own
+    // sides inside Q are vertical cuts with dx = 0)
+    const float sum = srf_edge_term(x0, y0, x1, y1, hx, hy) + srf_edge_term(x1, y1, x2, y2, hx, hy) +
+                      srf_edge_term(x2, y2, x3, y3, hx, hy) + srf_edge_term(x3, y3, x0, y0, hx, hy);
+    const float inter = fminf(fabsf(sum), fminf(area1, area2));
+    return inter / (area1 + area2 - inter);
 }
 
 // cls (may be null): class id per box; a box only suppresses boxes of its own class (the per-class loop of mmdet3d's

@@ -838,7 +838,7 @@ def nms_rotated(boxes_xywhr, scores, iou_threshold, classes=None):
     n = boxes_xywhr.shape[0]
     if n == 0:
         return torch.zeros((0,), dtype=torch.long, device=boxes_xywhr.device)
-    order = scores.sort(0, descending=True)[1]
+    order = scores.sort(dim=0, descending=True, stable=True)[1]  # equal scores (equal proposals): lower index first
     sorted_boxes = boxes_xywhr[order].contiguous()
     L = _lib.lib()
     keep = _empty((n,), torch.int32, boxes_xywhr.device)

@@ -174,10 +174,17 @@ def _area(poly):
     return 0.5 * abs(sum(poly[i][0] * poly[(i + 1) % len(poly)][1] - poly[(i + 1) % len(poly)][0] * poly[i][1] for i in range(len(poly))))
 
 
-def bbox_overlaps_3d_f64(b1, b2):
+def bbox_overlaps_3d_f64(b1, b2, bev_inter=None):
     """mmdet3d BboxOverlaps3D(coordinate='lidar') on [x y z dx dy dz yaw ...] with z as the bottom face: rotated BEV
-    intersection (float64 polygon clipping) x height overlap / union volume."""
+    intersection (float64 polygon clipping) x height overlap / union volume.
+    bev_inter: the (n, m) float64 BEV intersection areas computed elsewhere (tests/rotated_iou_ref.intersection, vectorised over
+    pairs) instead of the per-pair clip below; the same composition around them, and the result stays float64."""
     b1, b2 = b1.double().numpy(), b2.double().numpy()
+    if bev_inter is not None:
+        h = np.minimum((b1[:, 2] + b1[:, 5])[:, None], (b2[:, 2] + b2[:, 5])[None, :]) - np.maximum(b1[:, 2][:, None], b2[:, 2][None, :])
+        inter = np.asarray(bev_inter, dtype=np.float64) * np.clip(h, 0, None)
+        vol = (b1[:, 3] * b1[:, 4] * b1[:, 5])[:, None] + (b2[:, 3] * b2[:, 4] * b2[:, 5])[None, :]
+        return torch.from_numpy(inter / np.maximum(vol - inter, 1e-8))
     out = np.zeros((len(b1), len(b2)))
     for i, p in enumerate(b1):
         rp = _rect(p[0], p[1], p[3], p[4], p[6])
