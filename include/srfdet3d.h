@@ -622,6 +622,28 @@ int srf_conv_gemm_nhwc(const float *x, int N, int H, int W, int Cin, long long x
 int srf_stem_conv_nchw(const float *x, int N, int Cin, int H, int W, const float *Wt, int Cout, const float *scale,
                        const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream);
 
+/* srf_dcnv2_nhwc (csrc/dcn.hip): modulated deformable convolution (DCNv2) forward on channels-last activations -- mmcv's
+ * `modulated_deform_conv2d` under `ModulatedDeformConv2dPack`, the 3x3 convolution of the bottlenecks of stages 3 and 4 of
+ * the ResNet-101 image backbone of configs/others/srfdet_dvoxel_waymo_LC.py:68-69 (mmdet ResNet(dcn=dict(type='DCNv2'))):
+ *   y[n][oy][ox][co] = act(scale[co] * sum_{tap, ci} W[co][ci][tap] * m(n, oy, ox, g(ci), tap) * bilinear(x[n][.][.][ci], py, px)
+ *                          + shift[co]),
+ *   py = oy * stride - pad + ky * dilation + dy(n, oy, ox, g, tap),  px likewise with dx,
+ * bilinear sampling with zero padding (a corner outside the map contributes 0; continuous in the offsets), as
+ * srfdet3d_amd/compat/dcn.py defines it.  The srf_conv_gemm_nhwc GEMM with a gathered A operand: W_packed is the same packed
+ * weight (srf_conv1x1_nhwc_pack_weights of W reordered to (Cout, kh * kw * Cin), tap slowest); scale / shift (either may be
+ * NULL; a bias is folded into shift by the caller) and relu as there.  x: (N, H, W, x_ld) with Cin channels, y: (N, Ho, Wo,
+ * y_ld) with Cout channels, Ho = (H + 2 pad - dilation (kh - 1) - 1) / stride + 1.
+ * offset: (N, Ho, Wo, offset_ld) with 2 kh kw G channels, channel (g kh kw + tap) 2 = dy and + 1 = dx; mask: (N, Ho, Wo, mask_ld)
+ * with kh kw G channels, channel g kh kw + tap.  Both may point into one (N, Ho, Wo, 3 kh kw G) buffer, the raw `conv_offset`
+ * output in mmcv's channel order (mask = offset + 2 kh kw G, the same pitch).  mask_is_logit != 0: the kernel applies the
+ * sigmoid; 0: the mask is used as given.  Deterministic: fixed summation order, no atomics.
+ * SRF_EUNSUPPORTED (before any launch): groups != 1, Cin % deform_groups != 0, (Cin / deform_groups) % 32 != 0, H < 2 or
+ * W < 2, the input tensor of 2 GiB or more, x not 16-byte aligned, x_ld % 4 != 0. */
+int srf_dcnv2_nhwc(const float *x, int N, int H, int W, int Cin, long long x_ld, const float *offset, long long offset_ld,
+                   const float *mask, long long mask_ld, int mask_is_logit, const float *W_packed, int Cout, int kh, int kw,
+                   int stride, int pad, int dilation, int groups, int deform_groups, const float *scale, const float *shift,
+                   int relu, float *y, long long y_ld, srf_stream_t stream);
+
 /* ---- streaming layers of the channels-last camera branch (csrc/nhwc.hip); all take (N, H, W, ld) channel slices, C % 4 == 0,
  * 16-byte aligned pointers, ld % 4 == 0 ---------------------------------------------------------------------------------
  * srf_nhwc_affine: y = x * scale[(per_sample & 1 ? n : 0)][c] + shift[(per_sample & 2 ? n : 0)][c] (+ residual), optional ReLU; scale / shift / residual

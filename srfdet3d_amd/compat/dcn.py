@@ -7,8 +7,13 @@ available here, so nothing pins this module against it ("parity unpinned"); it f
   y(p) = sum_k w_k . x(p + p_k + dp_k) . m_k       (Zhu et al., "Deformable ConvNets v2", eq. 1)
 with bilinear sampling and zero padding, and mmcv's tensor conventions: `conv_offset` yields 3.K.G channels, split in three
 chunks (o1, o2, mask); offset = cat(o1, o2) is read as interleaved (dy, dx) pairs per kernel tap; mask = sigmoid(mask).
-Written on torch ops (`grid_sample` per tap), i.e. differentiable and device-agnostic; this branch is not on the measured
-path.  Parameter names follow mmcv (`weight`, `bias`, `conv_offset.weight`, `conv_offset.bias`).
+`modulated_deform_conv2d` below is written on torch ops (`grid_sample` per tap), i.e. differentiable and device-agnostic: it is the
+definition the tests pin (in float64 on the CPU) and the route of the module under autograd, on CPU tensors, in f16 / autocast, for
+shapes the kernel does not take and with SRF_DCN=0.  In inference on f32 GPU tensors the module runs `srf_dcnv2_nhwc`
+(csrc/dcn.hip, `ops.dcnv2_nhwc`): one channels-last copy of x, `conv_offset` as an implicit-im2col GEMM on that copy, the deformable
+convolution reading the raw `conv_offset` output (offsets and mask logits; the sigmoid is in the kernel) with the folded BatchNorm +
+ReLU behind it as its epilogue (`dense.conv_bn_act`), one copy back to NCHW: 4 launches where the torch route takes 136.
+Parameter names follow mmcv (`weight`, `bias`, `conv_offset.weight`, `conv_offset.bias`).
 """
 import math
 
@@ -63,7 +68,45 @@ class ModulatedDeformConv2dPack(nn.Module):
         nn.init.zeros_(self.conv_offset.weight)   # zero offsets and mask logits at the start: a plain conv scaled by 0.5
         nn.init.zeros_(self.conv_offset.bias)
 
+    def hip_route(self, x):
+        """The `srf_dcnv2_nhwc` route applies: inference on an f32 GPU tensor, a shape the kernel takes, SRF_DCN != 0."""
+        from .. import dense, ops
+        return (isinstance(x, torch.Tensor) and x.dim() == 4 and dense.fusable(x) and ops.dcn_enabled() and self.weight.is_cuda
+                and self.weight.dtype == torch.float32 and x.shape[1] == self.in_channels
+                and ops.dcnv2_supported(x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.groups, self.deform_groups))
+
+    def _packed(self, name, weight):
+        """Packed GEMM operand of `weight`, cached on the module until the parameter changes (as dense._packed_1x1)."""
+        from .. import ops
+        vers = (weight._version, weight.data_ptr())
+        cache = getattr(self, name, None)
+        if cache is None or cache[0] != vers:
+            cache = (vers, ops.pack_conv_gemm_weights(weight.detach()))
+            setattr(self, name, cache)
+        return cache[1]
+
+    def forward_hip(self, x, scale=None, shift=None, relu=False):
+        """act(scale * dcn(x) + shift) -> (N, Cout, Ho, Wo) NCHW-contiguous; the module's bias is folded into shift."""
+        from .. import ops
+        if self.bias is not None:
+            b = self.bias.detach() if scale is None else self.bias.detach() * scale
+            shift = b if shift is None else shift + b
+        k = self.kernel_size[0]
+        KG = k * k * self.deform_groups
+        xh = ops.to_channels_last(x).permute(0, 2, 3, 1)
+        co = self.conv_offset
+        if self.dilation == 1:
+            om = ops.conv_gemm_nhwc(xh, self._packed("_srf_packed_offset", co.weight), 3 * KG, (k, k), self.stride, self.padding,
+                                    None, co.bias.detach())
+        else:   # srf_conv_gemm_nhwc has no dilation: the 3 K G-channel convolution stays where it was
+            om = co(x).permute(0, 2, 3, 1).contiguous()
+        y = ops.dcnv2_nhwc(xh, om[..., :2 * KG], om[..., 2 * KG:], self._packed("_srf_packed", self.weight), self.out_channels, (k, k),
+                           self.stride, self.padding, self.dilation, self.deform_groups, True, scale, shift, relu)
+        return y.permute(0, 3, 1, 2).contiguous()
+
     def forward(self, x):
+        if self.hip_route(x):
+            return self.forward_hip(x)
         o1, o2, m = torch.chunk(self.conv_offset(x), 3, dim=1)
         return modulated_deform_conv2d(x, torch.cat((o1, o2), dim=1), torch.sigmoid(m), self.weight, self.bias, self.stride,
                                        self.padding, self.dilation, self.groups, self.deform_groups)

@@ -47,11 +47,20 @@ def _is_dw3x3s2(conv, x):
             and x.dim() == 4 and x.is_contiguous())
 
 
+def _is_dcn(conv):
+    from .compat.dcn import ModulatedDeformConv2dPack
+    return isinstance(conv, ModulatedDeformConv2dPack)
+
+
 def conv_bn_act(conv, bn, relu, x):
     if _is_dw3x3s2(conv, x) and _foldable(bn) and fusable(x):
         # the depthwise stair of the proposal generator: convolution, BatchNorm and ReLU in one streaming kernel
         scale, shift = _fold_bn2d(bn)
         return ops.dwconv3x3s2(x, conv.weight, scale, shift, relu)
+    if _is_dcn(conv) and _foldable(bn) and conv.hip_route(x):
+        # the deformable 3x3 of a ResNet bottleneck (compat/resnet.py): BatchNorm and ReLU as the epilogue of srf_dcnv2_nhwc
+        scale, shift = _fold_bn2d(bn)
+        return conv.forward_hip(x, scale, shift, relu)
     from . import train_conv
     if _train_fusable(x):
         y = train_conv.conv_bn_act(conv, bn, relu, x)   # training: conv + eval BatchNorm + ReLU as one autograd node

@@ -1727,6 +1727,89 @@ def conv_gemm_nhwc_supported(x):
     return x.shape[3] % 32 == 0 and ld % 4 == 0 and x.data_ptr() % 16 == 0 and 4 * x.shape[1] * x.shape[2] * ld < (1 << 31)
 
 
+# ---- modulated deformable convolution, DCNv2 (csrc/dcn.hip) ------------------------------------------------------------
+def dcn_enabled():
+    """SRF_DCN=0 keeps `compat.dcn.ModulatedDeformConv2dPack` on its torch route (one grid_sample, mask multiply, 1x1 conv2d and add per
+    kernel tap) on the GPU as well: the parity reference the tests and tools/bench_dcn.py alternate against, the role SRF_GEMM_SPLIT=0
+    has for the split GEMM.  Read at every call."""
+    return os.environ.get("SRF_DCN", "1") != "0"
+
+
+def dcnv2_out_size(H, W, ksize, stride=1, padding=0, dilation=1):
+    kh, kw = (ksize, ksize) if isinstance(ksize, int) else ksize
+    return (H + 2 * padding - dilation * (kh - 1) - 1) // stride + 1, (W + 2 * padding - dilation * (kw - 1) - 1) // stride + 1
+
+
+def dcnv2_supported(N, C, H, W, groups=1, deform_groups=1, x_ld=None):
+    """Shapes `srf_dcnv2_nhwc` takes, from the shape alone: an (N, C, H, W) input (logical shape; x_ld = floats per pixel of the
+    channels-last buffer, C when None) with convolution groups == 1, C divisible by deform_groups into groups of a multiple of 32
+    channels, H >= 2 and W >= 2 (on a one-row or one-column map compat/dcn.py's normalised grid collapses every position), x_ld % 4 == 0
+    and the whole input below 2 GiB."""
+    ld = C if x_ld is None else x_ld
+    return (groups == 1 and deform_groups >= 1 and C > 0 and C % deform_groups == 0 and (C // deform_groups) % 32 == 0 and H >= 2 and W >= 2
+            and N >= 0 and ld >= C and ld % 4 == 0 and 4 * N * H * W * ld < (1 << 31))
+
+
+def dcnv2_nhwc(x, offset, mask, packed_weight, Cout, ksize, stride=1, pad=0, dilation=1, deform_groups=1, mask_is_logit=False,
+               scale=None, shift=None, relu=False, out=None):
+    """DCNv2 forward on an NHWC slice (`srf_dcnv2_nhwc`): x (N, H, W, Cin); offset (N, Ho, Wo, 2 K G) and mask (N, Ho, Wo, K G) NHWC slices
+    (both may be views of one (N, Ho, Wo, 3 K G) `conv_offset` output); packed_weight from `pack_conv_gemm_weights`; -> (N, Ho, Wo, Cout).
+    mask_is_logit: the kernel applies the sigmoid.  scale / shift / relu: the epilogue of `conv_gemm_nhwc` (fold a bias into shift).
+    No host synchronisation, no allocation outside torch's allocator: capturable in a hipGraph."""
+    x_ld = nhwc_ld(x)
+    N, H, W, Cin = x.shape
+    kh, kw = ksize
+    K, G = kh * kw, int(deform_groups)
+    Ho, Wo = dcnv2_out_size(H, W, ksize, stride, pad, dilation)
+    off_ld, mask_ld = nhwc_ld(offset), nhwc_ld(mask)
+    if tuple(offset.shape) != (N, Ho, Wo, 2 * K * G) or tuple(mask.shape) != (N, Ho, Wo, K * G):
+        raise ValueError(f"dcnv2_nhwc: offset / mask must be (N, Ho, Wo, 2 K G) / (N, Ho, Wo, K G) = {(N, Ho, Wo, 2 * K * G)} / "
+                         f"{(N, Ho, Wo, K * G)}, got {tuple(offset.shape)} / {tuple(mask.shape)}")
+    if out is None:
+        out = _empty((N, Ho, Wo, Cout), torch.float32, x.device)
+    elif tuple(out.shape) != (N, Ho, Wo, Cout):
+        raise ValueError("dcnv2_nhwc: out has the wrong shape")
+    L = _lib.lib()
+    if callable(packed_weight):
+        packed_weight = packed_weight()
+    if packed_weight.numel() * 4 != L.srf_conv1x1_nhwc_packed_weight_bytes(Cout, K * Cin):
+        raise ValueError("dcnv2_nhwc: packed weight does not match the layer")
+    timing = _dense_timing("dcn")
+    check(L.srf_dcnv2_nhwc(_ptr(x), N, H, W, Cin, x_ld, _ptr(offset), off_ld, _ptr(mask), mask_ld, int(bool(mask_is_logit)),
+                           _ptr(packed_weight), Cout, kh, kw, stride, pad, dilation, 1, G, _opt(scale, "scale"), _opt(shift, "shift"),
+                           int(bool(relu)), _ptr(out), nhwc_ld(out), _stream()), "dcnv2_nhwc")
+    if timing is not None:
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev1.record()
+        M = N * Ho * Wo
+        fl = 2.0 * K * Cin * Cout * M + 8.0 * K * Cin * M     # the GEMM + the blend (4 multiply-adds per gathered element)
+        timing[1].append((timing[0], ev1, f"dcn {Cin}->{Cout} {kh}x{kw}/s{stride}/d{dilation}/g{G} @{N}x{H}x{W}", fl, fl,
+                          4.0 * (N * H * W * Cin + M * (Cout + 3 * K * G)) + 4.0 * K * Cin * Cout))
+    return out
+
+
+def modulated_deform_conv2d(x, offset, mask, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, deform_groups=1):
+    """mmcv's functional `modulated_deform_conv2d` on NCHW tensors: x (N, C, H, W), offset (N, 2 K G, Ho, Wo) interleaved (dy, dx) per
+    tap and deformable group, mask (N, K G, Ho, Wo) used as given, weight (Cout, C, kh, kw) -> (N, Cout, Ho, Wo) NCHW-contiguous.
+    Converts the layouts, packs the weight and calls `srf_dcnv2_nhwc`; raises on CPU tensors and on shapes the kernel does not take
+    (`dcnv2_supported`).  Forward only."""
+    x = _dev(x, "x", torch.float32)
+    offset, mask = _dev(offset, "offset", torch.float32), _dev(mask, "mask", torch.float32)
+    weight = _dev(weight, "weight", torch.float32)
+    stride, padding, dilation = (v if isinstance(v, int) else v[0] for v in (stride, padding, dilation))
+    N, C, H, W = x.shape
+    Cout, Cg, kh, kw = weight.shape
+    if not dcnv2_supported(N, C, H, W, groups, deform_groups) or Cg != C:
+        raise RuntimeError(f"srfdet3d_amd: modulated_deform_conv2d does not take x {tuple(x.shape)}, weight {tuple(weight.shape)}, "
+                           f"groups {groups}, deform_groups {deform_groups} (see ops.dcnv2_supported)")
+    xh = to_channels_last(x).permute(0, 2, 3, 1)
+    oh = offset.permute(0, 2, 3, 1).contiguous()
+    mh = mask.permute(0, 2, 3, 1).contiguous()
+    y = dcnv2_nhwc(xh, oh, mh, pack_conv_gemm_weights(weight), Cout, (kh, kw), stride, padding, dilation, deform_groups, False,
+                   None, None if bias is None else _dev(bias, "bias", torch.float32), False)
+    return y.permute(0, 3, 1, 2).contiguous()
+
+
 def stem_conv_nchw(x, weight, scale=None, shift=None, relu=False, out=None):
     """Conv2d(Cin <= 4, 64, 3, stride 2, padding 1) + affine + ReLU from contiguous NCHW images to an NHWC tensor."""
     x = _dev(x, "x", torch.float32)
