@@ -406,6 +406,8 @@ int orc_densify(const float *feats, const int *indices, int A, int C, int B, int
 static inline float bilinear(const float *plane, int H, int W, float y, float x)
 {
     if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return 0.0f;
+    if (!(y == y) || !(x == x)) return 0.0f; /* a NaN coordinate passes every comparison above and (int)NaN is no index: the
+                                                sample contributes nothing, as in the device kernel */
     if (y <= 0.0f) y = 0.0f;
     if (x <= 0.0f) x = 0.0f;
     int y_low = (int)y, x_low = (int)x, y_high, x_high;

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from roi_ref import grad64
 from spconv_ref import conv_ref, conv_ref_autograd, dense_grads
 from srfdet3d_amd import ops
 
@@ -295,68 +296,14 @@ IMG_STRIDES, BEV_STRIDES, FINEST = [4, 8, 16, 32], [8, 16, 32, 64], 56.0
 P, SR = 7, 2
 
 
-def _roi_taps(rois, shapes, strides, lv):
-    """Bilinear taps of every sample point of every RoI, on the level `lv` the kernel chose, with the geometry in float32 op
-    by op as csrc/roi.hip forms it (so that the sample points are the kernel's) and mmcv's RoIAlign(aligned) rules.
-    -> per level: (roi ids, flat tap rows (r, 14, 14, 4) into (N*H*W), weights (r, 14, 14, 4) float64)."""
-    res = []
-    for l, ((N, H, W), s) in enumerate(zip(shapes, strides)):
-        ids = torch.nonzero(lv == l).squeeze(1)
-        b = rois[ids]
-        r = b.shape[0]
-        sc = torch.tensor(1.0 / s, dtype=torch.float32)
-        x1, y1, x2, y2 = (b[:, j] * sc - 0.5 for j in (1, 2, 3, 4))
-        bw, bh = (x2 - x1) / torch.full_like(x1, P), (y2 - y1) / torch.full_like(y1, P)
-        j = torch.arange(P * SR)
-        pp, ii = (j // SR).float(), (j % SR).float() + 0.5
-        ys = (y1[:, None] + pp * bh[:, None]) + (ii * bh[:, None]) / torch.full((r, P * SR), float(SR))
-        xs = (x1[:, None] + pp * bw[:, None]) + (ii * bw[:, None]) / torch.full((r, P * SR), float(SR))
-        n = b[:, 0].long()   # (int) truncation, as the kernel
-        ok_n = (n >= 0) & (n < N)
-
-        def axis(v, size):
-            ok = ~((v < -1.0) | (v > size))
-            v = v.clamp(min=0.0)
-            lo = v.long()
-            top = lo >= size - 1
-            lo = torch.where(top, torch.full_like(lo, size - 1), lo)
-            hi = torch.where(top, lo, lo + 1)
-            v = torch.where(top, lo.float(), v)
-            frac = v - lo.float()
-            return ok, lo, hi, frac, 1.0 - frac
-
-        oky, yl, yh, ly, hy = axis(ys, H)
-        okx, xl, xh, lx, hx = axis(xs, W)
-        ok = (oky[:, :, None] & okx[:, None, :] & ok_n[:, None, None]).unsqueeze(-1)
-        w = torch.stack([hy[:, :, None] * hx[:, None, :], hy[:, :, None] * lx[:, None, :], ly[:, :, None] * hx[:, None, :],
-                         ly[:, :, None] * lx[:, None, :]], -1).double() * ok
-        nn_ = n.clamp(0, N - 1)[:, None, None]
-        row = lambda yy, xx: (nn_ * H + yy[:, :, None]) * W + xx[:, None, :]
-        taps = torch.stack([row(yl, xl), row(yl, xh), row(yh, xl), row(yh, xh)], -1)
-        res.append((ids, taps, w))
-    return res
+ROI_BWD_TOL = 1e-5         # |gradient - float64 gradient| over the sum of |weight * output gradient| of the element
 
 
 def _roi_grad_ref(shapes, strides, rois, lv, g_bm, dev, chunk=64):
-    """float64 gradient of the gather w.r.t. each map, channels-last (N, H, W, C), and its magnitude sums.
-    g_bm: (R, P*P, C) output gradient in bin-major form."""
-    C = g_bm.shape[2]
-    grads, mags = [], []
-    for (N, H, W), (ids, taps, w) in zip(shapes, _roi_taps(rois, shapes, strides, lv)):
-        gr = torch.zeros(N * H * W, C, dtype=torch.float64, device=dev)
-        mg = torch.zeros_like(gr)
-        for c0 in range(0, ids.shape[0], chunk):
-            sl = slice(c0, c0 + chunk)
-            g = g_bm[ids[sl].to(dev)].double().view(-1, P, P, C) * 0.25
-            g = g.repeat_interleave(SR, 1).repeat_interleave(SR, 2)            # (r, 14, 14, C): each bin's four samples
-            t, ww = taps[sl].to(dev), w[sl].to(dev)
-            for q in range(4):
-                src = ww[..., q:q + 1] * g
-                gr.index_add_(0, t[..., q].reshape(-1), src.reshape(-1, C))
-                mg.index_add_(0, t[..., q].reshape(-1), src.abs().reshape(-1, C))
-        grads.append(gr.view(N, H, W, C))
-        mags.append(mg.view(N, H, W, C))
-    return grads, mags
+    """float64 gradient of the gather w.r.t. each map, channels-last (N, H, W, C), and its magnitude sums, on the level `lv`
+    the kernel chose (tests/roi_ref.py: the geometry in float32 op by op as csrc/roi.hip forms it, mmcv's RoIAlign(aligned)
+    rules, float64 from the sample point on).  g_bm: (R, P*P, C) output gradient in bin-major form."""
+    return grad64(shapes, strides, rois, g_bm, P, SR, FINEST, lv=lv, dev=dev, chunk=chunk)
 
 
 def _mmdet_level(rois, nl):
@@ -429,7 +376,7 @@ def test_roi_extract_backward_training_form(dev):
             for l in range(4):
                 assert ref[l].abs().sum() > 0
                 err = ((got[l].double() - ref[l]).abs() / mag[l].clamp_min(1e-300)).max().item()
-                assert err <= 1e-5, f"{name} bin_major/channels_last {key} level {l}: {err:.3e}"
+                assert err <= ROI_BWD_TOL, f"{name} bin_major/channels_last {key} level {l}: {err:.3e}"
                 worst = max(worst, err)
         print(f"\nroi bwd {name}: {rois.shape[0]} RoIs, levels {torch.bincount(lv, minlength=4).tolist()}, worst normalised error "
               f"{worst:.2e}")
