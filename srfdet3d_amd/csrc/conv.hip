@@ -33,6 +33,7 @@
 // differs from a direct convolution by a few f32 roundings (tested against torch at 2e-4 of the map's max, the bar of the
 // SECOND / FPN tests).
 #include "common.hpp"
+#include "gemm_host.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1040,43 +1041,28 @@ extern "C" int srf_conv1x1_nhwc_pack_weights(const float *W, int Cout, int K, fl
     return SRF_OK;
 }
 
-// shared launcher: bpi == 0 -> flat row tiling; bpi > 0 -> per-image tiling with column sums into `colsum`
-struct TopDown {
-    const float *top;
-    long long top_ld;
-    int mapH, mapW, topH, topW;
-};
+static const SrfGemmFamily GEMM_LDS = {256, false, 64};   // x rows of a 256-row span; y by plain stores; column sums per block of >= 64 rows
 
+// the fields every launch of this family sets; the rest of GemmArgs starts as zero
+static GemmArgs gemm_args(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
+                          const float *shift, int relu, float *y, long long y_ld)
+{
+    GemmArgs a = {};
+    srf_gemm_set_base(a, x, M, K, x_ld, Cout, scale, shift, relu, y, y_ld);
+    a.Wp = reinterpret_cast<const f32x4 *>(W_packed);
+    a.coutBlocks = srf_ceil_div(Cout, 256);
+    return a;
+}
+
+// shared launcher: bpi == 0 -> flat row tiling; bpi > 0 -> per-image tiling with column sums into `colsum`
 static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
                           const float *shift, int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream,
-                          int *bpi_out = nullptr, const TopDown *td = nullptr)
+                          int *bpi_out = nullptr, const SrfGemmTop *td = nullptr)
 {
-    GemmArgs a;
-    a.x = x;
-    a.y = y;
-    a.Wp = reinterpret_cast<const f32x4 *>(W_packed);
-    a.scale = scale;
-    a.shift = shift;
-    a.x_ld = x_ld;
-    a.y_ld = y_ld;
-    a.M = M;
-    a.K = K;
-    a.Cout = Cout;
-    a.coutBlocks = srf_ceil_div(Cout, 256);
-    a.nchunk = K / 32;
-    a.relu = relu;
-    a.H = a.W = a.Ho = a.Wo = a.kw = a.stride = a.pad = a.cin_chunks = 0;
-    a.x_bytes = 0;
+    GemmArgs a = gemm_args(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
     a.colsum = colsum;
     a.HW = HW;
-    a.top = td ? td->top : nullptr;
-    a.top_ld = td ? td->top_ld : 0;
-    a.mapH = td ? td->mapH : 0;
-    a.mapW = td ? td->mapW : 0;
-    a.topH = td ? td->topH : 0;
-    a.topW = td ? td->topW : 0;
-    a.sy = td ? (float)td->topH / (float)td->mapH : 0.f;
-    a.sx = td ? (float)td->topW / (float)td->mapW : 0.f;
+    srf_gemm_set_top(a, td);
     int dev = 0;
     SRF_HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
@@ -1084,8 +1070,6 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
     int TM = 128, ncs = 2;
     // below ~0.8 rounds of 128 x 128 tiles at three per CU the 64 x 64 tiles win (stage 5 of VoVNet: 544 tiles, 417 -> 386 us)
     if (srf_ceil_div(M, 128) * srf_ceil_div(Cout, 128) < 640) TM = 64, ncs = 4;  // small problem: 64 x 64 tiles
-    a.row0 = 0;
-    a.slot0 = 0;
     const long long nimg = colsum ? M / HW : 1;
     if (colsum) {
         a.bpi = (int)srf_ceil_div(HW, TM);
@@ -1093,8 +1077,6 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
         a.mblocks = nimg * a.bpi;
         if (bpi_out) *bpi_out = a.bpi;
     } else {
-        a.bpi = 0;
-        a.slots = 0;
         a.mblocks = srf_ceil_div(M, TM);
     }
     // tail of the last, partly filled round of 128 x 128 tiles as 64 x 64 tiles (SRF_GEMM_TAIL=0 turns it off; developer A/B knob)
@@ -1144,11 +1126,8 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
 extern "C" int srf_conv1x1_nhwc(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
                                 const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream)
 {
-    if (M < 0 || K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout) return SRF_EINVAL;
-    if (M == 0) return SRF_OK;
-    if (!x || !W_packed || !y) return SRF_EINVAL;
-    if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    if (x_ld * 256 * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
+    const int rc = srf_gemm_check_1x1(GEMM_LDS, M, K, x_ld, x, W_packed, Cout, y, y_ld);
+    if (rc != SRF_OK || M == 0) return rc;
     return conv1x1_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream);
 }
 
@@ -1160,12 +1139,9 @@ extern "C" int srf_conv1x1_nhwc_topdown(const float *x, int N, int H, int W, int
                                         const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt, long long top_ld,
                                         float *y, long long y_ld, srf_stream_t stream)
 {
-    if (N < 0 || H <= 0 || W <= 0 || Ht <= 0 || Wt <= 0 || K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout || top_ld < Cout) return SRF_EINVAL;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y || !top) return SRF_EINVAL;
-    if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    if (x_ld * 256 * 4 >= (1ll << 31) || (long long)N * Ht * Wt * top_ld >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    const TopDown td = {top, top_ld, H, W, Ht, Wt};
+    const SrfGemmTop td = {top, top_ld, H, W, Ht, Wt};
+    const int rc = srf_gemm_check_1x1(GEMM_LDS, N, K, x_ld, x, W_packed, Cout, y, y_ld, &td);
+    if (rc != SRF_OK || N == 0) return rc;
     return conv1x1_launch(x, (long long)N * H * W, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream,
                           nullptr, &td);
 }
@@ -1177,8 +1153,8 @@ extern "C" int srf_conv1x1_nhwc_topdown(const float *x, int N, int H, int W, int
 #define PM_GROUPS 16
 // 256 threads = 16 channels x 16 groups; group g adds the blocks g, g + 16, ... of its image, the 16 group sums are then added
 // in group order: a fixed order whatever the grid
-__global__ __launch_bounds__(256) void srf_conv1x1_pool_finish_k(const float *__restrict__ partial, int bpi, int C, float inv,
-                                                                 float *__restrict__ mean)
+__global__ __launch_bounds__(256) void srf_gemm_pool_finish_k(const float *__restrict__ partial, int bpi, int C, float inv,
+                                                              float *__restrict__ mean)
 {
     __shared__ float s[PM_GROUPS][16];
     const int n = blockIdx.y, cl = threadIdx.x & 15, c = blockIdx.x * 16 + cl, g = threadIdx.x >> 4;
@@ -1195,29 +1171,30 @@ __global__ __launch_bounds__(256) void srf_conv1x1_pool_finish_k(const float *__
     }
 }
 
+int srf_gemm_pool_finish(const float *partial, int bpi, int N, int Cout, long long HW, float *mean, hipStream_t stream)
+{
+    hipLaunchKernelGGL(srf_gemm_pool_finish_k, dim3(srf_ceil_div(Cout, 16), N), dim3(256), 0, stream, partial, bpi, Cout, 1.0f / (float)HW, mean);
+    SRF_LAUNCH_CHECK();
+    return SRF_OK;
+}
+
 extern "C" size_t srf_conv1x1_nhwc_pooled_workspace_bytes(int N, long long HW, int Cout)
 {
-    return (N <= 0 || HW <= 0 || Cout <= 0) ? 0 : (size_t)N * (size_t)srf_ceil_div(HW, 64) * Cout * 4;  // row blocks of >= 64
+    return (N <= 0 || HW <= 0 || Cout <= 0) ? 0 : srf_gemm_pool_bytes(N, HW, Cout, GEMM_LDS.pool_rows);  // row blocks of >= 64
 }
 
 extern "C" int srf_conv1x1_nhwc_pooled(const float *x, int N, long long HW, int K, long long x_ld, const float *W_packed, int Cout,
                                        const float *scale, const float *shift, int relu, float *y, long long y_ld, float *mean, void *workspace,
                                        size_t workspace_bytes, srf_stream_t stream)
 {
-    if (N < 0 || HW <= 0 || K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout) return SRF_EINVAL;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y || !mean || !workspace) return SRF_EINVAL;
-    if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15) || N > 65535) return SRF_EUNSUPPORTED;
-    if (x_ld * 256 * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    if (workspace_bytes < srf_conv1x1_nhwc_pooled_workspace_bytes(N, HW, Cout)) return SRF_EWORKSPACE;
+    const SrfGemmPool pool = {HW, mean, workspace, workspace_bytes};
+    int rc = srf_gemm_check_1x1(GEMM_LDS, N, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, &pool);
+    if (rc != SRF_OK || N == 0) return rc;
     int bpi = 0;
-    const int rc = conv1x1_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW,
-                                  (hipStream_t)stream, &bpi);
+    rc = conv1x1_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW,
+                        (hipStream_t)stream, &bpi);
     if (rc != SRF_OK) return rc;
-    hipLaunchKernelGGL(srf_conv1x1_pool_finish_k, dim3(srf_ceil_div(Cout, 16), N), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)workspace, bpi, Cout, 1.0f / (float)HW, mean);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
+    return srf_gemm_pool_finish((const float *)workspace, bpi, N, Cout, HW, mean, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1232,47 +1209,12 @@ extern "C" int srf_conv_gemm_nhwc(const float *x, int N, int H, int W, int Cin, 
                                   int kw, int stride, int pad, const float *scale, const float *shift, int relu, float *y, long long y_ld,
                                   srf_stream_t stream)
 {
-    if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || x_ld < Cin || y_ld < Cout)
-        return SRF_EINVAL;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y) return SRF_EINVAL;
-    if ((Cin & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return SRF_EINVAL;
-    const long long x_bytes = (long long)N * H * W * x_ld * 4;
-    if (x_bytes >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    GemmArgs a;
-    a.x = x;
-    a.y = y;
-    a.Wp = reinterpret_cast<const f32x4 *>(W_packed);
-    a.scale = scale;
-    a.shift = shift;
-    a.x_ld = x_ld;
-    a.y_ld = y_ld;
-    a.M = (long long)N * Ho * Wo;
-    a.K = kh * kw * Cin;
-    a.Cout = Cout;
-    a.coutBlocks = srf_ceil_div(Cout, 256);
-    a.nchunk = a.K / 32;
-    a.relu = relu;
-    a.H = H;
-    a.W = W;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.kw = kw;
-    a.stride = stride;
-    a.pad = pad;
-    a.cin_chunks = Cin / 32;
-    a.x_bytes = x_bytes;
-    a.colsum = nullptr;
-    a.row0 = 0;
-    a.slot0 = a.slots = 0;
-    a.HW = 0;
-    a.bpi = 0;
-    a.top = nullptr;
-    a.top_ld = 0;
-    a.mapH = a.mapW = a.topH = a.topW = 0;
-    a.sy = a.sx = 0.f;
+    int Ho = 0, Wo = 0;
+    long long x_bytes = 0;
+    const int rc = srf_gemm_check_conv(GEMM_LDS, N, H, W, Cin, x_ld, x, W_packed, Cout, kh, kw, stride, pad, y, y_ld, &Ho, &Wo, &x_bytes);
+    if (rc != SRF_OK || N == 0) return rc;
+    GemmArgs a = gemm_args(x, (long long)N * Ho * Wo, kh * kw * Cin, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
+    srf_gemm_set_conv(a, H, W, Ho, Wo, kw, stride, pad, Cin, x_bytes);
     a.mblocks = srf_ceil_div(a.M, 128);
     long long blocks = ((a.mblocks + 7) / 8) * 8 * srf_ceil_div(Cout, 128);
     if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;

@@ -17,6 +17,7 @@
 // The order of the fma chain of every output is the one of srf_conv1x1_nhwc_k (sub-step s of a chunk multiplies the channels
 // 8 s + i (lanes 0-31) and 8 s + 4 + i (lanes 32-63), i = 0..3): identical bits.
 #include "common.hpp"
+#include "gemm_host.hpp"
 
 typedef float gd_f32x16 __attribute__((ext_vector_type(16)));
 typedef float gd_f32x4 __attribute__((ext_vector_type(4)));
@@ -217,45 +218,23 @@ extern "C" int srf_conv1x1_nhwc_direct_pack_weights(const float *W, int Cout, in
     return SRF_OK;
 }
 
-struct GdTop {
-    const float *top;
-    long long top_ld;
-    int mapH, mapW, topH, topW;
-};
+static const SrfGemmFamily GEMM_DIRECT = {128, true, 128};   // x and y through descriptors of one 128-row tile
 
 static int gd_launch(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale, const float *shift,
-                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const GdTop *td = nullptr)
+                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr)
 {
-    GdArgs a;
-    a.x = x;
-    a.y = y;
+    GdArgs a = {};
+    srf_gemm_set_base(a, x, M, K, x_ld, Cout, scale, shift, relu, y, y_ld);
     a.Wd = W_packed;
-    a.scale = scale;
-    a.shift = shift;
-    a.x_ld = x_ld;
-    a.y_ld = y_ld;
-    a.M = M;
-    a.K = K;
-    a.Cout = Cout;
-    a.nchunk = K / 32;
     a.nct = srf_ceil_div(Cout, 128);
-    a.relu = relu;
     a.colsum = colsum;
     a.HW = HW;
-    a.top = td ? td->top : nullptr;
-    a.top_ld = td ? td->top_ld : 0;
-    a.mapH = td ? td->mapH : 0;
-    a.mapW = td ? td->mapW : 0;
-    a.topH = td ? td->topH : 0;
-    a.topW = td ? td->topW : 0;
-    a.sy = td ? (float)td->topH / (float)td->mapH : 0.f;
-    a.sx = td ? (float)td->topW / (float)td->mapW : 0.f;
+    srf_gemm_set_top(a, td);
     if (colsum) {
         a.bpi = (int)srf_ceil_div(HW, 128);
         a.mblocks = (M / HW) * a.bpi;
         if (bpi_out) *bpi_out = a.bpi;
     } else {
-        a.bpi = 0;
         a.mblocks = srf_ceil_div(M, 128);
     }
     if (srf_conv1x1_nhwc_direct_packed_weight_bytes(Cout, K) >= ((size_t)1 << 31)) return SRF_EUNSUPPORTED;   // descriptor range of Wd
@@ -274,11 +253,8 @@ static int gd_launch(const float *x, long long M, int K, long long x_ld, const f
 extern "C" int srf_conv1x1_nhwc_direct(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
                                        const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream)
 {
-    if (M < 0 || K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout) return SRF_EINVAL;
-    if (M == 0) return SRF_OK;
-    if (!x || !W_packed || !y) return SRF_EINVAL;
-    if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    if (x_ld * 128 * 4 >= (1ll << 31) || y_ld * 128 * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
+    const int rc = srf_gemm_check_1x1(GEMM_DIRECT, M, K, x_ld, x, W_packed, Cout, y, y_ld);
+    if (rc != SRF_OK || M == 0) return rc;
     return gd_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr);
 }
 
@@ -286,50 +262,23 @@ extern "C" int srf_conv1x1_nhwc_direct_topdown(const float *x, int N, int H, int
                                                const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt,
                                                long long top_ld, float *y, long long y_ld, srf_stream_t stream)
 {
-    if (N < 0 || H <= 0 || W <= 0 || Ht <= 0 || Wt <= 0 || K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout || top_ld < Cout) return SRF_EINVAL;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y || !top) return SRF_EINVAL;
-    if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    if (x_ld * 128 * 4 >= (1ll << 31) || y_ld * 128 * 4 >= (1ll << 31) || (long long)N * Ht * Wt * top_ld >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    const GdTop td = {top, top_ld, H, W, Ht, Wt};
+    const SrfGemmTop td = {top, top_ld, H, W, Ht, Wt};
+    const int rc = srf_gemm_check_1x1(GEMM_DIRECT, N, K, x_ld, x, W_packed, Cout, y, y_ld, &td);
+    if (rc != SRF_OK || N == 0) return rc;
     return gd_launch(x, (long long)N * H * W, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, &td);
 }
 
 // the pooled form: as srf_conv1x1_nhwc_pooled (conv.hip); workspace = srf_conv1x1_nhwc_pooled_workspace_bytes(N, HW, Cout)
-__global__ __launch_bounds__(256) void srf_gemm_direct_pool_finish_k(const float *__restrict__ partial, int bpi, int C, float inv,
-                                                                    float *__restrict__ mean)
-{
-    __shared__ float s[16][16];
-    const int n = blockIdx.y, cl = threadIdx.x & 15, c = blockIdx.x * 16 + cl, g = threadIdx.x >> 4;
-    float acc = 0.f;
-    if (c < C)
-        for (int b = g; b < bpi; b += 16) acc += partial[((long long)n * bpi + b) * C + c];
-    s[g][cl] = acc;
-    __syncthreads();
-    if (g == 0 && c < C) {
-        float t = s[0][cl];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) t += s[k][cl];
-        mean[(long long)n * C + c] = t * inv;
-    }
-}
-
 extern "C" int srf_conv1x1_nhwc_direct_pooled(const float *x, int N, long long HW, int K, long long x_ld, const float *W_packed, int Cout,
                                               const float *scale, const float *shift, int relu, float *y, long long y_ld, float *mean,
                                               void *workspace, size_t workspace_bytes, srf_stream_t stream)
 {
-    if (N < 0 || HW <= 0 || K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout) return SRF_EINVAL;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y || !mean || !workspace) return SRF_EINVAL;
-    if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15) || N > 65535) return SRF_EUNSUPPORTED;
-    if (x_ld * 128 * 4 >= (1ll << 31) || y_ld * 128 * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    if (workspace_bytes < (size_t)N * (size_t)srf_ceil_div(HW, 128) * Cout * 4) return SRF_EWORKSPACE;
+    const SrfGemmPool pool = {HW, mean, workspace, workspace_bytes};
+    int rc = srf_gemm_check_1x1(GEMM_DIRECT, N, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, &pool);
+    if (rc != SRF_OK || N == 0) return rc;
     int bpi = 0;
-    const int rc = gd_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW,
-                             (hipStream_t)stream, &bpi);
+    rc = gd_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW, (hipStream_t)stream,
+                   &bpi);
     if (rc != SRF_OK) return rc;
-    hipLaunchKernelGGL(srf_gemm_direct_pool_finish_k, dim3(srf_ceil_div(Cout, 16), N), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)workspace, bpi, Cout, 1.0f / (float)HW, mean);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
+    return srf_gemm_pool_finish((const float *)workspace, bpi, N, Cout, HW, mean, (hipStream_t)stream);
 }

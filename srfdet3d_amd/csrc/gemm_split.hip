@@ -47,6 +47,7 @@
 // First version measured (same shapes): 189-199 TFLOP/s f32-equivalent (1.13-1.20 PFLOP/s of bf16 issued) on the three large
 // layers against 122-135 for the f32 kernels.
 #include "common.hpp"
+#include "gemm_host.hpp"
 
 typedef __bf16 gs_bf2 __attribute__((ext_vector_type(2)));
 typedef __bf16 gs_bf8 __attribute__((ext_vector_type(8)));
@@ -356,47 +357,31 @@ extern "C" int srf_conv1x1_nhwc_split_pack_weights(const float *W, int Cout, int
     return SRF_OK;
 }
 
-struct GsTop {
-    const float *top;
-    long long top_ld;
-    int mapH, mapW, topH, topW;
-};
+static const SrfGemmFamily GEMM_SPLIT = {128, true, 128};   // x and y through descriptors of one 128-row tile
+
+// the fields every launch of this family sets; the rest of GsArgs starts as zero
+static GsArgs gs_args(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale, const float *shift,
+                      int relu, float *y, long long y_ld)
+{
+    GsArgs a = {};
+    srf_gemm_set_base(a, x, M, K, x_ld, Cout, scale, shift, relu, y, y_ld);
+    a.Wp = (const unsigned char *)W_packed;
+    a.nct = srf_ceil_div(Cout, 128);
+    return a;
+}
 
 static int gs_launch(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale, const float *shift,
-                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const GsTop *td = nullptr)
+                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr)
 {
-    GsArgs a;
-    a.x = x;
-    a.y = y;
-    a.Wp = (const unsigned char *)W_packed;
-    a.scale = scale;
-    a.shift = shift;
-    a.x_ld = x_ld;
-    a.y_ld = y_ld;
-    a.M = M;
-    a.K = K;
-    a.Cout = Cout;
-    a.nchunk = K / 32;
-    a.nct = srf_ceil_div(Cout, 128);
-    a.relu = relu;
+    GsArgs a = gs_args(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
     a.colsum = colsum;
     a.HW = HW;
-    a.top = td ? td->top : nullptr;
-    a.top_ld = td ? td->top_ld : 0;
-    a.mapH = td ? td->mapH : 0;
-    a.mapW = td ? td->mapW : 0;
-    a.topH = td ? td->topH : 0;
-    a.topW = td ? td->topW : 0;
-    a.sy = td ? (float)td->topH / (float)td->mapH : 0.f;
-    a.sx = td ? (float)td->topW / (float)td->mapW : 0.f;
-    a.H = a.W = a.Ho = a.Wo = a.kw = a.stride = a.pad = a.cin_chunks = 0;
-    a.x_bytes = 0;
+    srf_gemm_set_top(a, td);
     if (colsum) {
         a.bpi = (int)srf_ceil_div(HW, 128);
         a.mblocks = (M / HW) * a.bpi;
         if (bpi_out) *bpi_out = a.bpi;
     } else {
-        a.bpi = 0;
         a.mblocks = srf_ceil_div(M, 128);
     }
     const long long blocks = ((a.mblocks + 7) / 8) * 8 * a.nct;
@@ -419,45 +404,12 @@ extern "C" int srf_conv_gemm_nhwc_split(const float *x, int N, int H, int W, int
                                         int kw, int stride, int pad, const float *scale, const float *shift, int relu, float *y,
                                         long long y_ld, srf_stream_t stream)
 {
-    if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || x_ld < Cin || y_ld < Cout)
-        return SRF_EINVAL;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y) return SRF_EINVAL;
-    if ((Cin & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return SRF_EINVAL;
-    const long long x_bytes = (long long)N * H * W * x_ld * 4;
-    if (x_bytes >= (1ll << 31) || y_ld * 128 * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    GsArgs a;
-    a.x = x;
-    a.y = y;
-    a.Wp = (const unsigned char *)W_packed;
-    a.scale = scale;
-    a.shift = shift;
-    a.x_ld = x_ld;
-    a.y_ld = y_ld;
-    a.M = (long long)N * Ho * Wo;
-    a.K = kh * kw * Cin;
-    a.Cout = Cout;
-    a.nchunk = a.K / 32;
-    a.nct = srf_ceil_div(Cout, 128);
-    a.relu = relu;
-    a.colsum = nullptr;
-    a.HW = 0;
-    a.bpi = 0;
-    a.top = nullptr;
-    a.top_ld = 0;
-    a.mapH = a.mapW = a.topH = a.topW = 0;
-    a.sy = a.sx = 0.f;
-    a.H = H;
-    a.W = W;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.kw = kw;
-    a.stride = stride;
-    a.pad = pad;
-    a.cin_chunks = Cin / 32;
-    a.x_bytes = x_bytes;
+    int Ho = 0, Wo = 0;
+    long long x_bytes = 0;
+    const int rc = srf_gemm_check_conv(GEMM_SPLIT, N, H, W, Cin, x_ld, x, W_packed, Cout, kh, kw, stride, pad, y, y_ld, &Ho, &Wo, &x_bytes);
+    if (rc != SRF_OK || N == 0) return rc;
+    GsArgs a = gs_args(x, (long long)N * Ho * Wo, kh * kw * Cin, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
+    srf_gemm_set_conv(a, H, W, Ho, Wo, kw, stride, pad, Cin, x_bytes);
     a.mblocks = srf_ceil_div(a.M, 128);
     const long long blocks = ((a.mblocks + 7) / 8) * 8 * a.nct;
     if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
@@ -466,22 +418,11 @@ extern "C" int srf_conv_gemm_nhwc_split(const float *x, int N, int H, int W, int
     return SRF_OK;
 }
 
-static int gs_check(const float *x, int K, long long x_ld, const void *W_packed, int Cout, long long y_ld)
-{
-    if (K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout) return SRF_EINVAL;
-    if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    if (x_ld * 128 * 4 >= (1ll << 31) || y_ld * 128 * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    return SRF_OK;
-}
-
 extern "C" int srf_conv1x1_nhwc_split(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale,
                                       const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream)
 {
-    if (M < 0) return SRF_EINVAL;
-    const int rc = gs_check(x, K, x_ld, W_packed, Cout, y_ld);
-    if (rc != SRF_OK) return rc;
-    if (M == 0) return SRF_OK;
-    if (!x || !W_packed || !y) return SRF_EINVAL;
+    const int rc = srf_gemm_check_1x1(GEMM_SPLIT, M, K, x_ld, x, W_packed, Cout, y, y_ld);
+    if (rc != SRF_OK || M == 0) return rc;
     return gs_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr);
 }
 
@@ -489,51 +430,23 @@ extern "C" int srf_conv1x1_nhwc_split_topdown(const float *x, int N, int H, int 
                                               const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt,
                                               long long top_ld, float *y, long long y_ld, srf_stream_t stream)
 {
-    if (N < 0 || H <= 0 || W <= 0 || Ht <= 0 || Wt <= 0 || top_ld < Cout) return SRF_EINVAL;
-    const int rc = gs_check(x, K, x_ld, W_packed, Cout, y_ld);
-    if (rc != SRF_OK) return rc;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y || !top) return SRF_EINVAL;
-    if ((long long)N * Ht * Wt * top_ld >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    const GsTop td = {top, top_ld, H, W, Ht, Wt};
+    const SrfGemmTop td = {top, top_ld, H, W, Ht, Wt};
+    const int rc = srf_gemm_check_1x1(GEMM_SPLIT, N, K, x_ld, x, W_packed, Cout, y, y_ld, &td);
+    if (rc != SRF_OK || N == 0) return rc;
     return gs_launch(x, (long long)N * H * W, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, &td);
 }
 
 // the pooled form: as srf_conv1x1_nhwc_pooled (conv.hip); workspace = srf_conv1x1_nhwc_pooled_workspace_bytes(N, HW, Cout)
-__global__ __launch_bounds__(256) void srf_gemm_split_pool_finish_k(const float *__restrict__ partial, int bpi, int C, float inv, float *__restrict__ mean)
-{
-    __shared__ float s[16][16];
-    const int n = blockIdx.y, cl = threadIdx.x & 15, c = blockIdx.x * 16 + cl, g = threadIdx.x >> 4;
-    float acc = 0.f;
-    if (c < C)
-        for (int b = g; b < bpi; b += 16) acc += partial[((long long)n * bpi + b) * C + c];
-    s[g][cl] = acc;
-    __syncthreads();
-    if (g == 0 && c < C) {
-        float t = s[0][cl];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) t += s[k][cl];
-        mean[(long long)n * C + c] = t * inv;
-    }
-}
-
 extern "C" int srf_conv1x1_nhwc_split_pooled(const float *x, int N, long long HW, int K, long long x_ld, const void *W_packed, int Cout,
                                              const float *scale, const float *shift, int relu, float *y, long long y_ld, float *mean,
                                              void *workspace, size_t workspace_bytes, srf_stream_t stream)
 {
-    if (N < 0 || HW <= 0) return SRF_EINVAL;
-    const int rc = gs_check(x, K, x_ld, W_packed, Cout, y_ld);
-    if (rc != SRF_OK) return rc;
-    if (N == 0) return SRF_OK;
-    if (!x || !W_packed || !y || !mean || !workspace) return SRF_EINVAL;
-    if (N > 65535) return SRF_EUNSUPPORTED;
-    if (workspace_bytes < (size_t)N * (size_t)srf_ceil_div(HW, 128) * Cout * 4) return SRF_EWORKSPACE;
+    const SrfGemmPool pool = {HW, mean, workspace, workspace_bytes};
+    int rc = srf_gemm_check_1x1(GEMM_SPLIT, N, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, &pool);
+    if (rc != SRF_OK || N == 0) return rc;
     int bpi = 0;
-    const int r2 = gs_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW,
-                             (hipStream_t)stream, &bpi);
-    if (r2 != SRF_OK) return r2;
-    hipLaunchKernelGGL(srf_gemm_split_pool_finish_k, dim3(srf_ceil_div(Cout, 16), N), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)workspace, bpi, Cout, 1.0f / (float)HW, mean);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
+    rc = gs_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW, (hipStream_t)stream,
+                   &bpi);
+    if (rc != SRF_OK) return rc;
+    return srf_gemm_pool_finish((const float *)workspace, bpi, N, Cout, HW, mean, (hipStream_t)stream);
 }

@@ -37,6 +37,10 @@ def _dev(t, name, dtype=None):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _opt(t, name):
+    return None if t is None else _ptr(_dev(t, name, torch.float32))
+
+
 def _empty(shape, dtype, device):
     return torch.empty(shape, dtype=dtype, device=device)
 
@@ -1096,10 +1100,8 @@ def channel_affine(x, scale, shift, relu, out=None, residual=None):
         residual = _dev(residual, "residual", torch.float32)
         if residual.shape != x.shape:
             raise ValueError("channel_affine: residual must match x")
-    check(_lib.lib().srf_channel_affine(_ptr(x), N, C, HW, C * HW, _ptr(_dev(scale, "scale", torch.float32)),
-                                        None if shift is None else _ptr(_dev(shift, "shift", torch.float32)), per_sample,
-                                        None if residual is None else _ptr(residual), int(bool(relu)), _ptr(out),
-                                        max(y_sn, C * HW), _stream()), "channel_affine")
+    check(_lib.lib().srf_channel_affine(_ptr(x), N, C, HW, C * HW, _ptr(_dev(scale, "scale", torch.float32)), _opt(shift, "shift"), per_sample,
+                                        _ptr(residual), int(bool(relu)), _ptr(out), max(y_sn, C * HW), _stream()), "channel_affine")
     return out
 
 
@@ -1127,7 +1129,6 @@ def conv1x1_supported(xs, Cout):
 
 def conv1x1(xs, packed_weight, Cout, scale=None, shift=None, relu=False):
     """1x1 convolution of cat(xs, dim=1) (never materialised) + per-channel scale/shift + ReLU -> (N, Cout, H, W)."""
-    import ctypes
     if not conv1x1_supported(xs, Cout):
         raise ValueError("conv1x1: unsupported shapes (see conv1x1_supported)")
     N, _, H, W = xs[0].shape
@@ -1137,10 +1138,8 @@ def conv1x1(xs, packed_weight, Cout, scale=None, shift=None, relu=False):
     K = sum(x.shape[1] for x in xs)
     if packed_weight.numel() != Cout * K:
         raise ValueError("conv1x1: packed weight does not match the sources")
-    check(_lib.lib().srf_conv1x1(ptrs, chans, len(xs), N, H * W, _ptr(packed_weight), Cout,
-                                 None if scale is None else _ptr(_dev(scale, "scale", torch.float32)),
-                                 None if shift is None else _ptr(_dev(shift, "shift", torch.float32)), int(bool(relu)),
-                                 _ptr(out), _stream()), "conv1x1")
+    check(_lib.lib().srf_conv1x1(ptrs, chans, len(xs), N, H * W, _ptr(packed_weight), Cout, _opt(scale, "scale"), _opt(shift, "shift"),
+                                 int(bool(relu)), _ptr(out), _stream()), "conv1x1")
     return out
 
 
@@ -1153,6 +1152,16 @@ def _dense_timing(key):
     ev0 = torch.cuda.Event(enable_timing=True)
     ev0.record()
     return ev0, t[key]
+
+
+def _dense_timed(records, start, label, flops, executed, nbytes):
+    """Closes a timed launch: records the end event and appends (start, end, label, FLOPs of the direct convolution, FLOPs the kernel
+    executes, bytes moved) to `records` (None: the event only); returns the end event."""
+    end = torch.cuda.Event(enable_timing=True)
+    end.record()
+    if records is not None:
+        records.append((start, end, label, flops, executed, nbytes))
+    return end
 
 
 def nhwc_ld(x):
@@ -1201,17 +1210,13 @@ def wino3x3(x, packed_weight, Cout, scale=None, shift=None, relu=False, out=None
     if packed_weight.numel() * 4 != L.srf_wino3x3_packed_weight_bytes(Cout, Cin):
         raise ValueError("wino3x3: packed weight does not match (Cout, Cin)")
     timing = _dense_timing("wino")
-    check(L.srf_wino3x3(_ptr(x), N, H, W, Cin, x_ld, _ptr(packed_weight), Cout,
-                        None if scale is None else _ptr(_dev(scale, "scale", torch.float32)),
-                        None if shift is None else _ptr(_dev(shift, "shift", torch.float32)), int(bool(relu)),
+    check(L.srf_wino3x3(_ptr(x), N, H, W, Cin, x_ld, _ptr(packed_weight), Cout, _opt(scale, "scale"), _opt(shift, "shift"), int(bool(relu)),
                         _ptr(out), y_ld, _stream()), "wino3x3")
     if timing is not None:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
         # direct-convolution FLOPs, FLOPs the Winograd kernel executes on the MFMA (16 of 36 products), bytes in + out + weights
         direct = 2.0 * 9 * Cin * Cout * N * H * W
-        timing[1].append((timing[0], ev1, f"{Cin}->{Cout} @{N}x{H}x{W}", direct, direct / 2.25,
-                          4.0 * N * H * W * (Cin + Cout) + 4.0 * 16 * Cin * Cout))
+        _dense_timed(timing[1], timing[0], f"{Cin}->{Cout} @{N}x{H}x{W}", direct, direct / 2.25,
+                     4.0 * N * H * W * (Cin + Cout) + 4.0 * 16 * Cin * Cout)
     return out
 
 
@@ -1268,7 +1273,7 @@ def wino43(x, packed_weight, Cout, scale=None, shift=None, relu=False, out=None)
     ws = _empty((ws_bytes // 4,), torch.float32, x.device)
     sc = None if scale is None else _aligned16(_dev(scale, "scale", torch.float32))
     sh = None if shift is None else _aligned16(_dev(shift, "shift", torch.float32))
-    scp, shp = None if sc is None else _ptr(sc), None if sh is None else _ptr(sh)
+    scp, shp = _ptr(sc), _ptr(sh)
     timing = _dense_timing("w43m")
     if timing is None:
         check(L.srf_wino43(_ptr(x), N, H, W, Cin, x_ld, _ptr(packed_weight), Cout, scp, shp, int(bool(relu)), _ptr(out), y_ld, _ptr(ws),
@@ -1280,63 +1285,80 @@ def wino43(x, packed_weight, Cout, scale=None, shift=None, relu=False, out=None)
         check(L.srf_wino43(_ptr(x), N, H, W, Cin, x_ld, _ptr(packed_weight), Cout, scp, shp, int(bool(relu)), _ptr(out), y_ld, _ptr(ws),
                            ws_bytes, _stream()), "wino43")
         return out
-    ev1 = torch.cuda.Event(enable_timing=True)
-    ev1.record()
-    check(L.srf_wino43_multiply(_ptr(ws), ws_bytes, N, H, W, Cin, _ptr(packed_weight), Cout, scp, shp, int(bool(relu)), _ptr(out), y_ld,
-                                _stream()), "wino43_multiply")
-    ev2 = torch.cuda.Event(enable_timing=True)
-    ev2.record()
     direct = 2.0 * 9 * Cin * Cout * N * H * W
     label = f"{Cin}->{Cout} @{N}x{H}x{W}"
     # transform: reads the input once, writes V (2.25x the input, padded to whole tile blocks)
-    xrec = KERNEL_TIMING.get("w43x")
-    if xrec is not None:
-        xrec.append((timing[0], ev1, label, 0.0, 0.0, 4.0 * N * H * W * Cin + ws_bytes))
+    ev1 = _dense_timed(KERNEL_TIMING.get("w43x"), timing[0], label, 0.0, 0.0, 4.0 * N * H * W * Cin + ws_bytes)
+    check(L.srf_wino43_multiply(_ptr(ws), ws_bytes, N, H, W, Cin, _ptr(packed_weight), Cout, scp, shp, int(bool(relu)), _ptr(out), y_ld,
+                                _stream()), "wino43_multiply")
     # multiply: executes direct / 4 FLOPs on the MFMA; reads V and U once, writes the output
-    timing[1].append((ev1, ev2, label, direct, direct / 4.0, float(ws_bytes) + 4.0 * 36 * Cin * Cout + 4.0 * N * H * W * Cout))
+    _dense_timed(timing[1], ev1, label, direct, direct / 4.0, float(ws_bytes) + 4.0 * 36 * Cin * Cout + 4.0 * N * H * W * Cout)
     return out
+
+
+# The three dense GEMM families behind conv1x1_nhwc / conv_gemm_nhwc (csrc/gemm_host.hpp): the C entry points of each by name, the
+# element of its packed weight, what the error messages call that weight and what the timing labels add.
+_GEMM_KINDS = {
+    "lds": dict(packed_bytes="srf_conv1x1_nhwc_packed_weight_bytes", pack="srf_conv1x1_nhwc_pack_weights", esize=4, dtype=torch.float32,
+                plain="srf_conv1x1_nhwc", topdown="srf_conv1x1_nhwc_topdown", pooled="srf_conv1x1_nhwc_pooled", conv="srf_conv_gemm_nhwc",
+                what="packed", tag=""),
+    "direct": dict(packed_bytes="srf_conv1x1_nhwc_direct_packed_weight_bytes", pack="srf_conv1x1_nhwc_direct_pack_weights", esize=4,
+                   dtype=torch.float32, plain="srf_conv1x1_nhwc_direct", topdown="srf_conv1x1_nhwc_direct_topdown",
+                   pooled="srf_conv1x1_nhwc_direct_pooled", conv=None, what="direct-packed", tag=" direct"),
+    "split": dict(packed_bytes="srf_conv1x1_nhwc_split_packed_weight_bytes", pack="srf_conv1x1_nhwc_split_pack_weights", esize=2,
+                  dtype=torch.int16, plain="srf_conv1x1_nhwc_split", topdown="srf_conv1x1_nhwc_split_topdown",
+                  pooled="srf_conv1x1_nhwc_split_pooled", conv="srf_conv_gemm_nhwc_split", what="split-packed", tag=" split"),
+}
+
+
+def _pack_gemm(kind, weight):
+    k = _GEMM_KINDS[kind]
+    weight = _dev(weight.reshape(weight.shape[0], -1), "weight", torch.float32)
+    Cout, K = weight.shape
+    L = _lib.lib()
+    nbytes = getattr(L, k["packed_bytes"])(Cout, K)
+    if nbytes == 0:
+        raise ValueError("conv1x1_nhwc: K must be a multiple of 32")
+    if kind == "split" and not gemm_split_weight_in_domain(weight):
+        return None     # callers keep such a layer on the f32-MFMA kernels
+    packed = _empty((nbytes // k["esize"],), k["dtype"], weight.device)
+    check(getattr(L, k["pack"])(_ptr(weight), Cout, K, _ptr(packed), _stream()), k["pack"][len("srf_"):])
+    return packed
+
+
+def _choose_gemm(op, layer, M, Cout, K, packed_weight, packed_direct=None, packed_split=None):
+    """The family a launch of M rows runs on and its packed weight -> (kind, row of _GEMM_KINDS, tensor).  Callables are called only for
+    the family that is taken (the split one also when it is merely wanted: it may answer None)."""
+    kind, packed = "lds", packed_weight
+    if packed_split is not None and gemm_split_wanted(M, Cout):
+        if callable(packed_split):
+            packed_split = packed_split()
+        if packed_split is not None:     # None: a weight outside the split's exact domain (gemm_split_weight_in_domain)
+            kind, packed = "split", packed_split
+    if kind == "lds" and packed_direct is not None and conv1x1_direct_wanted(M, Cout):
+        kind, packed = "direct", packed_direct
+    k = _GEMM_KINDS[kind]
+    if callable(packed):
+        packed = packed()
+    if packed.numel() * k["esize"] != getattr(_lib.lib(), k["packed_bytes"])(Cout, K):
+        raise ValueError(f"{op}: {k['what']} weight does not match {layer}")
+    return kind, k, packed
 
 
 def pack_conv1x1_nhwc_weights(weight):
     """(Cout, K) or (Cout, K, 1, 1) -> the LDS operand order srf_conv1x1_nhwc copies (once per layer)."""
-    weight = _dev(weight.reshape(weight.shape[0], -1), "weight", torch.float32)
-    Cout, K = weight.shape
-    L = _lib.lib()
-    nbytes = L.srf_conv1x1_nhwc_packed_weight_bytes(Cout, K)
-    if nbytes == 0:
-        raise ValueError("conv1x1_nhwc: K must be a multiple of 32")
-    packed = _empty((nbytes // 4,), torch.float32, weight.device)
-    check(L.srf_conv1x1_nhwc_pack_weights(_ptr(weight), Cout, K, _ptr(packed), _stream()), "conv1x1_nhwc_pack_weights")
-    return packed
+    return _pack_gemm("lds", weight)
 
 
 def pack_conv1x1_nhwc_direct_weights(weight):
     """(Cout, K) or (Cout, K, 1, 1) -> the operand order srf_conv1x1_nhwc_direct streams from L2 (once per layer)."""
-    weight = _dev(weight.reshape(weight.shape[0], -1), "weight", torch.float32)
-    Cout, K = weight.shape
-    L = _lib.lib()
-    nbytes = L.srf_conv1x1_nhwc_direct_packed_weight_bytes(Cout, K)
-    if nbytes == 0:
-        raise ValueError("conv1x1_nhwc: K must be a multiple of 32")
-    packed = _empty((nbytes // 4,), torch.float32, weight.device)
-    check(L.srf_conv1x1_nhwc_direct_pack_weights(_ptr(weight), Cout, K, _ptr(packed), _stream()), "conv1x1_nhwc_direct_pack_weights")
-    return packed
+    return _pack_gemm("direct", weight)
 
 
 def pack_conv1x1_nhwc_split_weights(weight):
     """(Cout, K) or (Cout, K, 1, 1) -> the three bf16 planes of the weight (w = wh + wm + wl exactly) in the LDS operand order
     srf_conv1x1_nhwc_split copies (once per layer); an int16 tensor (6 bytes per weight)."""
-    weight = _dev(weight.reshape(weight.shape[0], -1), "weight", torch.float32)
-    Cout, K = weight.shape
-    L = _lib.lib()
-    nbytes = L.srf_conv1x1_nhwc_split_packed_weight_bytes(Cout, K)
-    if nbytes == 0:
-        raise ValueError("conv1x1_nhwc: K must be a multiple of 32")
-    if not gemm_split_weight_in_domain(weight):
-        return None     # callers keep such a layer on the f32-MFMA kernels
-    packed = _empty((nbytes // 2,), torch.int16, weight.device)
-    check(L.srf_conv1x1_nhwc_split_pack_weights(_ptr(weight), Cout, K, _ptr(packed), _stream()), "conv1x1_nhwc_split_pack_weights")
-    return packed
+    return _pack_gemm("split", weight)
 
 
 GEMM_SPLIT_MAX = float.fromhex("0x1.FEp127")   # the largest bf16 (3.3895e38): above it the first plane rounds to infinity
@@ -1357,7 +1379,6 @@ def gemm_split_enabled():
     """SRF_GEMM_SPLIT=0 keeps the 1x1 convolutions on the f32-MFMA kernels (`srf_conv1x1_nhwc` / `_direct`: one k-ordered fma chain per
     output); the default runs them on `srf_conv1x1_nhwc_split` -- the same f32 GEMM through an exact three-way bf16 split of both
     operands on the bf16 MFMA (csrc/gemm_split.hip: error against float64 equal to the f32 chain's, 1.4-1.5x its rate)."""
-    import os
     return os.environ.get("SRF_GEMM_SPLIT", "1") != "0"
 
 
@@ -1369,7 +1390,6 @@ def gemm_split_wanted(M, Cout):
     FPN's laterals and stride-2 extras, the coarse image laterals) fills the chip better on the 64 x 64 tiles of the f32-MFMA kernels:
     nusc_L, whose GEMMs are all of that size, ran 1.5-2 % slower with everything on the split kernel (same box, alternating runs:
     229.7 / 233.7 against 234.8 / 237.1 frames/s).  SRF_GEMM_SPLIT_MIN overrides the threshold (A/B switch)."""
-    import os
     if not gemm_split_enabled():
         return False
     thr = int(os.environ.get("SRF_GEMM_SPLIT_MIN", GEMM_SPLIT_MIN_TILES))
@@ -1383,7 +1403,6 @@ def conv1x1_direct_wanted(M, Cout):
     """The LDS-free GEMM (`srf_conv1x1_nhwc_direct`) pays on launches of more than a round of 128 x 128 tiles at three workgroups
     per CU (VoVNet stages 2-4: 122-135 against 110-117 TFLOP/s); below that the 64 x 64 tiles of `srf_conv1x1_nhwc` fill the chip
     better (stage 5: 104 against 93).  SRF_GEMM_DIRECT=0 / 1 forces the choice (A/B switch for tests and benchmarks)."""
-    import os
     force = os.environ.get("SRF_GEMM_DIRECT")
     if force is not None:
         return force != "0"
@@ -1408,59 +1427,32 @@ def conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, out
         raise ValueError("conv1x1_nhwc: out has the wrong shape")
     y_ld = nhwc_ld(out)
     L = _lib.lib()
-    split = packed_split is not None and gemm_split_wanted(N * H * W, Cout) and max(x_ld, y_ld) * 512 < (1 << 31)
-    if split and callable(packed_split):
-        packed_split = packed_split()
-        split = packed_split is not None     # None: a weight outside the split's exact domain (gemm_split_weight_in_domain)
-    direct = not split and packed_direct is not None and conv1x1_direct_wanted(N * H * W, Cout) and max(x_ld, y_ld) * 512 < (1 << 31)
-    if split:
-        if packed_split.numel() * 2 != L.srf_conv1x1_nhwc_split_packed_weight_bytes(Cout, K):
-            raise ValueError("conv1x1_nhwc: split-packed weight does not match (Cout, K)")
-        wp = _ptr(packed_split)
-    elif direct:
-        if callable(packed_direct):
-            packed_direct = packed_direct()
-        if packed_direct.numel() * 4 != L.srf_conv1x1_nhwc_direct_packed_weight_bytes(Cout, K):
-            raise ValueError("conv1x1_nhwc: direct-packed weight does not match (Cout, K)")
-        wp = _ptr(packed_direct)
-    else:
-        if callable(packed_weight):
-            packed_weight = packed_weight()
-        if packed_weight.numel() * 4 != L.srf_conv1x1_nhwc_packed_weight_bytes(Cout, K):
-            raise ValueError("conv1x1_nhwc: packed weight does not match (Cout, K)")
-        wp = _ptr(packed_weight)
+    if max(x_ld, y_ld) * 512 >= (1 << 31):     # beyond the 128-row descriptors of the direct and the split family
+        packed_direct = packed_split = None
+    kind, k, packed = _choose_gemm("conv1x1_nhwc", "(Cout, K)", N * H * W, Cout, K, packed_weight, packed_direct, packed_split)
+    split, wp = kind == "split", _ptr(packed)
     timing = _dense_timing("gsplit" if split else "gemm")
-    sc = None if scale is None else _ptr(_dev(scale, "scale", torch.float32))
-    sh = None if shift is None else _ptr(_dev(shift, "shift", torch.float32))
+    sc, sh = _opt(scale, "scale"), _opt(shift, "shift")
     mean = None
     if top is not None:
         if pool or top.dim() != 4 or top.shape[0] != N or top.shape[3] != Cout:
             raise ValueError("conv1x1_nhwc: top must be (N, Ht, Wt, Cout) and excludes pool")
-        fn = L.srf_conv1x1_nhwc_split_topdown if split else (L.srf_conv1x1_nhwc_direct_topdown if direct else L.srf_conv1x1_nhwc_topdown)
-        check(fn(_ptr(x), N, H, W, K, x_ld, wp, Cout, sc, sh, int(bool(relu)), _ptr(top), top.shape[1], top.shape[2], nhwc_ld(top), _ptr(out),
-                 y_ld, _stream()), "conv1x1_nhwc_topdown")
+        check(getattr(L, k["topdown"])(_ptr(x), N, H, W, K, x_ld, wp, Cout, sc, sh, int(bool(relu)), _ptr(top), top.shape[1], top.shape[2],
+                                    nhwc_ld(top), _ptr(out), y_ld, _stream()), "conv1x1_nhwc_topdown")
     elif pool:
         mean = _empty((N, Cout), torch.float32, x.device)
         nbytes = L.srf_conv1x1_nhwc_pooled_workspace_bytes(N, H * W, Cout)
         ws = _empty((max(nbytes, 4) // 4,), torch.float32, x.device)
-        fn = L.srf_conv1x1_nhwc_split_pooled if split else (L.srf_conv1x1_nhwc_direct_pooled if direct else L.srf_conv1x1_nhwc_pooled)
-        check(fn(_ptr(x), N, H * W, K, x_ld, wp, Cout, sc, sh, int(bool(relu)), _ptr(out), y_ld, _ptr(mean), _ptr(ws), nbytes, _stream()),
-              "conv1x1_nhwc_pooled")
+        check(getattr(L, k["pooled"])(_ptr(x), N, H * W, K, x_ld, wp, Cout, sc, sh, int(bool(relu)), _ptr(out), y_ld, _ptr(mean), _ptr(ws), nbytes,
+                                   _stream()), "conv1x1_nhwc_pooled")
     else:
-        fn = L.srf_conv1x1_nhwc_split if split else (L.srf_conv1x1_nhwc_direct if direct else L.srf_conv1x1_nhwc)
-        check(fn(_ptr(x), N * H * W, K, x_ld, wp, Cout, sc, sh, int(bool(relu)), _ptr(out), y_ld, _stream()), "conv1x1_nhwc")
+        check(getattr(L, k["plain"])(_ptr(x), N * H * W, K, x_ld, wp, Cout, sc, sh, int(bool(relu)), _ptr(out), y_ld, _stream()), "conv1x1_nhwc")
     if timing is not None:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
         fl = 2.0 * K * Cout * N * H * W
         # split: six bf16 products per f32 product are issued on the bf16 MFMA; the weights are 6 bytes each
-        timing[1].append((timing[0], ev1, f"{K}->{Cout} @{N}x{H}x{W}" + (" split" if split else (" direct" if direct else "")), fl,
-                          6.0 * fl if split else fl, 4.0 * N * H * W * (K + Cout) + (6.0 if split else 4.0) * K * Cout))
+        _dense_timed(timing[1], timing[0], f"{K}->{Cout} @{N}x{H}x{W}" + k["tag"], fl, 6.0 * fl if split else fl,
+                     4.0 * N * H * W * (K + Cout) + (6.0 if split else 4.0) * K * Cout)
     return (out, mean) if pool else out
-
-
-def _opt(t, name):
-    return None if t is None else _ptr(_dev(t, name, torch.float32))
 
 
 def nhwc_affine(x, scale=None, shift=None, relu=False, residual=None, out=None):
@@ -1475,7 +1467,7 @@ def nhwc_affine(x, scale=None, shift=None, relu=False, residual=None, out=None):
     if shift is not None and shift.numel() != (N * C if per_sample & 2 else C):
         raise ValueError("nhwc_affine: shift has the wrong size")
     check(_lib.lib().srf_nhwc_affine(_ptr(x), x_ld, N, H * W, C, _opt(scale, "scale"), per_sample, _opt(shift, "shift"),
-                                     None if residual is None else _ptr(residual),
+                                     _ptr(residual),
                                      0 if residual is None else nhwc_ld(residual), int(bool(relu)), _ptr(out), nhwc_ld(out),
                                      _stream()), "nhwc_affine")
     return out
@@ -1653,21 +1645,9 @@ def conv_gemm_nhwc(x, packed_weight, Cout, ksize, stride, pad, scale=None, shift
         out = _empty((N, Ho, Wo, Cout), torch.float32, x.device)
     elif tuple(out.shape) != (N, Ho, Wo, Cout):
         raise ValueError("conv_gemm_nhwc: out has the wrong shape")
-    L = _lib.lib()
-    split = packed_split is not None and gemm_split_wanted(N * Ho * Wo, Cout)
-    if split and callable(packed_split):
-        packed_split = packed_split()
-        split = packed_split is not None     # None: a weight outside the split's exact domain stays on the f32 MFMA
-    if split:
-        if packed_split.numel() * 2 != L.srf_conv1x1_nhwc_split_packed_weight_bytes(Cout, kh * kw * Cin):
-            raise ValueError("conv_gemm_nhwc: split-packed weight does not match the layer")
-        packed_weight, fn = packed_split, L.srf_conv_gemm_nhwc_split
-    else:
-        if callable(packed_weight):
-            packed_weight = packed_weight()
-        if packed_weight.numel() * 4 != L.srf_conv1x1_nhwc_packed_weight_bytes(Cout, kh * kw * Cin):
-            raise ValueError("conv_gemm_nhwc: packed weight does not match the layer")
-        fn = L.srf_conv_gemm_nhwc
+    kind, k, packed_weight = _choose_gemm("conv_gemm_nhwc", "the layer", N * Ho * Wo, Cout, kh * kw * Cin, packed_weight,
+                                          packed_split=packed_split)
+    split, fn = kind == "split", getattr(_lib.lib(), k["conv"])
     # the kernel addresses its whole input through ONE 32-bit buffer descriptor (N H W x_ld 4 < 2^31 bytes): larger batches
     # run in groups of images (VoVNet stem_3 reads 464 x 800 x 64 per camera: 23 images reach the limit -- LC inference at
     # batch 4, the frozen prefix of config 4 at bs >= 4)
@@ -1680,11 +1660,9 @@ def conv_gemm_nhwc(x, packed_weight, Cout, ksize, stride, pad, scale=None, shift
         check(fn(_ptr(xs), xs.shape[0], H, W, Cin, x_ld, _ptr(packed_weight), Cout, kh, kw, stride, pad, sc, sh,
                  int(bool(relu)), _ptr(os_), nhwc_ld(out), _stream()), "conv_gemm_nhwc")
     if timing is not None:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
         fl = 2.0 * kh * kw * Cin * Cout * N * Ho * Wo
-        timing[1].append((timing[0], ev1, f"{Cin}->{Cout} {kh}x{kw}/s{stride} @{N}x{H}x{W}" + (" split" if split else ""), fl,
-                          6.0 * fl if split else fl, 4.0 * N * (H * W * Cin + Ho * Wo * Cout) + (6.0 if split else 4.0) * kh * kw * Cin * Cout))
+        _dense_timed(timing[1], timing[0], f"{Cin}->{Cout} {kh}x{kw}/s{stride} @{N}x{H}x{W}" + k["tag"], fl, 6.0 * fl if split else fl,
+                     4.0 * N * (H * W * Cin + Ho * Wo * Cout) + (6.0 if split else 4.0) * kh * kw * Cin * Cout)
     return out
 
 
@@ -1825,7 +1803,6 @@ def stem_conv_nchw(x, weight, scale=None, shift=None, relu=False, out=None):
 
 
 def _ptr_array(tensors):
-    import ctypes
     arr = (ctypes.c_void_p * max(len(tensors), 1))()
     for i, t in enumerate(tensors):
         arr[i] = t.data_ptr()
