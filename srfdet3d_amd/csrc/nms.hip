@@ -202,7 +202,8 @@ static int srf_nms_launch(const float *boxes, const long long *cls, int n, const
 //                    BEV boxes for the NMS `bev` (L, 5) = [x, y, w, l, yaw] (srf_nms_rotated_classes with `cls` is the
 //                    per-class NMS of the reference in ONE pass, on the boxes' own coordinates), and *m = number of pairs
 //                    above the threshold (may exceed L: the caller then falls back).
-//                    Rows >= min(*m, L) hold score -1 and an arbitrary valid box.
+//                    Rows >= min(*m, L) hold score -1 and the (box, class) pairs at or below the threshold (NaN scores
+//                    among them) in ascending flat index, on both sort paths: no row repeats a pair.
 //   srf_nms_finish:  survivors (keep != 0) first, class-major, descending score inside a class (the order of the
 //                    reference's per-class loop), stable; *kept = their number.
 // =====================================================================================================================

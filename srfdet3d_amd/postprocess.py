@@ -28,10 +28,10 @@ def box3d_multiclass_nms(boxes, scores, score_thr, max_num, nms_thr):
     s = scores[bi, ci]
     bev = boxes[bi][:, [0, 1, 3, 4, 6]].contiguous()
     keep = ops.nms_rotated(bev, s, nms_thr, classes=ci)  # suppression inside a class only: the reference's per-class loop
-    keep = keep.sort()[0]  # back to class-major / in-class score order is not needed before the top-k below
-    # the reference appends, per class, boxes in descending score order
-    k2 = torch.argsort(ci[keep] * 4 - s[keep].clamp(0, 1) * 2, stable=True)
-    keep = keep[k2]
+    # the reference appends, per class, boxes in descending score order.  The keeps arrive in descending score (equal scores:
+    # lower box first), so a STABLE sort by class alone is that order.  (A float32 key 4 * class - 2 * score is coarser than the
+    # scores from class 1 on: two survivors of class 9 one ulp apart shared a key and came out in box order.)
+    keep = keep[torch.argsort(ci[keep], stable=True)]
     out_b, out_s, out_l = boxes[bi[keep]], s[keep], ci[keep]
     if out_b.shape[0] > max_num:
         top = out_s.sort(descending=True)[1][:max_num]
