@@ -576,6 +576,30 @@ int srf_conv1x1_nhwc_split_pooled(const float *x, int N, long long HW, int K, lo
 int srf_conv_gemm_nhwc_split(const float *x, int N, int H, int W, int Cin, long long x_ld, const void *W_packed, int Cout, int kh, int kw,
                              int stride, int pad, const float *scale, const float *shift, int relu, float *y, long long y_ld,
                              srf_stream_t stream);
+/* srf_conv1x1_nhwc_bf16* / srf_conv_gemm_nhwc_bf16: the same four operations with ONE bf16 product per f32 product
+ * (csrc/gemm_bf16.hip) -- the opt-in reduced-precision mode of the image branch, never taken by default.  Tensors stay f32.  Each
+ * activation and each weight is rounded to bf16 once (round to nearest even, as v_cvt_pk_bf16_f32 and torch.Tensor.bfloat16()), the
+ * products (exact in f32) are accumulated in f32 on v_mfma_f32_32x32x16_bf16, and the epilogue of the split forms (scale / shift /
+ * ReLU, the top-down add, the column means of the stored outputs) is applied to the f32 accumulator: y = epilogue(sum bf16(x) bf16(w))
+ * up to f32 accumulation error (<= 6e-7 of sum |a b|), <= (2^-7 + 2^-16 + 6e-7) sum |a b| from the unrounded product.  Deterministic.
+ * +-inf / NaN and values that round to infinity (|v| > 0x1.FEp127) give what IEEE arithmetic gives on the rounded operands; operands
+ * whose rounding is a bf16 subnormal may be flushed: an absolute error of at most 2^-126 |partner| per such term.  W_packed (one bf16
+ * plane in the kernel's image order, K padded to a multiple of 64: 2 bytes per weight) comes from srf_conv1x1_nhwc_bf16_pack_weights;
+ * for the conv form of the weight reordered to (Cout, kh * kw * Cin), tap index slowest.  Same arguments, limits and error codes as
+ * the _split forms; workspace of the pooled form: srf_conv1x1_nhwc_pooled_workspace_bytes. */
+size_t srf_conv1x1_nhwc_bf16_packed_weight_bytes(int Cout, int K);
+int srf_conv1x1_nhwc_bf16_pack_weights(const float *W, int Cout, int K, void *packed, srf_stream_t stream);
+int srf_conv1x1_nhwc_bf16(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale,
+                          const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream);
+int srf_conv1x1_nhwc_bf16_topdown(const float *x, int N, int H, int W, int K, long long x_ld, const void *W_packed, int Cout,
+                                  const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt, long long top_ld,
+                                  float *y, long long y_ld, srf_stream_t stream);
+int srf_conv1x1_nhwc_bf16_pooled(const float *x, int N, long long HW, int K, long long x_ld, const void *W_packed, int Cout,
+                                 const float *scale, const float *shift, int relu, float *y, long long y_ld, float *mean,
+                                 void *workspace, size_t workspace_bytes, srf_stream_t stream);
+int srf_conv_gemm_nhwc_bf16(const float *x, int N, int H, int W, int Cin, long long x_ld, const void *W_packed, int Cout, int kh, int kw,
+                            int stride, int pad, const float *scale, const float *shift, int relu, float *y, long long y_ld,
+                            srf_stream_t stream);
 
 
 

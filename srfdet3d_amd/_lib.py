@@ -132,6 +132,15 @@ SIGNATURES = {
                                          c_longlong, _P]),
     "srf_conv1x1_nhwc_split_pooled": (c_int, [_P, c_int, c_longlong, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_longlong, _P, _P,
                                               c_size_t, _P]),
+    "srf_conv1x1_nhwc_bf16_packed_weight_bytes": (c_size_t, [c_int, c_int]),
+    "srf_conv1x1_nhwc_bf16_pack_weights": (c_int, [_P, c_int, c_int, _P, _P]),
+    "srf_conv1x1_nhwc_bf16": (c_int, [_P, c_longlong, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_longlong, _P]),
+    "srf_conv1x1_nhwc_bf16_topdown": (c_int, [_P, c_int, c_int, c_int, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_longlong,
+                                              _P, c_longlong, _P]),
+    "srf_conv_gemm_nhwc_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, c_longlong, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P,
+                                        c_longlong, _P]),
+    "srf_conv1x1_nhwc_bf16_pooled": (c_int, [_P, c_int, c_longlong, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_longlong, _P, _P,
+                                             c_size_t, _P]),
     "srf_conv1x1_nhwc_topdown": (c_int, [_P, c_int, c_int, c_int, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_longlong,
                                          _P, c_longlong, _P]),
     "srf_conv1x1_nhwc_pooled_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int]),

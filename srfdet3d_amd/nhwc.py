@@ -13,6 +13,9 @@ The torch modules stay the owners of the parameters (state_dict names untouched)
 * the stride-2 stem layers: stem_1 (3 -> 64) is a streaming kernel from the NCHW images to channels-last
   (`srf_stem_conv_nchw`), stem_3 an implicit-im2col GEMM (`srf_conv_gemm_nhwc`); nothing of the branch runs on MIOpen.
 
+Opt-in, off by default: inside `mfma_dtype(torch.bfloat16)` (`SRFDet.img_mfma_dtype`) the GEMM-shaped layers of VoVNet and the FPN run
+on the bf16-product kernels of csrc/gemm_bf16.hip instead (f32 tensors, operands rounded to bf16 once, f32 accumulation and epilogue).
+
 Tensors handed to the rest of the model are logical NCHW views with channels_last strides, so every consumer that only
 looks at shapes keeps working and the RoI gather finds its channels-last operand without a copy.
 
@@ -55,7 +58,8 @@ def _cached(mod, key, vers, make):
     return cache[1]
 
 
-_CACHE_KEYS = ("_srf_wino", "_srf_wino43", "_srf_gemm", "_srf_gemm_direct", "_srf_gemm_split", "_srf_cgemm", "_srf_cgemm_split", "_srf_packed")
+_CACHE_KEYS = ("_srf_wino", "_srf_wino43", "_srf_gemm", "_srf_gemm_direct", "_srf_gemm_split", "_srf_cgemm", "_srf_cgemm_split", "_srf_packed",
+               "_srf_gemm_bf16", "_srf_cgemm_bf16")
 
 
 def invalidate_caches(model):
@@ -67,6 +71,84 @@ def invalidate_caches(model):
         for k in _CACHE_KEYS:
             if hasattr(m, k):
                 delattr(m, k)
+
+
+# ---- the bf16-product mode of the image branch (csrc/gemm_bf16.hip) ------------------------------------------------------------
+_MFMA = None     # the innermost active `mfma_dtype` context, or None: every layer on its f32 route
+
+
+class mfma_dtype:
+    """Within `with nhwc.mfma_dtype(torch.bfloat16):` the layers executed by `conv3x3`, `conv1x1` (plain, pool=, top=) and
+    `conv_strided` -- so `vovnet_forward` and `fpn_forward` -- run on the bf16-product kernels: f32 tensors, both operands rounded to
+    bf16 once, exact products, f32 accumulation and epilogue (`srf_conv1x1_nhwc_bf16*`; `srf_conv_gemm_nhwc_bf16` for every 3x3 layer,
+    stride 1 included -- no Winograd in this mode: products of bf16-rounded transformed data are another, worse arithmetic).  Off by
+    default; `mfma_dtype(None)` inside an active context switches it off again (the head's `img_convs` inside the neck's chains).
+
+    A layer the family cannot take keeps its f32 route: input channels that are no multiple of 32 (VoVNet stem_1 with 3 input
+    channels, which `srf_stem_conv_nchw` runs anyway), an operand that is not 16-byte aligned or whose pitch is no multiple of 4,
+    tensors beyond the family's 32-bit ranges (one 128-row tile of x or y, one image of a conv layer's input, from 2^31 bytes).
+
+    routes: a list that receives one dict(layer=, route="bf16" | "f32", why=) per executed layer -- the per-layer report, as
+    bench.py's config.gemm_route is for the split rule.  `launches` counts the layers that ran on the bf16 kernels.  The switch is
+    process-wide while the context is open (the executor is single-threaded); it is not an environment variable and nothing outside
+    the context sees it."""
+
+    def __init__(self, dtype, routes=None):
+        if dtype is not None and dtype != torch.bfloat16:
+            raise ValueError(f"nhwc.mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
+        self.dtype, self.routes, self.launches = dtype, routes, 0
+
+    def __enter__(self):
+        global _MFMA
+        self._outer, _MFMA = _MFMA, (self if self.dtype is not None else None)
+        return self
+
+    def __exit__(self, *exc):
+        global _MFMA
+        _MFMA = self._outer
+        return False
+
+
+def mfma_active():
+    return _MFMA is not None
+
+
+def _bf16_route(x, conv, out, form):
+    """True when the active mode takes this layer; records the route.  form: "1x1" or "conv"."""
+    m = _MFMA
+    if m is None:
+        return False
+    why = None
+    try:
+        x_ld = ops.nhwc_ld(x)
+        y_ld = ops.nhwc_ld(out) if out is not None else conv.out_channels
+    except RuntimeError:
+        x_ld = y_ld = 0
+        why = "not a channel slice of a pixel-major buffer"
+    N, H, W, cin = x.shape
+    if why is None:
+        if cin % 32:
+            why = "input channels are no multiple of 32"
+        elif x_ld % 4 or x.data_ptr() % 16:
+            why = "operand alignment"
+        elif max(x_ld, y_ld) * 512 >= (1 << 31) or (form == "conv" and 4 * H * W * x_ld >= (1 << 31)):
+            why = "beyond the 32-bit ranges"
+    if m.routes is not None:
+        k, st = conv.kernel_size[0], conv.stride[0]
+        m.routes.append(dict(layer=f"{cin}->{conv.out_channels} {k}x{k}/s{st} @{N}x{H}x{W}", route="f32" if why else "bf16", why=why))
+    if why is None:
+        m.launches += 1
+    return why is None
+
+
+def _gemm_bf16_weights(conv):
+    w = conv.weight
+    return _cached(conv, "_srf_gemm_bf16", (w._version, w.data_ptr()), lambda: ops.pack_conv1x1_nhwc_bf16_weights(w.detach()))
+
+
+def _conv_bf16_weights(conv):
+    w = conv.weight
+    return _cached(conv, "_srf_cgemm_bf16", (w._version, w.data_ptr()), lambda: ops.pack_conv_gemm_bf16_weights(w))
 
 
 def _wino_weights(conv):
@@ -114,6 +196,9 @@ def use_wino43(x, cout, out=None):
 def conv3x3(x, conv, bn=None, relu=False, out=None):
     """x: NHWC slice; conv: nn.Conv2d 3x3 / stride 1 / padding 1."""
     scale, shift = _affine_of(conv, bn)
+    if _bf16_route(x, conv, out, "conv"):
+        return ops.conv_gemm_nhwc(x, None, conv.out_channels, (3, 3), 1, 1, scale, shift, relu, out=out,
+                                  packed_bf16=lambda: _conv_bf16_weights(conv))
     if use_wino43(x, conv.out_channels, out):
         return ops.wino43(x, _wino43_weights(conv), conv.out_channels, scale, shift, relu, out=out)
     return ops.wino3x3(x, _wino_weights(conv), conv.out_channels, scale, shift, relu, out=out)
@@ -133,7 +218,8 @@ def conv1x1(x, conv, bn=None, relu=False, out=None, pool=False, top=None):
     scale, shift = _affine_of(conv, bn)
     # the operand orders are packed lazily: a layer only ever packs the one its launch selects
     return ops.conv1x1_nhwc(x, lambda: _gemm_weights(conv), conv.out_channels, scale, shift, relu, out=out, pool=pool, top=top,
-                            packed_direct=lambda: _gemm_direct_weights(conv), packed_split=lambda: _gemm_split_weights(conv))
+                            packed_direct=lambda: _gemm_direct_weights(conv), packed_split=lambda: _gemm_split_weights(conv),
+                            packed_bf16=(lambda: _gemm_bf16_weights(conv)) if _bf16_route(x, conv, out, "1x1") else None)
 
 
 def wino_ok(conv, cin):
@@ -310,7 +396,8 @@ def conv_strided(x, conv, bn=None, relu=False, out=None):
     (`srf_conv_gemm_nhwc`): deterministic, where MIOpen's channels-last choice is an atomic split-K kernel."""
     scale, shift = _affine_of(conv, bn)
     return ops.conv_gemm_nhwc(x, lambda: _strided_weights(conv), conv.out_channels, conv.kernel_size, conv.stride[0], conv.padding[0],
-                              scale, shift, relu, out=out, packed_split=lambda: _strided_split_weights(conv))
+                              scale, shift, relu, out=out, packed_split=lambda: _strided_split_weights(conv),
+                              packed_bf16=(lambda: _conv_bf16_weights(conv)) if _bf16_route(x, conv, out, "conv") else None)
 
 
 def to_nhwc(x):
@@ -447,7 +534,10 @@ def fpn_forward(fpn, inputs):
 
     def chain(i):
         o = _cm(convs[i], lats[i], conv3x3)
-        return consumer(i, o) if consumer is not None else o
+        if consumer is None:
+            return o
+        with mfma_dtype(None):     # the consumer is not part of the neck: the head's `img_convs` stay f32 in the bf16 mode
+            return consumer(i, o)
 
     lats = [None] * n
     outs = [None] * n

@@ -1308,6 +1308,9 @@ _GEMM_KINDS = {
     "split": dict(packed_bytes="srf_conv1x1_nhwc_split_packed_weight_bytes", pack="srf_conv1x1_nhwc_split_pack_weights", esize=2,
                   dtype=torch.int16, plain="srf_conv1x1_nhwc_split", topdown="srf_conv1x1_nhwc_split_topdown",
                   pooled="srf_conv1x1_nhwc_split_pooled", conv="srf_conv_gemm_nhwc_split", what="split-packed", tag=" split"),
+    "bf16": dict(packed_bytes="srf_conv1x1_nhwc_bf16_packed_weight_bytes", pack="srf_conv1x1_nhwc_bf16_pack_weights", esize=2,
+                 dtype=torch.int16, plain="srf_conv1x1_nhwc_bf16", topdown="srf_conv1x1_nhwc_bf16_topdown",
+                 pooled="srf_conv1x1_nhwc_bf16_pooled", conv="srf_conv_gemm_nhwc_bf16", what="bf16-packed", tag=" bf16"),
 }
 
 
@@ -1326,11 +1329,14 @@ def _pack_gemm(kind, weight):
     return packed
 
 
-def _choose_gemm(op, layer, M, Cout, K, packed_weight, packed_direct=None, packed_split=None):
+def _choose_gemm(op, layer, M, Cout, K, packed_weight, packed_direct=None, packed_split=None, packed_bf16=None):
     """The family a launch of M rows runs on and its packed weight -> (kind, row of _GEMM_KINDS, tensor).  Callables are called only for
-    the family that is taken (the split one also when it is merely wanted: it may answer None)."""
+    the family that is taken (the split one also when it is merely wanted: it may answer None).  packed_bf16 is the caller's explicit
+    choice of the reduced-precision family (csrc/gemm_bf16.hip) and precedes the rules of the f32-accurate ones."""
     kind, packed = "lds", packed_weight
-    if packed_split is not None and gemm_split_wanted(M, Cout):
+    if packed_bf16 is not None:
+        kind, packed = "bf16", packed_bf16
+    elif packed_split is not None and gemm_split_wanted(M, Cout):
         if callable(packed_split):
             packed_split = packed_split()
         if packed_split is not None:     # None: a weight outside the split's exact domain (gemm_split_weight_in_domain)
@@ -1353,6 +1359,12 @@ def pack_conv1x1_nhwc_weights(weight):
 def pack_conv1x1_nhwc_direct_weights(weight):
     """(Cout, K) or (Cout, K, 1, 1) -> the operand order srf_conv1x1_nhwc_direct streams from L2 (once per layer)."""
     return _pack_gemm("direct", weight)
+
+
+def pack_conv1x1_nhwc_bf16_weights(weight):
+    """(Cout, K) or (Cout, K, 1, 1) -> the weight rounded to bf16 (round to nearest even) in the LDS operand order srf_conv1x1_nhwc_bf16
+    copies (once per layer); an int16 tensor (2 bytes per weight, K padded to a multiple of 64)."""
+    return _pack_gemm("bf16", weight)
 
 
 def pack_conv1x1_nhwc_split_weights(weight):
@@ -1410,7 +1422,7 @@ def conv1x1_direct_wanted(M, Cout):
 
 
 def conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, out=None, pool=False, top=None, packed_direct=None,
-                 packed_split=None):
+                 packed_split=None, packed_bf16=None):
     """1x1 convolution of the NHWC slice x (N, H, W, K) + per-channel scale / shift + ReLU into `out` ((N, H, W, Cout) slice
     of an NHWC buffer; new contiguous tensor when None).  pool=True: returns (out, mean (N, Cout) over the pixels of each
     image) from the same pass (`srf_conv1x1_nhwc_pooled`).  top: an (N, Ht, Wt, Cout) NHWC slice whose nearest-neighbour
@@ -1418,7 +1430,10 @@ def conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, out
     packed_direct: the same weight packed by `pack_conv1x1_nhwc_direct_weights`, or a callable returning it; large launches then
     run on the LDS-free kernel (`srf_conv1x1_nhwc_direct*`: the same bits in `out`).  packed_split: the weight packed by
     `pack_conv1x1_nhwc_split_weights` (or a callable): unless SRF_GEMM_SPLIT=0 the layer runs on `srf_conv1x1_nhwc_split*` (f32 GEMM
-    on the bf16 MFMA through an exact three-way split; f32-accurate, not the bits of the fma chain)."""
+    on the bf16 MFMA through an exact three-way split; f32-accurate, not the bits of the fma chain).  packed_bf16: the weight packed by
+    `pack_conv1x1_nhwc_bf16_weights` (or a callable): the layer runs on `srf_conv1x1_nhwc_bf16*` -- both operands rounded to bf16 once,
+    exact products, f32 accumulation and epilogue (csrc/gemm_bf16.hip; reduced precision, the caller's explicit choice; packed_weight
+    may then be None).  Tensors beyond the 32-bit ranges of that family keep the f32 route."""
     x_ld = nhwc_ld(x)
     N, H, W, K = x.shape
     if out is None:
@@ -1428,10 +1443,10 @@ def conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, out
     y_ld = nhwc_ld(out)
     L = _lib.lib()
     if max(x_ld, y_ld) * 512 >= (1 << 31):     # beyond the 128-row descriptors of the direct and the split family
-        packed_direct = packed_split = None
-    kind, k, packed = _choose_gemm("conv1x1_nhwc", "(Cout, K)", N * H * W, Cout, K, packed_weight, packed_direct, packed_split)
+        packed_direct = packed_split = packed_bf16 = None
+    kind, k, packed = _choose_gemm("conv1x1_nhwc", "(Cout, K)", N * H * W, Cout, K, packed_weight, packed_direct, packed_split, packed_bf16)
     split, wp = kind == "split", _ptr(packed)
-    timing = _dense_timing("gsplit" if split else "gemm")
+    timing = _dense_timing("gsplit" if kind in ("split", "bf16") else "gemm")
     sc, sh = _opt(scale, "scale"), _opt(shift, "shift")
     mean = None
     if top is not None:
@@ -1451,7 +1466,7 @@ def conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, out
         fl = 2.0 * K * Cout * N * H * W
         # split: six bf16 products per f32 product are issued on the bf16 MFMA; the weights are 6 bytes each
         _dense_timed(timing[1], timing[0], f"{K}->{Cout} @{N}x{H}x{W}" + k["tag"], fl, 6.0 * fl if split else fl,
-                     4.0 * N * H * W * (K + Cout) + (6.0 if split else 4.0) * K * Cout)
+                     4.0 * N * H * W * (K + Cout) + (6.0 if split else 2.0 if kind == "bf16" else 4.0) * K * Cout)
     return (out, mean) if pool else out
 
 
@@ -1633,10 +1648,19 @@ def pack_conv_gemm_split_weights(weight):
     return pack_conv1x1_nhwc_split_weights(weight.detach().permute(0, 2, 3, 1).reshape(Cout, -1).contiguous())
 
 
-def conv_gemm_nhwc(x, packed_weight, Cout, ksize, stride, pad, scale=None, shift=None, relu=False, out=None, packed_split=None):
+def pack_conv_gemm_bf16_weights(weight):
+    """(Cout, Cin, kh, kw) -> packed operand of srf_conv_gemm_nhwc_bf16 (one bf16 plane): k = (tap, input channel), tap slowest."""
+    Cout = weight.shape[0]
+    return pack_conv1x1_nhwc_bf16_weights(weight.detach().permute(0, 2, 3, 1).reshape(Cout, -1).contiguous())
+
+
+def conv_gemm_nhwc(x, packed_weight, Cout, ksize, stride, pad, scale=None, shift=None, relu=False, out=None, packed_split=None,
+                   packed_bf16=None):
     """Conv2d on an NHWC slice as an implicit-im2col GEMM (the strided 3x3 layers); -> (N, Ho, Wo, Cout).  On the f32 MFMA
     (`srf_conv_gemm_nhwc`, packed_weight) or, when packed_split (from `pack_conv_gemm_split_weights`, or a callable) is given and
-    SRF_GEMM_SPLIT is not 0, on the split GEMM (`srf_conv_gemm_nhwc_split`: f32-accurate on the bf16 MFMA)."""
+    SRF_GEMM_SPLIT is not 0, on the split GEMM (`srf_conv_gemm_nhwc_split`: f32-accurate on the bf16 MFMA).  packed_bf16 (from
+    `pack_conv_gemm_bf16_weights`, or a callable): on `srf_conv_gemm_nhwc_bf16` -- operands rounded to bf16 once, f32 accumulation and
+    epilogue (reduced precision, the caller's explicit choice; any stride, so the 3x3 / stride 1 layers of the bf16 image mode too)."""
     x_ld = nhwc_ld(x)
     N, H, W, Cin = x.shape
     kh, kw = ksize
@@ -1646,7 +1670,7 @@ def conv_gemm_nhwc(x, packed_weight, Cout, ksize, stride, pad, scale=None, shift
     elif tuple(out.shape) != (N, Ho, Wo, Cout):
         raise ValueError("conv_gemm_nhwc: out has the wrong shape")
     kind, k, packed_weight = _choose_gemm("conv_gemm_nhwc", "the layer", N * Ho * Wo, Cout, kh * kw * Cin, packed_weight,
-                                          packed_split=packed_split)
+                                          packed_split=packed_split, packed_bf16=packed_bf16)
     split, fn = kind == "split", getattr(_lib.lib(), k["conv"])
     # the kernel addresses its whole input through ONE 32-bit buffer descriptor (N H W x_ld 4 < 2^31 bytes): larger batches
     # run in groups of images (VoVNet stem_3 reads 464 x 800 x 64 per camera: 23 images reach the limit -- LC inference at
@@ -1662,7 +1686,7 @@ def conv_gemm_nhwc(x, packed_weight, Cout, ksize, stride, pad, scale=None, shift
     if timing is not None:
         fl = 2.0 * kh * kw * Cin * Cout * N * Ho * Wo
         _dense_timed(timing[1], timing[0], f"{Cin}->{Cout} {kh}x{kw}/s{stride} @{N}x{H}x{W}" + k["tag"], fl, 6.0 * fl if split else fl,
-                     4.0 * N * (H * W * Cin + Ho * Wo * Cout) + (6.0 if split else 4.0) * kh * kw * Cin * Cout)
+                     4.0 * N * (H * W * Cin + Ho * Wo * Cout) + (6.0 if split else 2.0 if kind == "bf16" else 4.0) * kh * kw * Cin * Cout)
     return out
 
 

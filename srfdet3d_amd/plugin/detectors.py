@@ -56,6 +56,31 @@ class SRFDet(BaseModule):
         # autocast with fp32 outputs, i.e. the reference's `auto_fp16(apply_to=('img'), out_fp32=True)` mode
         # (srfdet.py:141); opt-in, never the default.
         self.img_autocast_dtype = None
+        self._img_mfma_dtype = None
+
+    @property
+    def img_mfma_dtype(self):
+        """None (default: f32) or torch.bfloat16: the image backbone + neck -- the same scope as `img_autocast_dtype`, the reference's
+        `auto_fp16(apply_to=('img'))` -- run on the hand-written bf16-product kernels (`nhwc.mfma_dtype`, csrc/gemm_bf16.hip): f32
+        tensors, operands rounded to bf16 once per layer, f32 accumulation and epilogue.  The head's `img_convs` and everything LiDAR
+        stay f32.  Setting it drops the packed weights and the captured graphs (`_drop_derived_state`): a graph holds pointers to the
+        packed weights of the route it was captured on; `enable_hip_graphs()` captures whichever mode is set."""
+        return self._img_mfma_dtype
+
+    @img_mfma_dtype.setter
+    def img_mfma_dtype(self, dtype):
+        if dtype is not None:
+            if dtype != torch.bfloat16:
+                raise ValueError(f"img_mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
+            if self.img_autocast_dtype is not None:
+                raise ValueError("img_mfma_dtype and img_autocast_dtype exclude each other: set img_autocast_dtype = None first")
+            from .vovnet import VoVNet
+            if not isinstance(getattr(self, "img_backbone", None), VoVNet):
+                raise NotImplementedError("img_mfma_dtype needs an image backbone on the channels-last executor (VoVNet); "
+                                          f"{type(getattr(self, 'img_backbone', None)).__name__} runs through torch")
+        if dtype != self._img_mfma_dtype:
+            self._img_mfma_dtype = dtype
+            self._drop_derived_state()
 
     def enable_hip_graphs(self, enabled=True, img_overlap=False, whole_frame=True):
         """Replay the static-shape tail (SECOND -> FPN -> decoder -> decode) as a captured hipGraph in `simple_test`
@@ -206,12 +231,23 @@ class SRFDet(BaseModule):
             img = img.reshape(-1, *img.shape[2:])
         if self.use_grid_mask and self.training:
             img = self.grid_mask(img)
-        with torch.autocast(img.device.type, dtype=self.img_autocast_dtype, enabled=self.img_autocast_dtype is not None):
+        if self._img_mfma_dtype is not None:
+            if self.img_autocast_dtype is not None:
+                raise ValueError("img_mfma_dtype and img_autocast_dtype exclude each other")
+            if torch.is_grad_enabled() or self.training:
+                # training in the mode is not implemented: no quiet f32 pass through the modules instead
+                raise RuntimeError("img_mfma_dtype covers inference under no_grad in eval mode only (the channels-last executor)")
+        with torch.autocast(img.device.type, dtype=self.img_autocast_dtype, enabled=self.img_autocast_dtype is not None), \
+                nhwc.mfma_dtype(self._img_mfma_dtype) as mode:
             feats = self.img_backbone(img)
             if isinstance(feats, dict):
                 feats = list(feats.values())
             if self.img_neck is not None:
                 feats = self.img_neck(feats)
+        if self._img_mfma_dtype is not None and mode.launches == 0:
+            # a missing kernel route is an error, never a quiet f32 pass (training, autograd or a CPU tensor leave the executor)
+            raise RuntimeError("img_mfma_dtype is set but the image branch did not run on the channels-last executor "
+                               "(it covers fp32 GPU inference under no_grad with BatchNorm in eval mode)")
         out = [f.float().view(B, f.shape[0] // B, *f.shape[1:]) for f in feats]
         return nhwc.ConsumedLevels(out) if isinstance(feats, nhwc.ConsumedLevels) else out
 
