@@ -670,12 +670,23 @@ int srf_dcnv2_nhwc(const float *x, int N, int H, int W, int Cin, long long x_ld,
 
 /* ---- streaming layers of the channels-last camera branch (csrc/nhwc.hip); all take (N, H, W, ld) channel slices, C % 4 == 0,
  * 16-byte aligned pointers, ld % 4 == 0 ---------------------------------------------------------------------------------
+ * Defined exactly by tests/nhwc_ref.py.  Checks, in this order: sizes (negative count, C <= 0, map extent < 1, ld < C: SRF_EINVAL);
+ * the empty batch (N, M or B == 0: SRF_OK, nothing read or written, except that srf_nhwc_affine_relu_bwd* zero `sums`; SRF_OK
+ * also where HW == 0, which srf_nhwc_colmean / _colsum_prod refuse for N > 0); null pointers (SRF_EINVAL); C % 4, ld % 4, pointer
+ * alignment -- the workspace of srf_nhwc_colmean / _colsum_prod included -- and range limits (SRF_EUNSUPPORTED); workspace size
+ * (SRF_EWORKSPACE).
+ * Non-finite values: ReLU and the pooling maximum are fmaxf, which drops a NaN operand: relu(NaN) = 0 in srf_nhwc_affine and
+ * srf_nhwc_dwconv3x3s2*, and a pooling window holding a NaN returns the maximum of its other values, the taps past the bottom /
+ * right edge counting as -inf values: nine NaN give NaN, a clipped window of NaN gives -inf (torch returns NaN in both places).  +-inf, and NaN where no fmaxf follows, propagate as IEEE arithmetic has them.  In srf_nhwc_affine_relu_bwd* a NaN
+ * in y masks the gradient to 0, and a masked gy (NaN included) reaches neither gz nor the sums.
  * srf_nhwc_affine: y = x * scale[(per_sample & 1 ? n : 0)][c] + shift[(per_sample & 2 ? n : 0)][c] (+ residual), optional ReLU; scale / shift / residual
  *   may be NULL; in place allowed: eval BatchNorm2d + ReLU behind a library convolution, and the eSE gate multiply + OSA
- *   identity add of VoVNet (vovnet.py:165-177, :225-228).  HW = pixels per sample.
+ *   identity add of VoVNet (vovnet.py:165-177, :225-228).  HW = pixels per sample (0: nothing to do).  One f32 rounding per
+ *   step (multiply, add shift, add residual); r_ld is ignored when residual is NULL.
  * srf_nhwc_colmean: mean[n][c] over the HW pixels (AdaptiveAvgPool2d(1) of the eSE module), deterministic two-level sum;
  *   C <= 1024.
- * srf_nhwc_maxpool3s2_ceil: MaxPool2d(3, stride 2, ceil_mode=True) (the VoVNet stage pooling) -> (N, Ho, Wo, C).
+ * srf_nhwc_maxpool3s2_ceil: MaxPool2d(3, stride 2, ceil_mode=True) (the VoVNet stage pooling) -> (N, Ho, Wo, C); Ho, Wo as
+ *   torch's for H, W >= 2; H == 1 or W == 1, which torch refuses, gives the one clipped window (Ho = 1 / Wo = 1).
  * srf_nhwc_upsample_add: y = lat + nearest-upsampled top (the FPN top-down step; F.interpolate 'nearest' index rule).
  * srf_nhwc_dwconv3x3s2: depthwise Conv2d(C, C, 3, stride 2, padding 1, groups=C) + scale / shift (+ ReLU): the stair of the
  *   proposal generator on the camera levels (srfdet_head.py:265-320, :525-536); w is (C, 3, 3). */

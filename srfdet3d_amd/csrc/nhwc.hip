@@ -8,12 +8,27 @@
 // (MaxPool2d(3, 2, ceil_mode=True), vovnet.py `_OSA_stage`), the global average pool of the eSE module, the FPN top-down
 // step (mmdet FPN: lateral + nearest-upsampled coarser level), and the depthwise stride-2 stair of the proposal
 // generator (srfdet_head.py:265-320, :525-536).
+//
+// The definition every kernel of this file is held to is tests/nhwc_ref.py (numpy), compared in tests/test_gpu_nhwc_layers.py;
+// the return codes are tabulated in tests/test_nhwc_args.py.  Common to all entry points:
+//   * order of the host checks: sizes (a negative count, C <= 0, a map extent < 1, an ld below its C: SRF_EINVAL), the empty batch
+//     (N, M or B == 0: SRF_OK, nothing is read or written -- except srf_nhwc_affine_relu_bwd*, which zero `sums`), null pointers
+//     (SRF_EINVAL), C % 4 / ld % 4 / 16-byte alignment / range limits (SRF_EUNSUPPORTED), workspace size (SRF_EWORKSPACE).
+//     An empty batch is SRF_OK also where a pixel count that may not be 0 otherwise (HW of the column sums) is 0.
+//   * non-finite values: ReLU and the pooling maximum are fmaxf, which returns its other operand when one is NaN: relu(NaN) = 0
+//     (srf_nhwc_affine, srf_nhwc_dwconv3x3s2*), and a pooling window holding a NaN returns the maximum of its other values, the taps
+//     past the bottom / right edge counting as -inf values (nine NaN give NaN, a clipped window of NaN gives -inf); torch returns
+//     NaN in both places.  +-inf, and NaN wherever no fmaxf follows, propagate as IEEE
+//     arithmetic has them.  srf_nhwc_affine_relu_bwd: the mask is !(y > 0), so a NaN in y masks the gradient to 0, and a masked
+//     gy (NaN included) reaches neither gz nor the sums.
 #include "common.hpp"
 
 typedef float f32x4n __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------------------
-// y[p][c] = x[p][c] * scale[(per_sample ? n : 0)][c] + shift[c] (+ residual[p][c]), optional ReLU.  In place allowed.
+// y[p][c] = x[p][c] * scale[(per_sample & 1 ? n : 0)][c] + shift[(per_sample & 2 ? n : 0)][c] (+ residual[p][c]), optional ReLU:
+// one f32 rounding per step, each step only where its operand is given, ReLU = fmaxf(v, 0) (NaN -> 0).  In place allowed.
+// r_ld is ignored without a residual.  HW == 0 is an empty tensor: SRF_OK.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void srf_nhwc_affine_k(const float *__restrict__ x, long long x_ld, long long M, long long HW, int Cq,
                                                          const float *__restrict__ scale, int per_sample, const float *__restrict__ shift,
@@ -47,7 +62,7 @@ extern "C" int srf_nhwc_affine(const float *x, long long x_ld, int N, long long 
     if (N < 0 || HW < 0 || C <= 0 || x_ld < C || y_ld < C || (residual && r_ld < C)) return SRF_EINVAL;
     if (N == 0 || HW == 0) return SRF_OK;
     if (!x || !y) return SRF_EINVAL;
-    if ((C & 3) || (x_ld & 3) || (y_ld & 3) || (r_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)residual & 15) ||
+    if ((C & 3) || (x_ld & 3) || (y_ld & 3) || (residual && (r_ld & 3)) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)residual & 15) ||
         ((uintptr_t)scale & 15) || ((uintptr_t)shift & 15))
         return SRF_EUNSUPPORTED;
     const long long M = (long long)N * HW, total = M * (C / 4);
@@ -61,7 +76,11 @@ extern "C" int srf_nhwc_affine(const float *x, long long x_ld, int N, long long 
 // mean over the pixels of every (sample, channel): AdaptiveAvgPool2d(1) of the eSE module.  Deterministic two-level sum:
 // level 1: grid (P chunks of pixels, N); a workgroup = 256 threads = (C / 4 channel quads) x (256 / (C / 4) pixel lanes)
 // when C <= 1024; each thread sums its pixels in order, the pixel lanes are combined through LDS in a fixed order;
-// level 2: one thread per (n, channel) adds the P partial sums in order and divides.
+// level 2: one thread per (n, channel) adds the P partial sums in order and multiplies by f32(1 / HW).
+// Longest chain of rounded operations behind one output, with per = ceil(HW / 64) pixels per chunk and lanes = 256 / (C / 4):
+// ceil(per / lanes) adds in a lane (+ 1 for the product of srf_nhwc_colsum_prod), lanes - 1 to combine the lanes, 64 over the
+// chunks (+ 1 for the multiply of srf_nhwc_colmean) -- the d of the error bound gamma_d sum |terms| of tests/nhwc_ref.py.
+// The workspace is written as 16-byte vectors: it must be 16-byte aligned (SRF_EUNSUPPORTED).  HW == 0 with N > 0: SRF_EINVAL.
 // ---------------------------------------------------------------------------------------------------------------------
 #define CM_CHUNKS 64
 
@@ -111,11 +130,11 @@ extern "C" size_t srf_nhwc_colmean_workspace_bytes(int N, int C) { return (N <= 
 extern "C" int srf_nhwc_colmean(const float *x, long long x_ld, int N, long long HW, int C, float *mean, void *workspace,
                                 size_t workspace_bytes, srf_stream_t stream)
 {
-    if (N < 0 || HW <= 0 || C <= 0 || x_ld < C) return SRF_EINVAL;
+    if (N < 0 || HW < 0 || C <= 0 || x_ld < C) return SRF_EINVAL;
     if (N == 0) return SRF_OK;
-    if (!x || !mean || !workspace) return SRF_EINVAL;
+    if (HW == 0 || !x || !mean || !workspace) return SRF_EINVAL;
     const int Cq = C / 4;
-    if ((C & 3) || Cq > 256 || (x_ld & 3) || ((uintptr_t)x & 15) || N > 65535) return SRF_EUNSUPPORTED;
+    if ((C & 3) || Cq > 256 || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)workspace & 15) || N > 65535) return SRF_EUNSUPPORTED;
     if (workspace_bytes < srf_nhwc_colmean_workspace_bytes(N, C)) return SRF_EWORKSPACE;
     hipLaunchKernelGGL(srf_nhwc_colsum_k, dim3(CM_CHUNKS, N), dim3(256), 0, (hipStream_t)stream, x, x_ld, HW, Cq, (float *)workspace);
     hipLaunchKernelGGL(srf_nhwc_colmean_finish_k, dim3(srf_ceil_div((long long)N * C, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -129,11 +148,13 @@ extern "C" int srf_nhwc_colmean(const float *x, long long x_ld, int N, long long
 extern "C" int srf_nhwc_colsum_prod(const float *a, long long a_ld, const float *b, long long b_ld, int N, long long HW, int C, float *out,
                                     void *workspace, size_t workspace_bytes, srf_stream_t stream)
 {
-    if (N < 0 || HW <= 0 || C <= 0 || a_ld < C || b_ld < C) return SRF_EINVAL;
+    if (N < 0 || HW < 0 || C <= 0 || a_ld < C || b_ld < C) return SRF_EINVAL;
     if (N == 0) return SRF_OK;
-    if (!a || !b || !out || !workspace) return SRF_EINVAL;
+    if (HW == 0 || !a || !b || !out || !workspace) return SRF_EINVAL;
     const int Cq = C / 4;
-    if ((C & 3) || Cq > 256 || (a_ld & 3) || (b_ld & 3) || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || N > 65535) return SRF_EUNSUPPORTED;
+    if ((C & 3) || Cq > 256 || (a_ld & 3) || (b_ld & 3) || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)workspace & 15) ||
+        N > 65535)
+        return SRF_EUNSUPPORTED;
     if (workspace_bytes < srf_nhwc_colmean_workspace_bytes(N, C)) return SRF_EWORKSPACE;
     hipLaunchKernelGGL(srf_nhwc_colsum_k, dim3(CM_CHUNKS, N), dim3(256), 0, (hipStream_t)stream, a, a_ld, HW, Cq, (float *)workspace, b, b_ld);
     hipLaunchKernelGGL(srf_nhwc_colmean_finish_k, dim3(srf_ceil_div((long long)N * C, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -144,6 +165,8 @@ extern "C" int srf_nhwc_colsum_prod(const float *a, long long a_ld, const float 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // MaxPool2d(kernel 3, stride 2, ceil_mode=True, no padding): windows that reach past the bottom / right edge are clipped.
+// Output extent srf_pool_out(H) = torch's for every H >= 2; H == 1 (or W == 1), which torch refuses, gives the one clipped
+// window.  The maximum is fmaxf: a NaN in a window is dropped (see the head of the file).
 // ---------------------------------------------------------------------------------------------------------------------
 // One thread = a 2 x 2 block of outputs x 4 channels: its 5 x 5 input pixels are loaded once (25 float4 instead of the 36 that
 // four independent windows read: the kernel is bound by the loads it issues, not by HBM) and reduced as three-tap maxima
@@ -221,7 +244,8 @@ extern "C" int srf_nhwc_maxpool3s2_ceil(const float *x, long long x_ld, int N, i
 
 // ---------------------------------------------------------------------------------------------------------------------
 // FPN top-down step: y[n][yy][xx][c] = lat[n][yy][xx][c] + top[n][floor(yy Ht / H)][floor(xx Wt / W)][c] (F.interpolate
-// mode='nearest' index rule: src = floor(dst * in / out), computed in float like torch: min(int(dst * scale), in - 1)).
+// mode='nearest' index rule: src = floor(dst * in / out), computed in float like torch: min(int(dst * scale), in - 1)),
+// scale = f32(in) / f32(out), the product rounded to f32 -- equal to torch's index for every in <= 64, out <= 129 (swept on the CPU).
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void srf_nhwc_upsample_add_k(const float *__restrict__ lat, long long l_ld, const float *__restrict__ top,
                                                                long long t_ld, int N, int H, int W, int Ht, int Wt, int Cq, float sy, float sx,
@@ -379,6 +403,7 @@ extern "C" int srf_nhwc_dwconv3x3s2_cat(const float *x, long long x_ld, int N, i
 // sy / sx the `nearest` source index of torch (floor(dst * in / out) in float32, clamped); Ho = H, Wo = W, n_cam = 1 is the
 // plain channel sum.  One wave per output: lanes take float4 strides over (cam, c), then an xor-shuffle tree -- a fixed
 // order.  Row b of `out` has out_ld >= Ho * Wo floats; the columns past Ho * Wo are written as zeros (the K padding of fc1).
+// Longest chain of rounded adds behind one output: ceil(n_cam (C / 4) / 64) in a lane, 3 inside a float4, 6 shuffle steps.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void srf_nhwc_pool_sum_k(const float *__restrict__ x, long long x_ld, int B, int n_cam, int H, int W, int Cq,
                                                          int Ho, int Wo, float sy_scale, float sx_scale, float *__restrict__ out, int out_ld)
@@ -428,6 +453,9 @@ extern "C" int srf_nhwc_pool_sum(const float *x, long long x_ld, int B, int n_ca
 // from which the caller forms  d beta = sum_gu  and  d s = sum_p gu * z = (sum_guy - t * sum_gu) / s  (z = (y - t) / s wherever
 // gu != 0) without ever having stored z.  As torch ops this is threshold_backward, a multiply and two strided column sums
 // (four passes over the tensor).  Column sums are deterministic: per-block partials (256 rows each), added in block order.
+// Longest chain of rounded operations behind one sum, with rpp = 256 / (C / 4) rows per pass and nb = ceil(M / 256) blocks:
+// ceil(256 / rpp) in a thread (+ 1 for the fma of sum gu y), rpp to combine the threads, ceil(nb / 16) in a finish segment, 16
+// over the segments.  M == 0: `sums` is zeroed, nothing else is touched.
 // ---------------------------------------------------------------------------------------------------------------------
 #define SRF_ARB_ROWS 256
 

@@ -1164,6 +1164,15 @@ def _dense_timed(records, start, label, flops, executed, nbytes):
     return end
 
 
+def _dw_vectors(name, C, weight, scale, shift):
+    """Lengths of a depthwise convolution's per-channel operands: weight C * 9, scale / shift C."""
+    if weight.numel() != C * 9:
+        raise ValueError(f"{name}: weight must be (C, 1, 3, 3)")
+    for v, what in ((scale, "scale"), (shift, "shift")):
+        if v is not None and v.numel() != C:
+            raise ValueError(f"{name}: {what} must have C elements")
+
+
 def nhwc_ld(x):
     """Floats per pixel of an (N, H, W, C) f32 view whose channels are a slice of a pixel-major buffer; raises if the
     view is not of that form."""
@@ -1476,6 +1485,10 @@ def nhwc_affine(x, scale=None, shift=None, relu=False, residual=None, out=None):
     N, H, W, C = x.shape
     if out is None:
         out = _empty((N, H, W, C), torch.float32, x.device)
+    elif tuple(out.shape) != (N, H, W, C):
+        raise ValueError("nhwc_affine: out has another shape")
+    if residual is not None and tuple(residual.shape) != (N, H, W, C):
+        raise ValueError("nhwc_affine: residual has another shape")
     per_sample = int(scale is not None and scale.dim() == 2) | (2 if (shift is not None and shift.dim() == 2) else 0)
     if scale is not None and scale.numel() != (N * C if per_sample & 1 else C):
         raise ValueError("nhwc_affine: scale has the wrong size")
@@ -1532,8 +1545,12 @@ def nhwc_maxpool3s2_ceil(x, out=None):
 def nhwc_upsample_add(lat, top, out=None):
     """lat (N, H, W, C) + nearest-upsampled top (N, Ht, Wt, C); out defaults to lat (in place)."""
     N, H, W, C = lat.shape
+    if top.dim() != 4 or top.shape[0] != N or top.shape[3] != C:
+        raise ValueError("nhwc_upsample_add: top has another batch size or channel count")
     if out is None:
         out = lat
+    elif tuple(out.shape) != (N, H, W, C):
+        raise ValueError("nhwc_upsample_add: out has another shape")
     check(_lib.lib().srf_nhwc_upsample_add(_ptr(lat), nhwc_ld(lat), _ptr(top), nhwc_ld(top), N, H, W, top.shape[1], top.shape[2], C,
                                            _ptr(out), nhwc_ld(out), _stream()), "nhwc_upsample_add")
     return out
@@ -1548,6 +1565,7 @@ def nhwc_dwconv3x3s2(x, weight, scale=None, shift=None, relu=False, out=None):
         out = _empty((N, Ho, Wo, C), torch.float32, x.device)
     elif tuple(out.shape) != (N, Ho, Wo, C):
         raise ValueError("nhwc_dwconv3x3s2: out has the wrong shape")
+    _dw_vectors("nhwc_dwconv3x3s2", C, weight, scale, shift)
     w = _dev(weight.reshape(C, 9), "weight", torch.float32)
     check(_lib.lib().srf_nhwc_dwconv3x3s2(_ptr(x), x_ld, N, H, W, C, _ptr(w), _opt(scale, "scale"), _opt(shift, "shift"),
                                           int(bool(relu)), _ptr(out), nhwc_ld(out), _stream()), "nhwc_dwconv3x3s2")
@@ -1562,6 +1580,7 @@ def nhwc_dwconv3x3s2_cat(x, weight, scale, shift, relu, side, out):
     Cs = side.shape[3]
     if tuple(side.shape[:3]) != (N, Ho, Wo) or tuple(out.shape) != (N, Ho, Wo, Cs + C):
         raise ValueError("nhwc_dwconv3x3s2_cat: side / out have the wrong shape")
+    _dw_vectors("nhwc_dwconv3x3s2_cat", C, weight, scale, shift)
     w = _dev(weight.reshape(C, 9), "weight", torch.float32)
     check(_lib.lib().srf_nhwc_dwconv3x3s2_cat(_ptr(x), x_ld, N, H, W, C, _ptr(w), _opt(scale, "scale"), _opt(shift, "shift"),
                                               int(bool(relu)), _ptr(out[..., Cs:]), nhwc_ld(out), _ptr(side), nhwc_ld(side), Cs,
@@ -1577,6 +1596,10 @@ def nhwc_affine_relu_bwd(gy, y, scale, relu, gy2=None):
     gy_ld, y_ld = nhwc_ld(gy), nhwc_ld(y)
     if gy2 is not None and tuple(gy2.shape) != tuple(gy.shape):
         raise ValueError("nhwc_affine_relu_bwd: gy2 has another shape")
+    if tuple(y.shape) != tuple(gy.shape):
+        raise ValueError("nhwc_affine_relu_bwd: y has another shape")
+    if scale is not None and scale.numel() != C:
+        raise ValueError("nhwc_affine_relu_bwd: scale must have C elements")
     M = N * H * W
     L = _lib.lib()
     gz = _empty((N, H, W, C), torch.float32, gy.device)
@@ -1592,6 +1615,8 @@ def nhwc_affine_relu_bwd(gy, y, scale, relu, gy2=None):
 def bn_eval_fold(gamma, beta, mean, var, eps):
     """(3, C): s = gamma / sqrt(var + eps), t0 = beta - mean s, inv = 1 / sqrt(var + eps) of an eval-mode BatchNorm (one launch)."""
     C = gamma.numel()
+    if not (beta.numel() == mean.numel() == var.numel() == C):
+        raise ValueError("bn_eval_fold: gamma, beta, mean and var must have one length")
     out = _empty((3, C), torch.float32, gamma.device)
     check(_lib.lib().srf_bn_eval_fold(_ptr(_dev(gamma, "gamma", torch.float32)), _ptr(_dev(beta, "beta", torch.float32)),
                                       _ptr(_dev(mean, "mean", torch.float32)), _ptr(_dev(var, "var", torch.float32)), float(eps), C, _ptr(out),
@@ -1602,6 +1627,8 @@ def bn_eval_fold(gamma, beta, mean, var, eps):
 def bn_eval_grads(sums, fold, mean):
     """(2, C): d gamma, d beta of an eval-mode BatchNorm from nhwc_affine_relu_bwd's column sums and bn_eval_fold's vectors (one launch)."""
     C = mean.numel()
+    if sums.numel() != 2 * C or fold.numel() != 3 * C:
+        raise ValueError("bn_eval_grads: sums must be (2, C) and fold (3, C)")
     out = _empty((2, C), torch.float32, sums.device)
     check(_lib.lib().srf_bn_eval_grads(_ptr(sums), _ptr(fold), _ptr(_dev(mean, "mean", torch.float32)), C, _ptr(out), _stream()), "bn_eval_grads")
     return out
@@ -1612,6 +1639,8 @@ def nhwc_pool_sum(x, n_cam=1, size=None, pad_to=4):
     source pixel (size = (Ho, Wo); None: the map itself); columns past Ho * Wo are zeros (row length rounded up to pad_to)."""
     x_ld = nhwc_ld(x)
     Nimg, H, W, C = x.shape
+    if n_cam < 1 or Nimg % n_cam:
+        raise ValueError("nhwc_pool_sum: the image count is not a multiple of n_cam")
     B = Nimg // n_cam
     Ho, Wo = (H, W) if size is None else (int(size[0]), int(size[1]))
     out_ld = -(-(Ho * Wo) // pad_to) * pad_to
