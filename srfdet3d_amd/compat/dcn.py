@@ -76,14 +76,9 @@ class ModulatedDeformConv2dPack(nn.Module):
                 and ops.dcnv2_supported(x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.groups, self.deform_groups))
 
     def _packed(self, name, weight):
-        """Packed GEMM operand of `weight`, cached on the module until the parameter changes (as dense._packed_1x1)."""
-        from .. import ops
-        vers = (weight._version, weight.data_ptr())
-        cache = getattr(self, name, None)
-        if cache is None or cache[0] != vers:
-            cache = (vers, ops.pack_conv_gemm_weights(weight.detach()))
-            setattr(self, name, cache)
-        return cache[1]
+        """Packed GEMM operand of `weight`, kept until the parameter changes (derived.py)."""
+        from .. import derived, ops
+        return derived.get(self, name, (weight,), lambda: ops.pack_conv_gemm_weights(weight.detach()))
 
     def forward_hip(self, x, scale=None, shift=None, relu=False):
         """act(scale * dcn(x) + shift) -> (N, Cout, Ho, Wo) NCHW-contiguous; the module's bias is folded into shift."""
@@ -96,11 +91,11 @@ class ModulatedDeformConv2dPack(nn.Module):
         xh = ops.to_channels_last(x).permute(0, 2, 3, 1)
         co = self.conv_offset
         if self.dilation == 1:
-            om = ops.conv_gemm_nhwc(xh, self._packed("_srf_packed_offset", co.weight), 3 * KG, (k, k), self.stride, self.padding,
+            om = ops.conv_gemm_nhwc(xh, self._packed("dcn_offset", co.weight), 3 * KG, (k, k), self.stride, self.padding,
                                     None, co.bias.detach())
         else:   # srf_conv_gemm_nhwc has no dilation: the 3 K G-channel convolution stays where it was
             om = co(x).permute(0, 2, 3, 1).contiguous()
-        y = ops.dcnv2_nhwc(xh, om[..., :2 * KG], om[..., 2 * KG:], self._packed("_srf_packed", self.weight), self.out_channels, (k, k),
+        y = ops.dcnv2_nhwc(xh, om[..., :2 * KG], om[..., 2 * KG:], self._packed("dcn", self.weight), self.out_channels, (k, k),
                            self.stride, self.padding, self.dilation, self.deform_groups, True, scale, shift, relu)
         return y.permute(0, 3, 1, 2).contiguous()
 

@@ -10,21 +10,9 @@ import os
 import torch
 from torch import nn
 
-from . import ops
+from . import derived, ops
 
-
-def _fold_bn2d(bn):
-    """scale = gamma / sqrt(var + eps), shift = beta - mean * scale, cached until a BN tensor changes."""
-    vers = (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version,
-            bn.weight.data_ptr(), bn.running_var.data_ptr())
-    cache = getattr(bn, "_srf_fold", None)
-    if cache is None or cache[0] != vers:
-        with torch.no_grad():
-            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            shift = bn.bias - bn.running_mean * scale
-        cache = (vers, scale.contiguous(), shift.contiguous())
-        bn._srf_fold = cache
-    return cache[1], cache[2]
+_fold_bn2d = derived.fold_bn   # the name tests/test_gpu_dense.py and tests/test_gpu_dcn.py take the fold by
 
 
 def _foldable(bn):
@@ -37,7 +25,7 @@ def fusable(x):
 
 def bn_act_(y, bn, relu):
     """In place on the contiguous NCHW conv output y."""
-    scale, shift = _fold_bn2d(bn)
+    scale, shift = derived.fold_bn(bn)
     return ops.channel_affine(y, scale, shift, relu, out=y)
 
 
@@ -55,11 +43,11 @@ def _is_dcn(conv):
 def conv_bn_act(conv, bn, relu, x):
     if _is_dw3x3s2(conv, x) and _foldable(bn) and fusable(x):
         # the depthwise stair of the proposal generator: convolution, BatchNorm and ReLU in one streaming kernel
-        scale, shift = _fold_bn2d(bn)
+        scale, shift = derived.fold_bn(bn)
         return ops.dwconv3x3s2(x, conv.weight, scale, shift, relu)
     if _is_dcn(conv) and _foldable(bn) and conv.hip_route(x):
         # the deformable 3x3 of a ResNet bottleneck (compat/resnet.py): BatchNorm and ReLU as the epilogue of srf_dcnv2_nhwc
-        scale, shift = _fold_bn2d(bn)
+        scale, shift = derived.fold_bn(bn)
         return conv.forward_hip(x, scale, shift, relu)
     from . import train_conv
     if _train_fusable(x):
@@ -73,15 +61,6 @@ def conv_bn_act(conv, bn, relu, x):
     return torch.relu_(y) if relu else y
 
 
-def _packed_1x1(conv):
-    vers = (conv.weight._version, conv.weight.data_ptr())
-    cache = getattr(conv, "_srf_packed", None)
-    if cache is None or cache[0] != vers:
-        cache = (vers, ops.pack_conv1x1_weights(conv.weight.detach()))
-        conv._srf_packed = cache
-    return cache[1]
-
-
 def _is_plain_1x1(conv):
     return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
             and conv.groups == 1 and conv.dilation == (1, 1))
@@ -93,12 +72,13 @@ def conv1x1_cat_bn_act(conv, bn, relu, xs):
     if (_is_plain_1x1(conv) and (bn is None or _foldable(bn)) and fusable(xs[0]) and ops.conv1x1_supported(xs, conv.out_channels)
             and sum(x.shape[1] for x in xs) == conv.in_channels):
         if bn is not None:
-            scale, shift = _fold_bn2d(bn)
+            scale, shift = derived.fold_bn(bn)
             if conv.bias is not None:
                 shift = shift + conv.bias * scale
         else:
             scale, shift = None, conv.bias
-        return ops.conv1x1(xs, _packed_1x1(conv), conv.out_channels, scale, shift, relu)
+        packed = derived.get(conv, "conv1x1_nchw", (conv.weight,), lambda: ops.pack_conv1x1_weights(conv.weight.detach()))
+        return ops.conv1x1(xs, packed, conv.out_channels, scale, shift, relu)
     x = xs[0] if len(xs) == 1 else torch.cat(xs, dim=1)
     if bn is None:
         from . import train_conv
@@ -153,15 +133,11 @@ def linear_graph_safe(lin, x, relu=False, act=None):
     K = lin.in_features
     w = lin.weight
     if K % 4:
-        vers = (w._version, w.data_ptr())
-        cache = getattr(lin, "_srf_padded", None)
-        if cache is None or cache[0] != vers:
-            Kp = (K + 3) // 4 * 4
-            wp = w.new_zeros((w.shape[0], Kp))
+        def pad():
+            wp = w.new_zeros((w.shape[0], (K + 3) // 4 * 4))
             wp[:, :K] = w.detach()
-            cache = (vers, wp)
-            lin._srf_padded = cache
-        w = cache[1]
+            return wp
+        w = derived.get(lin, "linear_padded", (w,), pad)
         if x.shape[1] != w.shape[1]:
             x = torch.nn.functional.pad(x, (0, w.shape[1] - K))
     return ops.linear(x.contiguous(), w, lin.bias, relu1=bool(relu))

@@ -27,8 +27,8 @@ import os
 import torch
 from torch import nn
 
-from . import ops
-from .dense import _fold_bn2d, _foldable, fusable
+from . import derived, ops
+from .dense import _foldable, fusable
 
 
 def enabled():
@@ -50,27 +50,26 @@ def is_channels_last(x):
     return x.dim() == 4 and x.stride(1) == 1 and x.shape[1] > 1
 
 
-def _cached(mod, key, vers, make):
-    cache = getattr(mod, key, None)
-    if cache is None or cache[0] != vers:
-        cache = (vers, make())
-        setattr(mod, key, cache)
-    return cache[1]
+# kind -> the pack call of that operand; the packed images are held by `derived` under the kind's name
+_PACK = {
+    "wino": ops.pack_wino3x3_weights, "wino43": ops.pack_wino43_weights,
+    "gemm": ops.pack_conv1x1_nhwc_weights, "gemm_direct": ops.pack_conv1x1_nhwc_direct_weights,
+    "gemm_split": ops.pack_conv1x1_nhwc_split_weights, "gemm_bf16": ops.pack_conv1x1_nhwc_bf16_weights,
+    "cgemm": ops.pack_conv_gemm_weights, "cgemm_split": ops.pack_conv_gemm_split_weights, "cgemm_bf16": ops.pack_conv_gemm_bf16_weights,
+}
 
 
-_CACHE_KEYS = ("_srf_wino", "_srf_wino43", "_srf_gemm", "_srf_gemm_direct", "_srf_gemm_split", "_srf_cgemm", "_srf_cgemm_split", "_srf_packed",
-               "_srf_gemm_bf16", "_srf_cgemm_bf16")
+def packed(conv, kind):
+    """The `kind` operand of conv.weight, packed once and kept until the weight changes."""
+    return derived.get(conv, kind, (conv.weight,), lambda: _PACK[kind](conv.weight.detach()))
 
 
 def invalidate_caches(model):
-    """Drops the packed-weight images cached on the convolution modules of `model`.  The caches are keyed on (weight._version,
-    data_ptr): optimiser steps, `copy_` and `load_state_dict` bump the version, but an in-place update THROUGH `.data`
-    (`p.data.mul_()`, old-style EMA) does not -- call this after such an update.  The detector calls it from `train()` and
-    after `load_state_dict`."""
-    for m in model.modules():
-        for k in _CACHE_KEYS:
-            if hasattr(m, k):
-                delattr(m, k)
+    """Drops everything derived from the parameters and buffers of `model`'s modules (packed operands, BatchNorm folds, padded
+    weights: derived.py).  Needed after an update the version counters cannot see, `p.data.mul_()` or old-style EMA; the detector
+    calls it from `train()`, after `load_state_dict` and from `weights_changed()`, which also drops the graphs captured over these
+    tensors -- on a model with live graphs call that, not this."""
+    derived.invalidate(model)
 
 
 # ---- the bf16-product mode of the image branch (csrc/gemm_bf16.hip) ------------------------------------------------------------
@@ -141,26 +140,6 @@ def _bf16_route(x, conv, out, form):
     return why is None
 
 
-def _gemm_bf16_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_gemm_bf16", (w._version, w.data_ptr()), lambda: ops.pack_conv1x1_nhwc_bf16_weights(w.detach()))
-
-
-def _conv_bf16_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_cgemm_bf16", (w._version, w.data_ptr()), lambda: ops.pack_conv_gemm_bf16_weights(w))
-
-
-def _wino_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_wino", (w._version, w.data_ptr()), lambda: ops.pack_wino3x3_weights(w.detach()))
-
-
-def _gemm_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_gemm", (w._version, w.data_ptr()), lambda: ops.pack_conv1x1_nhwc_weights(w.detach()))
-
-
 def _is_conv(conv, k, stride=1):
     return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (k, k) and conv.stride == (stride, stride)
             and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1) and conv.groups == 1)
@@ -169,16 +148,11 @@ def _is_conv(conv, k, stride=1):
 def _affine_of(conv, bn):
     """(scale, shift) of the layer's epilogue: folded eval BatchNorm (and bias), or the bias alone."""
     if bn is not None:
-        scale, shift = _fold_bn2d(bn)
+        scale, shift = derived.fold_bn(bn)
         if conv.bias is not None:
             shift = shift + conv.bias * scale
         return scale, shift
     return None, conv.bias
-
-
-def _wino43_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_wino43", (w._version, w.data_ptr()), lambda: ops.pack_wino43_weights(w.detach()))
 
 
 def wino43_enabled():
@@ -198,28 +172,18 @@ def conv3x3(x, conv, bn=None, relu=False, out=None):
     scale, shift = _affine_of(conv, bn)
     if _bf16_route(x, conv, out, "conv"):
         return ops.conv_gemm_nhwc(x, None, conv.out_channels, (3, 3), 1, 1, scale, shift, relu, out=out,
-                                  packed_bf16=lambda: _conv_bf16_weights(conv))
+                                  packed_bf16=lambda: packed(conv, "cgemm_bf16"))
     if use_wino43(x, conv.out_channels, out):
-        return ops.wino43(x, _wino43_weights(conv), conv.out_channels, scale, shift, relu, out=out)
-    return ops.wino3x3(x, _wino_weights(conv), conv.out_channels, scale, shift, relu, out=out)
-
-
-def _gemm_direct_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_gemm_direct", (w._version, w.data_ptr()), lambda: ops.pack_conv1x1_nhwc_direct_weights(w.detach()))
-
-
-def _gemm_split_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_gemm_split", (w._version, w.data_ptr()), lambda: ops.pack_conv1x1_nhwc_split_weights(w.detach()))
+        return ops.wino43(x, packed(conv, "wino43"), conv.out_channels, scale, shift, relu, out=out)
+    return ops.wino3x3(x, packed(conv, "wino"), conv.out_channels, scale, shift, relu, out=out)
 
 
 def conv1x1(x, conv, bn=None, relu=False, out=None, pool=False, top=None):
     scale, shift = _affine_of(conv, bn)
     # the operand orders are packed lazily: a layer only ever packs the one its launch selects
-    return ops.conv1x1_nhwc(x, lambda: _gemm_weights(conv), conv.out_channels, scale, shift, relu, out=out, pool=pool, top=top,
-                            packed_direct=lambda: _gemm_direct_weights(conv), packed_split=lambda: _gemm_split_weights(conv),
-                            packed_bf16=(lambda: _gemm_bf16_weights(conv)) if _bf16_route(x, conv, out, "1x1") else None)
+    return ops.conv1x1_nhwc(x, lambda: packed(conv, "gemm"), conv.out_channels, scale, shift, relu, out=out, pool=pool, top=top,
+                            packed_direct=lambda: packed(conv, "gemm_direct"), packed_split=lambda: packed(conv, "gemm_split"),
+                            packed_bf16=(lambda: packed(conv, "gemm_bf16")) if _bf16_route(x, conv, out, "1x1") else None)
 
 
 def wino_ok(conv, cin):
@@ -376,16 +340,6 @@ def vovnet_forward(net, x, upto=None):
     return out
 
 
-def _strided_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_cgemm", (w._version, w.data_ptr()), lambda: ops.pack_conv_gemm_weights(w))
-
-
-def _strided_split_weights(conv):
-    w = conv.weight
-    return _cached(conv, "_srf_cgemm_split", (w._version, w.data_ptr()), lambda: ops.pack_conv_gemm_split_weights(w))
-
-
 def strided_ok(conv, cin):
     return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.dilation == (1, 1) and conv.stride[0] == conv.stride[1]
             and conv.padding[0] == conv.padding[1] and cin % 32 == 0)
@@ -395,9 +349,9 @@ def conv_strided(x, conv, bn=None, relu=False, out=None):
     """A convolution the Winograd kernel does not cover (stride 2) as an implicit-im2col GEMM on the f32 MFMA
     (`srf_conv_gemm_nhwc`): deterministic, where MIOpen's channels-last choice is an atomic split-K kernel."""
     scale, shift = _affine_of(conv, bn)
-    return ops.conv_gemm_nhwc(x, lambda: _strided_weights(conv), conv.out_channels, conv.kernel_size, conv.stride[0], conv.padding[0],
-                              scale, shift, relu, out=out, packed_split=lambda: _strided_split_weights(conv),
-                              packed_bf16=(lambda: _conv_bf16_weights(conv)) if _bf16_route(x, conv, out, "conv") else None)
+    return ops.conv_gemm_nhwc(x, lambda: packed(conv, "cgemm"), conv.out_channels, conv.kernel_size, conv.stride[0], conv.padding[0],
+                              scale, shift, relu, out=out, packed_split=lambda: packed(conv, "cgemm_split"),
+                              packed_bf16=(lambda: packed(conv, "cgemm_bf16")) if _bf16_route(x, conv, out, "conv") else None)
 
 
 def to_nhwc(x):

@@ -98,10 +98,10 @@ class SRFDet(BaseModule):
         return self
 
     def _drop_derived_state(self):
-        """Packed-weight images cached on the convolutions AND the captured hipGraphs.  A graph holds the raw device pointers of
-        the packed weights of its warm-up pass; once those tensors are dropped their blocks return to the caching allocator, and a
-        replay would read whatever lives there next as weights.  So both go together: the next inference pass packs
-        afresh and recaptures."""
+        """Everything derived from parameters and buffers (derived.py: packed operands, BatchNorm folds, padded weights) AND the
+        captured hipGraphs.  A graph holds the raw device pointers of the derived tensors of its warm-up pass; once those are dropped
+        their blocks return to the caching allocator, and a replay would read whatever lives there next as weights.  So
+        both go together: the next inference pass builds them afresh and recaptures."""
         from .. import nhwc
         nhwc.invalidate_caches(self)
         cfg = getattr(self, "_graph_cfg", None)
@@ -130,8 +130,8 @@ class SRFDet(BaseModule):
 
     def weights_changed(self):
         """Tell the model that its weights were modified in place while it stayed in eval mode (optimizer.step() between two
-        inference calls, `p.data.copy_()`, EMA updates): captured hipGraphs replay raw pointers to packed-weight images that no
-        longer match.  `train()`, `load_state_dict()` and `.to()` / `.cuda()` / `.float()` call this themselves."""
+        inference calls, `p.data.copy_()`, EMA updates): everything derived from them is dropped, BatchNorm folds included, and with it
+        the captured hipGraphs, which replay raw pointers into those tensors.  `train()`, `load_state_dict()` and `.to()` / `.cuda()` / `.float()` call this themselves."""
         self._drop_derived_state()
 
     def _apply(self, fn, *args, **kwargs):

@@ -25,7 +25,8 @@ from torch import nn
 from .. import nhwc, ops
 from ..compat.cnn import BaseModule, ConvModule, ModuleList, build_activation_layer, build_conv_layer
 from ..compat.registry import HEADS, LOSSES, BBOX_ASSIGNERS, build_head, build_roi_extractor
-from ..dense import _fold_bn2d, _foldable, fusable, linear_graph_safe
+from ..dense import _foldable, fusable, linear_graph_safe
+from ..derived import fold_bn
 from ..roi import SingleRoIExtractor
 from .bbox_util import denormalize_bbox
 
@@ -560,11 +561,11 @@ class SRFDetHead(BaseModule):
             cm = convs[lvl - 1]
             c_lvl, c_x = f.shape[3], x.shape[3]
             buf = torch.empty((*f.shape[:3], c_lvl + c_x), dtype=torch.float32, device=f.device)
-            scale, shift = _fold_bn2d(getattr(cm, cm.norm_name))
+            scale, shift = fold_bn(getattr(cm, cm.norm_name))
             x = ops.nhwc_dwconv3x3s2_cat(x, cm.conv.weight, scale, shift, True, f, buf)
             if lvl == len(feats) - 1 and lvl < len(convs):
                 cm = convs[lvl]
-                scale, shift = _fold_bn2d(getattr(cm, cm.norm_name))
+                scale, shift = fold_bn(getattr(cm, cm.norm_name))
                 x = ops.nhwc_dwconv3x3s2(x, cm.conv.weight, scale, shift, True)
         return x if as_nhwc else nhwc.nchw_view(x)
 

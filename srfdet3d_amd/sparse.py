@@ -17,7 +17,7 @@ import math
 import torch
 from torch import nn
 
-from . import ops
+from . import derived, ops
 from .compat.cnn import build_norm_layer
 from .compat.registry import CONV_LAYERS
 
@@ -105,18 +105,7 @@ class SparseConvTensor:
         return int(torch.tensor(self.spatial_shape).prod())
 
 
-def _fold_bn(bn):
-    """alpha = gamma / sqrt(var + eps), beta = bias - mean * alpha, cached until any BN tensor changes."""
-    vers = (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version,
-            bn.weight.data_ptr(), bn.running_var.data_ptr())
-    cache = getattr(bn, "_srf_fold", None)
-    if cache is None or cache[0] != vers:
-        with torch.no_grad():
-            alpha = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            beta = bn.bias - bn.running_mean * alpha
-        cache = (vers, alpha.contiguous(), beta.contiguous())
-        bn._srf_fold = cache
-    return cache[1], cache[2]
+_fold_bn = derived.fold_bn   # the name tests/test_host_modules.py takes the fold by
 
 
 def _bn_foldable(bn):
@@ -213,20 +202,12 @@ class _SparseConv(SparseModule):
         w = self.weight.view(K, self.in_channels, self.out_channels)
         alpha = beta = None
         if bn is not None:
-            alpha, beta = _fold_bn(bn)
+            alpha, beta = derived.fold_bn(bn)
             if self.bias is not None:
                 beta = beta + self.bias * alpha
         elif self.bias is not None:
             alpha, beta = torch.ones_like(self.bias), self.bias
-        packed = None
-        if use_packed:
-            vers = (self.weight._version, self.weight.data_ptr())
-            cache = getattr(self, "_srf_packed", None)
-            if cache is None or cache[0] != vers:
-                with torch.no_grad():
-                    cache = (vers, ops.pack_spconv_weights(w.detach()))
-                self._srf_packed = cache
-            packed = cache[1]
+        packed = derived.get(self, "spconv", (self.weight,), lambda: ops.pack_spconv_weights(w.detach())) if use_packed else None
         feats = ops.spconv_fwd(x.features, w, nbr, alpha, beta, residual, relu, pair_counts=counts, packed=packed,
                                rows_dev=rows_dev, tiles=tiles, subm=self.subm)
         return SparseConvTensor(feats, out_idx, oshape, x.batch_size, x.indice_dict, rows_dev)

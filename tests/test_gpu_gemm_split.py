@@ -122,17 +122,17 @@ def test_split_topdown_equals_conv_then_upsample_add(dev, N, H, W, Ht, Wt, K, Co
 def test_camera_executor_routes_1x1_layers_to_the_split_kernel_by_default(dev, monkeypatch):
     """nhwc.conv1x1 (OSA `concat` layers, FPN laterals) takes the split kernel unless SRF_GEMM_SPLIT=0, and both routes agree
     within the f32 chain's own error."""
-    from srfdet3d_amd import nhwc
+    from srfdet3d_amd import derived, nhwc
     g = torch.Generator().manual_seed(9)
     conv = torch.nn.Conv2d(256, 128, 1, bias=True).to(dev)
     x = torch.relu(torch.randn(2, 24, 40, 256, generator=g)).to(dev)
     with torch.no_grad():
         monkeypatch.delenv("SRF_GEMM_SPLIT", raising=False)
         a = nhwc.conv1x1(x, conv).clone()
-        assert hasattr(conv, "_srf_gemm_split") and not hasattr(conv, "_srf_gemm")
+        assert "gemm_split" in derived.names(conv) and "gemm" not in derived.names(conv)
         monkeypatch.setenv("SRF_GEMM_SPLIT", "0")
         b = nhwc.conv1x1(x, conv).clone()
-        assert hasattr(conv, "_srf_gemm") or hasattr(conv, "_srf_gemm_direct")
+        assert derived.names(conv) & {"gemm", "gemm_direct"}
         want = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2).double().cpu(), conv.weight.double().cpu(), conv.bias.double().cpu()).permute(0, 2, 3, 1)
     assert (a.double().cpu() - want).abs().max().item() <= 3e-6 * want.abs().max().item()
     assert (b.double().cpu() - want).abs().max().item() <= 3e-6 * want.abs().max().item()
@@ -142,7 +142,7 @@ def test_camera_executor_routes_1x1_layers_to_the_split_kernel_by_default(dev, m
     conv2 = torch.nn.Conv2d(256, 128, 1, bias=True).to(dev)
     with torch.no_grad():
         nhwc.conv1x1(x, conv2)
-    assert not hasattr(conv2, "_srf_gemm_split") and (hasattr(conv2, "_srf_gemm") or hasattr(conv2, "_srf_gemm_direct"))
+    assert "gemm_split" not in derived.names(conv2) and derived.names(conv2) & {"gemm", "gemm_direct"}
     assert ops.gemm_split_wanted(6 * 232 * 400, 256) and not ops.gemm_split_wanted(92 * 92, 128)
 
 

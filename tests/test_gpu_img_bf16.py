@@ -12,7 +12,7 @@ from torch import nn
 if __name__ == "__main__":   # run as the child process of `switch_results`: what tests/conftest.py does for pytest
     sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
 
-from srfdet3d_amd import nhwc, ops, synthetic as S, workloads
+from srfdet3d_amd import derived, nhwc, ops, synthetic as S, workloads
 from srfdet3d_amd.compat.boxes import LiDARInstance3DBoxes
 
 pytestmark = pytest.mark.gpu
@@ -37,8 +37,12 @@ def _bn(c, seed):
     return bn
 
 
+_PACKED = {"wino", "wino43", "gemm", "gemm_direct", "gemm_split", "gemm_bf16", "cgemm", "cgemm_split", "cgemm_bf16", "conv1x1_nchw", "spconv", "dcn"}
+
+
 def _cache_keys(mod):
-    return sorted(k for k in nhwc._CACHE_KEYS if hasattr(mod, k))
+    """The packed operands held for `mod` (derived.py)."""
+    return sorted(derived.names(mod) & _PACKED)
 
 
 # ---- routing -------------------------------------------------------------------------------------------------------------------
@@ -87,7 +91,7 @@ def test_mode_routes_the_three_layer_kinds_to_the_bf16_kernels_and_leaves_them_a
     assert torch.equal(inner, off0[0])
     assert mode.launches == 5 and [r["route"] for r in routes] == ["bf16"] * 5
     assert routes[0]["layer"] == "64->72 3x3/s1 @2x21x27" and routes[4]["layer"] == "96->136 3x3/s2 @2x21x27"
-    assert "_srf_cgemm_bf16" in _cache_keys(c3) and "_srf_gemm_bf16" in _cache_keys(c1) and "_srf_cgemm_bf16" in _cache_keys(cs)
+    assert "cgemm_bf16" in _cache_keys(c3) and "gemm_bf16" in _cache_keys(c1) and "cgemm_bf16" in _cache_keys(cs)
     for m in (c3, c1, cs):
         nhwc.invalidate_caches(m)
         assert _cache_keys(m) == []
@@ -192,7 +196,7 @@ def _switch_scenario(lc, dev):
     r["mode_captured"] = bool(g._graphed_img.entries)
     r["mode_replays_repeat"] = _same_det(d1, det(g))
     r["mode_changes_detections"] = not _same_det(d1, d0)
-    r["mode_packed_bf16"] = any("_srf_cgemm_bf16" in _cache_keys(m) for m in g.img_backbone.modules())
+    r["mode_packed_bf16"] = any("cgemm_bf16" in _cache_keys(m) for m in g.img_backbone.modules())
     # graph replay == eager, bit for bit, in the mode: the camera graph's feature buffers against the same chain run eagerly
     replayed = [f.clone() for f in next(iter(g._graphed_img.entries.values()))["feats"]]
     with torch.no_grad(), nhwc.level_consumer(g.img_neck, g.bbox_head.img_level_consumer()):

@@ -26,7 +26,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from srfdet3d_amd import dense, ops, synthetic as S, workloads  # noqa: E402
+from srfdet3d_amd import dense, derived, ops, synthetic as S, workloads  # noqa: E402
 from srfdet3d_amd.compat.dcn import ModulatedDeformConv2dPack  # noqa: E402
 
 F32_MFMA_PEAK_TFLOPS = 157.3
@@ -83,9 +83,9 @@ def layer(shape, dev, min_s, repeats, once):
         diff = ((y_hip - y_torch).abs().max() / y_torch.abs().max()).item()
         # the kernel alone, and the plain convolution on the same channels-last tensor
         xh = ops.to_channels_last(x).permute(0, 2, 3, 1)
-        om = ops.conv_gemm_nhwc(xh, pack._packed("_srf_packed_offset", pack.conv_offset.weight), 27, (3, 3), 1, 1, None, pack.conv_offset.bias)
-        pw = pack._packed("_srf_packed", pack.weight)
-        scale, shift = dense._fold_bn2d(bn)
+        om = ops.conv_gemm_nhwc(xh, pack._packed("dcn_offset", pack.conv_offset.weight), 27, (3, 3), 1, 1, None, pack.conv_offset.bias)
+        pw = pack._packed("dcn", pack.weight)
+        scale, shift = derived.fold_bn(bn)
         yk = torch.empty(N, H, W, Cout, device=dev)
         yp = torch.empty(N, H, W, Cout, device=dev)
 
