@@ -3,6 +3,7 @@ mmcv.runner's BaseModule (state_dict names match mmcv: ConvModule.{conv,bn,activ
 import torch
 from torch import nn
 
+from .. import train_conv
 from .registry import ACTIVATION_LAYERS, CONV_LAYERS, NORM_LAYERS
 
 CONV_LAYERS.register_module("Conv2d", module=nn.Conv2d)
@@ -95,12 +96,10 @@ class ConvModule(nn.Module):
             if _foldable(norm) and fusable(x) and (relu or not self.with_activation):
                 return conv_bn_act(self.conv, norm, relu, x)
         if isinstance(self.conv, nn.Conv2d):
-            from .. import train_conv
             x = train_conv.conv2d(self.conv, x)   # training: the 3x3 layers on srf_wino43 (forward and data gradient)
         else:
             x = self.conv(x)
         if self.with_norm:
-            from .. import train_conv
             norm = getattr(self, self.norm_name)
             x = norm(train_conv.bn_train_input(norm, x))   # a train-mode BatchNorm never sees a channels-last tensor (MIOpen crash)
         if self.with_activation:

@@ -5,18 +5,16 @@ The convolutions stay on MIOpen; the eval-mode BatchNorm2d and the ReLU behind e
 autograd / autocast behaviour are untouched: the fused route is taken only for fp32 CUDA tensors with grad disabled and
 BatchNorm in eval mode, everything else goes through the modules as written.
 """
-import os
-
 import torch
 from torch import nn
 
-from . import derived, ops
+from . import derived, ops, train_conv
 
 _fold_bn2d = derived.fold_bn   # the name tests/test_gpu_dense.py and tests/test_gpu_dcn.py take the fold by
 
 
 def _foldable(bn):
-    return isinstance(bn, nn.BatchNorm2d) and not bn.training and bn.track_running_stats and bn.affine
+    return derived.foldable_bn(bn, nn.BatchNorm2d)
 
 
 def fusable(x):
@@ -49,7 +47,6 @@ def conv_bn_act(conv, bn, relu, x):
         # the deformable 3x3 of a ResNet bottleneck (compat/resnet.py): BatchNorm and ReLU as the epilogue of srf_dcnv2_nhwc
         scale, shift = derived.fold_bn(bn)
         return conv.forward_hip(x, scale, shift, relu)
-    from . import train_conv
     if _train_fusable(x):
         y = train_conv.conv_bn_act(conv, bn, relu, x)   # training: conv + eval BatchNorm + ReLU as one autograd node
         if y is not None:
@@ -81,7 +78,6 @@ def conv1x1_cat_bn_act(conv, bn, relu, xs):
         return ops.conv1x1(xs, packed, conv.out_channels, scale, shift, relu)
     x = xs[0] if len(xs) == 1 else torch.cat(xs, dim=1)
     if bn is None:
-        from . import train_conv
         y = train_conv.conv2d(conv, x)
         return torch.relu_(y) if relu else y
     return conv_bn_act(conv, bn, relu, x)
@@ -89,8 +85,7 @@ def conv1x1_cat_bn_act(conv, bn, relu, xs):
 
 def _train_fusable(x):
     """under autograd: conv -> eval-mode BatchNorm -> ReLU may run as train_conv._ConvAffineRelu (conv_bn_act decides per layer)"""
-    return (torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
-            and os.environ.get("SRF_TRAIN_FUSED", "1") != "0")
+    return train_conv.trains("dense", x)
 
 
 def run_sequential(seq, x):
@@ -104,11 +99,9 @@ def run_sequential(seq, x):
             x = conv_bn_act(m, mods[i + 1], relu, x)
             i += 3 if relu else 2
         elif isinstance(m, nn.Conv2d):
-            from . import train_conv
             x = train_conv.conv2d(m, x)
             i += 1
         elif isinstance(m, nn.BatchNorm2d):
-            from . import train_conv
             x = train_conv.bn_eval(m, x)
             i += 1
         else:

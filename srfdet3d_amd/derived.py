@@ -42,6 +42,11 @@ def invalidate(model):
         m.__dict__.pop(_SLOT, None)
 
 
+def foldable_bn(bn, cls):
+    """A `cls` (nn.BatchNorm1d / nn.BatchNorm2d) that is the affine map `fold_bn` folds: eval mode, running statistics, gamma and beta."""
+    return isinstance(bn, cls) and not bn.training and bn.track_running_stats and bn.affine
+
+
 def fold_bn(bn):
     """(scale, shift) of an eval-mode BatchNorm1d / BatchNorm2d: scale = gamma / sqrt(var + eps), shift = beta - mean * scale."""
     def make():

@@ -126,11 +126,11 @@ def _bf16_route(x, conv, out, form):
         why = "not a channel slice of a pixel-major buffer"
     N, H, W, cin = x.shape
     if why is None:
-        if cin % 32:
+        if not ops.gemm_k_ok(cin):
             why = "input channels are no multiple of 32"
         elif x_ld % 4 or x.data_ptr() % 16:
             why = "operand alignment"
-        elif max(x_ld, y_ld) * 512 >= (1 << 31) or (form == "conv" and 4 * H * W * x_ld >= (1 << 31)):
+        elif not ops.gemm_rows_ok(max(x_ld, y_ld)) or (form == "conv" and not ops.below_2gb(H * W, x_ld)):
             why = "beyond the 32-bit ranges"
     if m.routes is not None:
         k, st = conv.kernel_size[0], conv.stride[0]

@@ -1242,9 +1242,24 @@ def pack_wino43_weights(weight):
     return packed
 
 
+def wino43_channels_ok(Cin, Cout):
+    """srf_wino43's channel multiples: 8 input channels per operand chunk (csrc/wino43.hip:461), output quads (:402)."""
+    return Cin % 8 == 0 and Cout % 4 == 0
+
+
+def wino43_range_ok(pixels, ld):
+    """The images one slab of srf_wino43 touches, `pixels` of pitch `ld` floats, inside its 32-bit byte offsets (csrc/wino43.hip:561)."""
+    return 4 * pixels * ld < (1 << 32) - 16
+
+
+def wino43_tiles_ok(N, H, W):
+    """The 4 x 4 output tiles of srf_wino43 inside an int: refused from 2^31 - 64 here, from 2^31 - 32 by the kernel (csrc/wino43.hip:546)."""
+    return N * ((H + 3) // 4) * ((W + 3) // 4) < (1 << 31) - 64
+
+
 def wino43_supported(x, Cout, out=None):
     """Shape / layout limits of srf_wino43 (csrc/wino43.hip: w43_make_args, w43_slab_args)."""
-    if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.shape[3] % 8 == 0 and Cout % 4 == 0
+    if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and wino43_channels_ok(x.shape[3], Cout)
             and x.data_ptr() % 16 == 0):
         return False
     try:
@@ -1256,7 +1271,7 @@ def wino43_supported(x, Cout, out=None):
         return False
     N, H, W, _ = x.shape
     # one slab = the whole layer below 2 GB of V: its images must span less than 4 GB of x and of y
-    return 4 * N * H * W * max(ld, old) < (1 << 32) - 16 and N * ((H + 3) // 4) * ((W + 3) // 4) < (1 << 31) - 64
+    return wino43_range_ok(N * H * W, max(ld, old)) and wino43_tiles_ok(N, H, W)
 
 
 def _aligned16(t):
@@ -1321,6 +1336,21 @@ _GEMM_KINDS = {
                  dtype=torch.int16, plain="srf_conv1x1_nhwc_bf16", topdown="srf_conv1x1_nhwc_bf16_topdown",
                  pooled="srf_conv1x1_nhwc_bf16_pooled", conv="srf_conv_gemm_nhwc_bf16", what="bf16-packed", tag=" bf16"),
 }
+
+
+def gemm_k_ok(K):
+    """Every family reads K in chunks of 32 (csrc/gemm_host.hpp:48, :64)."""
+    return K % 32 == 0
+
+
+def gemm_rows_ok(ld):
+    """128 rows of pitch `ld` floats inside the 2^31-byte descriptor of the direct, split and bf16 families (csrc/gemm_host.hpp:49)."""
+    return ld * 512 < (1 << 31)
+
+
+def below_2gb(pixels, ld):
+    """`pixels` rows of `ld` floats below 2 GB: the implicit-im2col input (csrc/gemm_host.hpp:69), the weight gradient's operands (csrc/wgrad.hip:337)."""
+    return 4 * pixels * ld < (1 << 31)
 
 
 def _pack_gemm(kind, weight):
@@ -1451,7 +1481,7 @@ def conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, out
         raise ValueError("conv1x1_nhwc: out has the wrong shape")
     y_ld = nhwc_ld(out)
     L = _lib.lib()
-    if max(x_ld, y_ld) * 512 >= (1 << 31):     # beyond the 128-row descriptors of the direct and the split family
+    if not gemm_rows_ok(max(x_ld, y_ld)):     # beyond the 128-row descriptors of the direct and the split family
         packed_direct = packed_split = packed_bf16 = None
     kind, k, packed = _choose_gemm("conv1x1_nhwc", "(Cout, K)", N * H * W, Cout, K, packed_weight, packed_direct, packed_split, packed_bf16)
     split, wp = kind == "split", _ptr(packed)
@@ -1729,7 +1759,7 @@ def conv_wgrad_supported(g, x, ksize):
     N, H, W, Cin = x.shape
     Cout = g.shape[3]
     return (ksize in (1, 3) and tuple(g.shape[:3]) == (N, H, W) and W >= 32 and Cin % 4 == 0 and Cout % 4 == 0 and g_ld % 4 == 0
-            and x_ld % 4 == 0 and g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and N * H * W * max(g_ld, x_ld) * 4 < (1 << 31))
+            and x_ld % 4 == 0 and g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and below_2gb(N * H * W, max(g_ld, x_ld)))
 
 
 def conv_wgrad_nhwc(g, x, ksize):
@@ -1755,7 +1785,7 @@ def conv_gemm_nhwc_supported(x):
         ld = nhwc_ld(x)
     except RuntimeError:
         return False
-    return x.shape[3] % 32 == 0 and ld % 4 == 0 and x.data_ptr() % 16 == 0 and 4 * x.shape[1] * x.shape[2] * ld < (1 << 31)
+    return gemm_k_ok(x.shape[3]) and ld % 4 == 0 and x.data_ptr() % 16 == 0 and below_2gb(x.shape[1] * x.shape[2], ld)
 
 
 # ---- modulated deformable convolution, DCNv2 (csrc/dcn.hip) ------------------------------------------------------------

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import nhwc, ops
+from .. import nhwc, ops, train_conv
 from ..compat.cnn import BaseModule, ConvModule, ModuleList, build_activation_layer, build_conv_layer
 from ..compat.registry import HEADS, LOSSES, BBOX_ASSIGNERS, build_head, build_roi_extractor
 from ..dense import _foldable, fusable, linear_graph_safe
@@ -648,7 +648,6 @@ class SRFDetHead(BaseModule):
             if nhwc.enabled() and fusable(f4) and nhwc.is_channels_last(f4) and nhwc.wino_ok(conv, C):
                 g = nhwc.nchw_view(nhwc.conv3x3(nhwc.nhwc_view(f4), conv))  # Winograd on the f32 MFMA, bias in the epilogue
             else:
-                from .. import train_conv
                 g = train_conv.conv2d(conv, f4)     # training: srf_wino43 forward + data gradient; else conv(f4)
             out[i] = g.reshape(bs, n_cam, *g.shape[1:])
         return out

@@ -18,7 +18,7 @@ from torch.nn.modules.batchnorm import _BatchNorm
 
 from ..compat.cnn import BaseModule
 from ..compat.registry import BACKBONES
-from .. import ops
+from .. import ops, train_conv
 from ..dense import conv1x1_cat_bn_act, fusable, run_sequential
 
 # name: (stem widths, per-stage conv width, per-stage output width, layers per block, blocks per stage, depthwise)
@@ -51,7 +51,6 @@ class eSEModule(nn.Module):
         self.fc = nn.Conv2d(channel, channel, kernel_size=1)
 
     def forward(self, x, identity=None):
-        from .. import train_conv
         if train_conv.ese_eligible(self, x, identity):
             return train_conv.ese_apply(self, x, identity)     # training on channels-last tensors: one autograd node
         if fusable(x) and x.shape[0] <= 8 and x.shape[1] % 4 == 0:
@@ -85,7 +84,6 @@ class OSAModule(nn.Module):
         self.ese = eSEModule(cout)
 
     def forward(self, x):
-        from .. import train_conv
         if train_conv.enabled() and train_conv.osa_eligible(self, x):
             # training behind the frozen prefix: layers + concat convolution as one autograd node over one channels-last buffer
             return self.ese(train_conv.osa_chain(self, x), x if self.identity else None)
@@ -173,7 +171,6 @@ class VoVNet(BaseModule):
             if not nhwc.vovnet_supported(self, x):
                 return None
             part, cur = nhwc.vovnet_forward(self, x, upto=last)
-            from .. import train_conv
             keep_cl = train_conv.enabled()       # the trainable remainder runs channels-last (train_conv.py): no copy at all
             for k, v in part.items():
                 out[k] = v if keep_cl else v.contiguous()   # else NCHW for the module path on MIOpen

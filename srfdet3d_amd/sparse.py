@@ -109,7 +109,7 @@ _fold_bn = derived.fold_bn   # the name tests/test_host_modules.py takes the fol
 
 
 def _bn_foldable(bn):
-    return isinstance(bn, nn.BatchNorm1d) and not bn.training and bn.track_running_stats and bn.affine
+    return derived.foldable_bn(bn, nn.BatchNorm1d)
 
 
 class SparseModule(nn.Module):

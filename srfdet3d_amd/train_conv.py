@@ -15,18 +15,36 @@ in NCHW <-> NHWC transposes for the weight gradient.  Here
 
 Tensors stay logical NCHW with channels_last strides, which every torch op of the module path preserves (BatchNorm in eval
 mode -- `norm_eval=True` -- ReLU, cat, max_pool2d, nearest interpolate), so nothing is copied between the layers.
-SRF_TRAIN_CONV=0 switches back to torch's convolution (A/B switch for tests and benchmarks).
 """
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 from torch import nn
 
-from . import ops
+from . import derived, ops
+
+# The SRF_TRAIN_* switches: A/B switches for tests and benchmarks, "1" when unset, read on every call (tests flip them mid-process).
+_SWITCHES = {
+    "CONV": "0: no route of this file is taken -- every layer runs as torch's own module",
+    "FUSED": "0: conv -> eval BatchNorm -> ReLU as three autograd nodes (`conv2d`, `bn_eval`, relu), not `_ConvAffineRelu` / `_OSAChain`",
+    "OSA": "0: the layers of an OSA block as `_ConvAffineRelu` nodes, not one `_OSAChain`",
+    "ESE": "0: the eSE module as torch ops, not `_ESEApply`",
+    "CONV1X1": "0: the bias-carrying 1x1 layers as torch's `linear` on the pixel view, not `_Conv1x1`",
+    "WGRAD": "0: weight gradients on the library route (aten.convolution_backward, one GEMM for 1x1), not `srf_conv_wgrad_nhwc`; "
+             "2: on `srf_conv_wgrad_nhwc` whatever share of its tiles a layer fills",
+}
+# SRF_TRAIN_CONV_DEBUG (read once, at import): (input shape, Cout, events) of every weight-gradient call, for `debug_report`
+_DEBUG = [] if os.environ.get("SRF_TRAIN_CONV_DEBUG") else None
 
 
-_DEBUG = [] if os.environ.get("SRF_TRAIN_CONV_DEBUG") else None   # developer: (input shape, Cout, events) of every weight-gradient call
+def switch(name, _env={k: "SRF_TRAIN_" + k for k in _SWITCHES}):
+    return os.environ.get(_env[name], "1")   # KeyError: not a switch of this file
+
+
+def enabled():
+    return switch("CONV") != "0"
 
 
 def debug_report():
@@ -39,8 +57,79 @@ def debug_report():
     return sorted(((k, n, ms / n) for k, (n, ms) in rows.items()), key=lambda t: -t[2] * t[1])
 
 
-def enabled():
-    return os.environ.get("SRF_TRAIN_CONV", "1") != "0"
+# ---- the gate --------------------------------------------------------------------------------------------------------
+# "This tensor trains on the library's kernels": autograd is recording and x is an f32 GPU tensor -- plus, per route, the switches that
+# must be on and what else the route asks of x.  The differences are as they grew; each is pinned by tests/test_gpu_train_gate.py.
+_Route = namedtuple("_Route", "switches no_autocast dim4 channels_last")
+_ROUTES = {
+    "wino43":    _Route(("CONV",),        True,  True,  False),   # `eligible`: NCHW tensors too (`_Wino43Conv` keeps the caller's format)
+    "conv1x1":   _Route(("CONV",),        True,  True,  True),    # `eligible_1x1`
+    "depthwise": _Route(("CONV",),        False, True,  False),   # `eligible_depthwise`: does not look at autocast
+    "fused":     _Route(("CONV",),        True,  True,  True),    # `fused_eligible` (its caller consults FUSED: the "dense" row)
+    "osa":       _Route(("OSA", "FUSED"), True,  True,  True),    # `osa_eligible`: CONV is left to its caller
+    "ese":       _Route(("CONV", "ESE"),  True,  True,  True),    # `ese_eligible`
+    "bn_eval":   _Route(("CONV",),        True,  False, False),   # `bn_eval`: does not look at dim()
+    "dense":     _Route(("FUSED",),       True,  False, False),   # `dense._train_fusable`: FUSED but not CONV
+}
+
+
+def trains(route, x):
+    switches, no_autocast, dim4, channels_last = _ROUTES[route]
+    for s in switches:
+        if switch(s) == "0":
+            return False
+    return (torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and (not dim4 or x.dim() == 4)
+            and (not channels_last or x.stride(1) == 1) and (not no_autocast or not torch.is_autocast_enabled()))
+
+
+def _plain_conv(conv, k):
+    """nn.Conv2d itself, k x k / stride 1 / padding k // 2, dense."""
+    return (type(conv) is nn.Conv2d and conv.kernel_size == (k, k) and conv.stride == (1, 1) and conv.padding == (k // 2, k // 2)
+            and conv.dilation == (1, 1) and conv.groups == 1)
+
+
+# ---- shape limits of a layer, as functions of integers (the kernels' own limits: ops.py) ------------------------------------------
+MAX_COUT = 1024   # channels of one block of srf_nhwc_affine_relu_bwd's column sums (csrc/nhwc.hip:592); `_Conv1x1` keeps the same bound
+
+
+def wino_layer_ok(N, H, W, Cin, Cout):
+    """A 3x3 layer on srf_wino43 forward (Cin -> Cout) and backward (Cout -> Cin: Cout % 8 too); below 32 input channels it stays on torch."""
+    return ops.wino43_channels_ok(Cin, Cout) and Cout % 8 == 0 and Cin >= 32 and ops.wino43_range_ok(N * H * W, max(Cin, Cout))
+
+
+def gemm_layer_ok(N, H, W, Cin, Cout):
+    """A 1x1 layer on the library's GEMMs in three directions: K = Cin forward, K = Cout backward, both tensors in the weight gradient's range."""
+    return (ops.gemm_k_ok(Cin) and ops.gemm_k_ok(Cout) and Cout <= MAX_COUT and H * W > 1 and ops.below_2gb(N * H * W, max(Cin, Cout)))
+
+
+def fused_layer_ok(k, N, H, W, Cin, Cout):
+    """conv k x k -> eval BatchNorm -> ReLU as a layer of `_ConvAffineRelu` or `_OSAChain`."""
+    if k == 3:
+        return wino_layer_ok(N, H, W, Cin, Cout) and Cout <= MAX_COUT and ops.wino43_tiles_ok(N, H, W)
+    return k == 1 and gemm_layer_ok(N, H, W, Cin, Cout)
+
+
+# ---- one layer in its three directions ---------------------------------------------------------------------------------
+def _nhwc(t):
+    """logical NCHW tensor -> its (N, H, W, C) view over channels-last storage (a copy only if it was not channels-last)."""
+    return t.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+
+
+def _layer_fwd(xn, w, scale=None, shift=None, relu=False, out=None):
+    """A layer on the channels-last slice xn: w (Cout, Cin, 3, 3) on `srf_wino43`, (Cout, Cin[, 1, 1]) on the 1x1 GEMM; packed once per call."""
+    Cout = w.shape[0]
+    if w.dim() == 4 and w.shape[2] == 3:
+        return ops.wino43(xn, ops.pack_wino43_weights(w), Cout, scale, shift, relu, out=out)
+    w2 = w.reshape(Cout, -1)
+    return ops.conv1x1_nhwc(xn, lambda: ops.pack_conv1x1_nhwc_weights(w2), Cout, scale, shift, relu, out=out,
+                            packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w2))
+
+
+def _layer_dgrad(gn, w):
+    """Its data gradient: the same kernels on the weight rotated by 180 degrees with the channel axes swapped (3x3), transposed (1x1)."""
+    if w.shape[2] == 3:
+        return _layer_fwd(gn, w.flip(2, 3).transpose(0, 1).contiguous())      # (Cin, Cout, 3, 3)
+    return _layer_fwd(gn, w.reshape(w.shape[0], w.shape[1]).t().contiguous())  # (Cin, Cout)
 
 
 def _weight_grad(gn, xn, weight, k):
@@ -49,41 +138,47 @@ def _weight_grad(gn, xn, weight, k):
     added in a fixed order -- deterministic) where it applies; else (SRF_TRAIN_WGRAD=0, maps narrower than 32 pixels, tensors of 2 GB)
     the library route of rounds 3-4: aten.convolution_backward = MIOpen's float-atomic split-K kernels for 3x3, one rocBLAS GEMM for 1x1."""
     Co, Ci = weight.shape[0], weight.shape[1]
-    cols = k * k * Ci if (k > 1 and Ci % 32 == 0) else None            # 3x3 layers: the column tiles run over the flattened (tap, channel) axis
-    fill = ((Co * cols) / float(((Co + 127) // 128) * ((cols + 127) // 128) * 128 * 128) if cols is not None
-            else (Co * Ci) / float(((Co + 127) // 128) * ((Ci + 127) // 128) * 128 * 128))   # share of the kernel's 128 x 128 tiles that is real
+    if _DEBUG is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    cols = k * k * Ci if (k > 1 and Ci % 32 == 0) else Ci            # 3x3 layers: the column tiles run over the flattened (tap, channel) axis
+    fill = (Co * cols) / float(((Co + 127) // 128) * ((cols + 127) // 128) * 128 * 128)   # share of the kernel's 128 x 128 tiles that is real
     # (192 -> 192, VoVNet stage 4, with every tap's channels in tiles of their own: 56 % -- 543 us against MIOpen's 465; flattened: 72 %;
     # every other trainable shape of config 4 is 1.1-3x faster on the kernel: profiles/r05_wgrad_bench.txt)
-    want = os.environ.get("SRF_TRAIN_WGRAD", "1")
+    want = switch("WGRAD")
     if want != "0" and (fill >= 0.6 or k == 1 or want == "2") and ops.conv_wgrad_supported(gn, xn, k):
-        return ops.conv_wgrad_nhwc(gn, xn, k)
-    Cout, Cin = weight.shape[0], weight.shape[1]
-    if k == 1:
-        return (gn.reshape(-1, Cout).t() @ xn.reshape(-1, Cin)).view(Cout, Cin, 1, 1)
-    return torch.ops.aten.convolution_backward(gn.permute(0, 3, 1, 2), xn.permute(0, 3, 1, 2), weight, None, (1, 1), (1, 1), (1, 1), False,
-                                               (0, 0), 1, (False, True, False))[1]
+        gw = ops.conv_wgrad_nhwc(gn, xn, k)
+    elif k == 1:
+        gw = (gn.reshape(-1, Co).t() @ xn.reshape(-1, Ci)).view(Co, Ci, 1, 1)
+    else:
+        gw = torch.ops.aten.convolution_backward(gn.permute(0, 3, 1, 2), xn.permute(0, 3, 1, 2), weight, None, (1, 1), (1, 1), (1, 1), False,
+                                                 (0, 0), 1, (False, True, False))[1]
+    if _DEBUG is not None:
+        e1.record()
+        _DEBUG.append(((xn.shape[0], Ci, xn.shape[1], xn.shape[2]), Co, e0, e1))
+    return gw
 
 
+def _bn_relu_bwd(gyn, yn, fold, mean, relu, need_gamma, need_beta, gy2=None):
+    """The head of a fused layer's backward pass: `srf_nhwc_affine_relu_bwd` (ReLU mask, scale and the two column sums; gy2 is a second
+    gradient of the same output, added on the way in), then d gamma / d beta where asked -> gz, sums, d gamma, d beta.
+    u = (z - mean) inv gamma + beta:  d gamma = inv (sum gu z - mean sum gu),  sum gu z = (sum gu y - t0 sum gu) / s;  d beta = sum gu."""
+    gz, sums = ops.nhwc_affine_relu_bwd(gyn, yn, fold[0], relu, gy2=gy2)
+    pg = ops.bn_eval_grads(sums, fold, mean) if (need_gamma or need_beta) else None
+    return gz, sums, pg[0] if need_gamma else None, pg[1] if need_beta else None
+
+
+# ---- the nodes -------------------------------------------------------------------------------------------------------
 def eligible(conv, x):
     """A trainable (or gradient-carrying) 3x3 / stride 1 / padding 1 convolution on an fp32 GPU tensor under autograd."""
-    return (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and not torch.is_autocast_enabled() and type(conv) is nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
-            and conv.in_channels % 8 == 0 and conv.out_channels % 8 == 0 and conv.in_channels >= 32
-            and (x.requires_grad or conv.weight.requires_grad) and x.shape[0] * x.shape[2] * x.shape[3] * max(conv.in_channels, conv.out_channels) * 4 < (1 << 32) - 16)
-
-
-def _nhwc(t):
-    """logical NCHW tensor -> its (N, H, W, C) view over channels-last storage (a copy only if it was not channels-last)."""
-    return t.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+    return (trains("wino43", x) and _plain_conv(conv, 3) and conv.padding_mode == "zeros" and (x.requires_grad or conv.weight.requires_grad)
+            and wino_layer_ok(x.shape[0], x.shape[2], x.shape[3], conv.in_channels, conv.out_channels))
 
 
 class _Wino43Conv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
-        xn = _nhwc(x)
-        Cout = weight.shape[0]
-        y = ops.wino43(xn, ops.pack_wino43_weights(weight.detach()), Cout, None, None if bias is None else bias.detach(), False)
+        y = _layer_fwd(_nhwc(x), weight.detach(), None, None if bias is None else bias.detach(), False)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.keep_cl = x.stride(1) == 1
@@ -102,19 +197,11 @@ class _Wino43Conv(torch.autograd.Function):
         gy_cl = gyn.permute(0, 3, 1, 2)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            w_t = weight.detach().flip(2, 3).transpose(0, 1).contiguous()          # (Cin, Cout, 3, 3), rotated by 180 degrees
-            gx = ops.wino43(gyn, ops.pack_wino43_weights(w_t), weight.shape[1]).permute(0, 3, 1, 2)
+            gx = _layer_dgrad(gyn, weight.detach()).permute(0, 3, 1, 2)
             if not ctx.keep_cl:
                 gx = gx.contiguous()
         if ctx.needs_input_grad[1]:
-            dbg = _DEBUG is not None
-            if dbg:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
             gw = _weight_grad(gyn, _nhwc(x), weight, 3)
-            if dbg:
-                e1.record()
-                _DEBUG.append((tuple(x.shape), weight.shape[0], e0, e1))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gy_cl.sum(dim=(0, 2, 3))
         return gx, gw, gb
@@ -133,59 +220,37 @@ class _ConvAffineRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, mean, var, eps, relu):
         xn = _nhwc(x)
-        Cout, Cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
         fold = ops.bn_eval_fold(gamma.detach(), beta.detach(), mean, var, eps)     # s, t0, inv in one launch
         s, t0 = fold[0], fold[1]
         t = t0 if bias is None else t0 + bias.detach() * s
-        w = weight.detach()
-        if k == 3:
-            yn = ops.wino43(xn, ops.pack_wino43_weights(w), Cout, s, t, relu)
-        else:
-            w2 = w.reshape(Cout, Cin)
-            yn = ops.conv1x1_nhwc(xn, lambda: ops.pack_conv1x1_nhwc_weights(w2), Cout, s, t, relu,
-                                  packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w2))
+        yn = _layer_fwd(xn, weight.detach(), s, t, relu)
         ctx.save_for_backward(x, weight, yn, fold, mean)
-        ctx.relu, ctx.has_bias, ctx.k = bool(relu), bias is not None, k
+        ctx.relu, ctx.has_bias = bool(relu), bias is not None
         return yn.permute(0, 3, 1, 2)          # logical NCHW, channels-last strides
 
     @staticmethod
     def backward(ctx, gy):
         x, weight, yn, fold, mean = ctx.saved_tensors
-        s = fold[0]
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        gz, sums = ops.nhwc_affine_relu_bwd(_nhwc(gy), yn, s, ctx.relu)
         need = ctx.needs_input_grad
-        gx = gw = gb = ggamma = gbeta = None
-        if need[3] or need[4]:
-            # u = (z - mean) inv gamma + beta:  d gamma = inv (sum gu z - mean sum gu),  sum gu z = (sum gu y - t0 sum gu) / s;  d beta = sum gu
-            pg = ops.bn_eval_grads(sums, fold, mean)
-            ggamma = pg[0] if need[3] else None
-            gbeta = pg[1] if need[4] else None
+        gz, sums, ggamma, gbeta = _bn_relu_bwd(_nhwc(gy), yn, fold, mean, ctx.relu, need[3], need[4])
+        gx = gw = gb = None
         if ctx.has_bias and need[2]:
-            gb = sums[0] * s
-        w = weight.detach()
+            gb = sums[0] * fold[0]
         if need[0]:
-            if ctx.k == 3:
-                w_t = w.flip(2, 3).transpose(0, 1).contiguous()           # (Cin, Cout, 3, 3), rotated by 180 degrees
-                gx = ops.wino43(gz, ops.pack_wino43_weights(w_t), Cin).permute(0, 3, 1, 2)
-            else:
-                w_t = w.reshape(Cout, Cin).t().contiguous()              # (Cin, Cout): dx = gz W
-                gx = ops.conv1x1_nhwc(gz, lambda: ops.pack_conv1x1_nhwc_weights(w_t), Cin,
-                                      packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w_t)).permute(0, 3, 1, 2)
+            gx = _layer_dgrad(gz, weight.detach()).permute(0, 3, 1, 2)
         if need[1]:
-            gw = _weight_grad(gz, _nhwc(x), weight, ctx.k)
+            gw = _weight_grad(gz, _nhwc(x), weight, weight.shape[2])
         return gx, gw, gb, ggamma, gbeta, None, None, None, None
 
 
 def fused_eligible(conv, bn, x):
     """conv -> eval-mode BatchNorm2d (-> ReLU) under autograd on a channels-last tensor, in the shapes `_ConvAffineRelu` covers."""
-    if not (isinstance(bn, nn.BatchNorm2d) and not bn.training and bn.track_running_stats and bn.affine and x.dim() == 4 and x.is_cuda
-            and x.stride(1) == 1 and conv.out_channels % 4 == 0 and conv.out_channels <= 1024):
+    if not (trains("fused", x) and derived.foldable_bn(bn, nn.BatchNorm2d)):
         return False
+    N, _, H, W = x.shape
     if eligible(conv, x):
-        return ops.wino43_supported(x.permute(0, 2, 3, 1), conv.out_channels)
-    return (eligible_1x1(conv, x) and conv.in_channels % 32 == 0 and conv.out_channels % 32 == 0
-            and x.shape[0] * x.shape[2] * x.shape[3] * max(conv.in_channels, conv.out_channels) * 512 < (1 << 31) * 128)
+        return fused_layer_ok(3, N, H, W, conv.in_channels, conv.out_channels) and ops.wino43_supported(x.permute(0, 2, 3, 1), conv.out_channels)
+    return eligible_1x1(conv, x) and fused_layer_ok(1, N, H, W, conv.in_channels, conv.out_channels)
 
 
 GAMMA_GUARD_RATIO = 1e-3   # min |s| / max |s| of a layer below which `_ConvAffineRelu` is not used (s = gamma / sqrt(var + eps))
@@ -230,6 +295,17 @@ def conv_bn_act(conv, bn, relu, x):
     return None
 
 
+# What `_OSAChain` takes per layer behind (x, eps), in this order: `osa_chain` packs it, the node unpacks its arguments, their need flags
+# and its gradients by it.
+_OSALayer = namedtuple("_OSALayer", "weight gamma beta mean var")
+_OSASaved = namedtuple("_OSASaved", "weight mean fold")   # what it saves per layer behind (cat, yc); fold = (3, C): s, t0, inv
+
+
+def _records(flat, cls):
+    n = len(cls._fields)
+    return [cls(*flat[i:i + n]) for i in range(0, len(flat), n)]
+
+
 class _OSAChain(torch.autograd.Function):
     """The body of a VoVNet OSA block (vovnet.py:208-230) -- L x [conv 3x3 -> eval BatchNorm -> ReLU] in a chain, then the 1x1 `concat`
     convolution over [x, y_0 .. y_{L-1}] -> eval BatchNorm -> ReLU -- as ONE autograd node over ONE channels-last buffer
@@ -247,83 +323,61 @@ class _OSAChain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, eps, *params):
-        L = len(params) // 5 - 1
+        layers = _records(params, _OSALayer)       # L chain layers, then the concat convolution
+        L = len(layers) - 1
         xn = _nhwc(x)
         N, H, W, Cin = xn.shape
-        ws = [params[5 * i] for i in range(L + 1)]
-        widths = [int(w.shape[0]) for w in ws[:L]]
+        widths = [int(p.weight.shape[0]) for p in layers[:L]]
         Ctot = Cin + sum(widths)
         cat = torch.empty((N, H, W, Ctot), dtype=torch.float32, device=x.device)
         cat[..., :Cin].copy_(xn)
-        aff = []
+        saved = []
         lo, hi = 0, Cin            # the input slice of the next layer
-        for i in range(L):
-            w, gamma, beta, mean, var = params[5 * i:5 * i + 5]
-            fold = ops.bn_eval_fold(gamma.detach(), beta.detach(), mean, var, eps[i])
-            ops.wino43(cat[..., lo:hi], ops.pack_wino43_weights(w.detach()), widths[i], fold[0], fold[1], True, out=cat[..., hi:hi + widths[i]])
-            aff.append(fold)
-            lo, hi = hi, hi + widths[i]
-            if i == 0:
-                lo = Cin
-        wc, gamma, beta, mean, var = params[5 * L:5 * L + 5]
-        Cout = int(wc.shape[0])
-        fold = ops.bn_eval_fold(gamma.detach(), beta.detach(), mean, var, eps[L])
-        w2 = wc.detach().reshape(Cout, Ctot)
-        yc = ops.conv1x1_nhwc(cat, lambda: ops.pack_conv1x1_nhwc_weights(w2), Cout, fold[0], fold[1], True,
-                              packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w2))
-        aff.append(fold)
-        ctx.save_for_backward(cat, yc, *ws, *[params[5 * i + 3] for i in range(L + 1)], *aff)
-        ctx.L, ctx.Cin, ctx.widths = L, Cin, widths
+        for i, p in enumerate(layers):
+            fold = ops.bn_eval_fold(p.gamma.detach(), p.beta.detach(), p.mean, p.var, eps[i])
+            if i < L:
+                _layer_fwd(cat[..., lo:hi], p.weight.detach(), fold[0], fold[1], True, out=cat[..., hi:hi + widths[i]])
+                lo, hi = hi, hi + widths[i]
+            else:
+                yc = _layer_fwd(cat, p.weight.detach(), fold[0], fold[1], True)
+            saved += [p.weight, p.mean, fold]
+        ctx.save_for_backward(cat, yc, *saved)
+        ctx.Cin, ctx.widths = Cin, widths
         return yc.permute(0, 3, 1, 2)          # logical NCHW, channels-last strides
 
     @staticmethod
     def backward(ctx, gy):
-        L, Cin, widths = ctx.L, ctx.Cin, ctx.widths
-        sv = ctx.saved_tensors
-        cat, yc = sv[0], sv[1]
-        ws, means, aff = sv[2:3 + L], sv[3 + L:4 + 2 * L], sv[4 + 2 * L:]      # aff[i] = (3, C): s, t0, inv of layer i
-        need = ctx.needs_input_grad            # x, eps, then 5 per layer: weight, gamma, beta, mean, var
-        grads = [None] * (2 + 5 * (L + 1))
-
-        def affine_grads(i, sums):
-            if need[2 + 5 * i + 1] or need[2 + 5 * i + 2]:
-                pg = ops.bn_eval_grads(sums, aff[i], means[i])
-                if need[2 + 5 * i + 1]:
-                    grads[2 + 5 * i + 1] = pg[0]
-                if need[2 + 5 * i + 2]:
-                    grads[2 + 5 * i + 2] = pg[1]
+        Cin, widths = ctx.Cin, ctx.widths
+        L = len(widths)
+        cat, yc = ctx.saved_tensors[:2]
+        layers = _records(ctx.saved_tensors[2:], _OSASaved)
+        need_x = ctx.needs_input_grad[0]
+        need = _records(ctx.needs_input_grad[2:], _OSALayer)
+        grads = [[None] * len(_OSALayer._fields) for _ in layers]     # d weight, d gamma, d beta, -, - of every layer
 
         # the concat convolution
         Ctot = cat.shape[3]
-        wc = ws[L].detach()
-        Cout = wc.shape[0]
-        gz, sums = ops.nhwc_affine_relu_bwd(_nhwc(gy), yc, aff[L][0], True)
-        affine_grads(L, sums)
-        w_t = wc.reshape(Cout, Ctot).t().contiguous()
-        g_cat = ops.conv1x1_nhwc(gz, lambda: ops.pack_conv1x1_nhwc_weights(w_t), Ctot,
-                                 packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w_t))
-        if need[2 + 5 * L]:
-            grads[2 + 5 * L] = _weight_grad(gz, cat, ws[L], 1)
+        p = layers[L]
+        gz, _, grads[L][1], grads[L][2] = _bn_relu_bwd(_nhwc(gy), yc, p.fold, p.mean, True, need[L].gamma, need[L].beta)
+        g_cat = _layer_dgrad(gz, p.weight.detach())
+        if need[L].weight:
+            grads[L][0] = _weight_grad(gz, cat, p.weight, 1)
         del gz
         # the chain, last layer first
         carry = None
         out_hi = Ctot
         for i in range(L - 1, -1, -1):
+            p = layers[i]
             out_lo = out_hi - widths[i]
             in_lo, in_hi = (0, Cin) if i == 0 else (out_lo - widths[i - 1], out_lo)
-            gz, sums = ops.nhwc_affine_relu_bwd(g_cat[..., out_lo:out_hi], cat[..., out_lo:out_hi], aff[i][0], True, gy2=carry)
-            affine_grads(i, sums)
-            w = ws[i].detach()
-            if need[2 + 5 * i]:
-                grads[2 + 5 * i] = _weight_grad(gz, cat[..., in_lo:in_hi], ws[i], 3)
-            carry = None
-            if i > 0 or need[0]:
-                w_r = w.flip(2, 3).transpose(0, 1).contiguous()           # (Cin, Cout, 3, 3), rotated by 180 degrees
-                carry = ops.wino43(gz, ops.pack_wino43_weights(w_r), in_hi - in_lo)
+            gz, _, grads[i][1], grads[i][2] = _bn_relu_bwd(g_cat[..., out_lo:out_hi], cat[..., out_lo:out_hi], p.fold, p.mean, True,
+                                                           need[i].gamma, need[i].beta, gy2=carry)
+            if need[i].weight:
+                grads[i][0] = _weight_grad(gz, cat[..., in_lo:in_hi], p.weight, 3)
+            carry = _layer_dgrad(gz, p.weight.detach()) if (i > 0 or need_x) else None
             out_hi = out_lo
-        if need[0]:
-            grads[0] = carry.add_(g_cat[..., :Cin]).permute(0, 3, 1, 2)
-        return tuple(grads)
+        gx = carry.add_(g_cat[..., :Cin]).permute(0, 3, 1, 2) if need_x else None
+        return (gx, None, *[g for rec in grads for g in rec])
 
 
 class _ESEApply(torch.autograd.Function):
@@ -367,10 +421,8 @@ class _ESEApply(torch.autograd.Function):
 
 def ese_eligible(mod, x, identity):
     """The eSE module under autograd on a channels-last f32 GPU tensor (SRF_TRAIN_ESE=0: the torch ops)."""
-    C = x.shape[1] if x.dim() == 4 else 0
-    return (enabled() and os.environ.get("SRF_TRAIN_ESE", "1") != "0" and torch.is_grad_enabled() and x.dim() == 4 and x.is_cuda
-            and x.dtype == torch.float32 and x.stride(1) == 1 and not torch.is_autocast_enabled() and C % 4 == 0 and 0 < C <= 1024
-            and x.shape[0] <= 65535 and (x.requires_grad or mod.fc.weight.requires_grad)
+    return (trains("ese", x) and x.shape[1] % 4 == 0 and 0 < x.shape[1] <= 1024 and x.shape[0] <= 65535
+            and (x.requires_grad or mod.fc.weight.requires_grad)
             and (identity is None or (tuple(identity.shape) == tuple(x.shape) and identity.stride(1) == 1))
             and type(mod.fc) is nn.Conv2d and mod.fc.kernel_size == (1, 1) and mod.fc.bias is not None)
 
@@ -381,54 +433,36 @@ def ese_apply(mod, x, identity):
 
 def osa_eligible(block, x):
     """An OSA block whose body can run as `_OSAChain`: plain 3x3 layers (no reduction / depthwise form), every layer and the concat
-    convolution fit `_ConvAffineRelu`'s conditions (bias-free convolutions, eval-mode BatchNorms with well-conditioned gammas), and
-    the input is channels-last under autograd.  SRF_TRAIN_OSA=0 keeps the per-layer nodes."""
-    if os.environ.get("SRF_TRAIN_OSA", "1") == "0" or os.environ.get("SRF_TRAIN_FUSED", "1") == "0" or block.reduce is not None:
-        return False
-    if not (torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.stride(1) == 1 and len(block.layers) >= 1):
-        return False
-    if torch.is_autocast_enabled():
+    convolution fit `_ConvAffineRelu`'s conditions (`fused_layer_ok`) with bias-free convolutions and eval-mode BatchNorms with
+    well-conditioned gammas, and the input is channels-last under autograd.  SRF_TRAIN_OSA=0 keeps the per-layer nodes."""
+    if not (trains("osa", x) and block.reduce is None and len(block.layers) >= 1):
         return False
     N, _, H, W = x.shape
     seqs = list(block.layers) + [block.concat]
-    cin = x.shape[1]
-    ctot = cin
-    for j, seq in enumerate(seqs):
+    cin = ctot = x.shape[1]            # the running width of the chain, the width of `cat`
+    for seq in seqs:
         mods = list(seq.children())
         if len(mods) != 3 or type(mods[0]) is not nn.Conv2d or not isinstance(mods[2], nn.ReLU) or mods[0].bias is not None:
             return False
         conv, bn = mods[0], mods[1]
-        if not (isinstance(bn, nn.BatchNorm2d) and not bn.training and bn.track_running_stats and bn.affine):
+        k, width = (1, ctot) if seq is seqs[-1] else (3, cin)
+        if not (derived.foldable_bn(bn, nn.BatchNorm2d) and _plain_conv(conv, k) and conv.padding_mode == "zeros" and conv.in_channels == width
+                and fused_layer_ok(k, N, H, W, width, conv.out_channels)):
             return False
-        if conv.dilation != (1, 1) or conv.groups != 1 or conv.stride != (1, 1) or conv.padding_mode != "zeros":
-            return False
-        last = j == len(seqs) - 1
-        if not last:
-            if not (conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.in_channels == cin and cin % 8 == 0 and cin >= 32
-                    and conv.out_channels % 8 == 0 and conv.out_channels <= 1024):
-                return False
+        if k == 3:
             cin = conv.out_channels
             ctot += cin
-        elif not (conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.in_channels == ctot and ctot % 32 == 0
-                  and conv.out_channels % 32 == 0 and conv.out_channels <= 1024 and H * W > 1):
-            return False
         if bn.weight.requires_grad and not gamma_well_conditioned(bn):
             return False
     if not (x.requires_grad or any(p.requires_grad for seq in seqs for p in seq.parameters())):
         return False
-    if N * H * W * ctot * 4 >= (1 << 31) or N * H * W * max(ctot, seqs[-1][0].out_channels) * 512 >= (1 << 31) * 128:
-        return False
-    return N * ((H + 3) // 4) * ((W + 3) // 4) < (1 << 31) - 64   # (the Winograd kernel's tile count)
+    return ops.below_2gb(N * H * W, ctot)   # `cat` and the concat convolution's data gradient feed the weight gradients
 
 
 def osa_chain(block, x):
     seqs = list(block.layers) + [block.concat]
-    params, eps = [], []
-    for seq in seqs:
-        conv, bn = seq[0], seq[1]
-        params += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        eps.append(float(bn.eps))
-    return _OSAChain.apply(x, tuple(eps), *params)
+    layers = [_OSALayer(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var) for conv, bn, _ in seqs]
+    return _OSAChain.apply(x, tuple(float(seq[1].eps) for seq in seqs), *[t for p in layers for t in p])
 
 
 class _DepthwiseNative(torch.autograd.Function):
@@ -456,17 +490,13 @@ class _DepthwiseNative(torch.autograd.Function):
 
 
 def eligible_depthwise(conv, x):
-    return (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and type(conv) is nn.Conv2d
-            and conv.groups > 1 and conv.groups == conv.in_channels == conv.out_channels and conv.dilation == (1, 1)
-            and conv.padding_mode == "zeros" and (x.requires_grad or conv.weight.requires_grad))
+    return (trains("depthwise", x) and type(conv) is nn.Conv2d and conv.groups > 1 and conv.groups == conv.in_channels == conv.out_channels
+            and conv.dilation == (1, 1) and conv.padding_mode == "zeros" and (x.requires_grad or conv.weight.requires_grad))
 
 
 def eligible_1x1(conv, x):
     # only for tensors that ARE channels-last already: an NCHW pipeline keeps torch's convolution (and its memory format)
-    return (enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.stride(1) == 1
-            and not torch.is_autocast_enabled() and type(conv) is nn.Conv2d and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-            and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and x.shape[2] * x.shape[3] > 1
-            and (x.requires_grad or conv.weight.requires_grad))
+    return (trains("conv1x1", x) and _plain_conv(conv, 1) and x.shape[2] * x.shape[3] > 1 and (x.requires_grad or conv.weight.requires_grad))
 
 
 def conv2d(conv, x):
@@ -479,8 +509,7 @@ def conv2d(conv, x):
     if eligible_depthwise(conv, x):
         return _DepthwiseNative.apply(x.contiguous(), conv.weight, conv.bias, conv.stride, conv.padding, conv.groups)
     if eligible_1x1(conv, x):
-        if (os.environ.get("SRF_TRAIN_CONV1X1", "1") != "0" and conv.in_channels % 32 == 0 and conv.out_channels % 32 == 0
-                and conv.out_channels <= 1024 and x.shape[0] * x.shape[2] * x.shape[3] * max(conv.in_channels, conv.out_channels) * 512 < (1 << 31) * 128):
+        if switch("CONV1X1") != "0" and gemm_layer_ok(x.shape[0], x.shape[2], x.shape[3], conv.in_channels, conv.out_channels):
             return _Conv1x1.apply(x, conv.weight, conv.bias)
         xn = _nhwc(x)
         N, H, W, C = xn.shape
@@ -496,11 +525,7 @@ class _Conv1x1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        xn = _nhwc(x)
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        w2 = weight.detach().reshape(Cout, Cin)
-        yn = ops.conv1x1_nhwc(xn, lambda: ops.pack_conv1x1_nhwc_weights(w2), Cout, None, None if bias is None else bias.detach(), False,
-                              packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w2))
+        yn = _layer_fwd(_nhwc(x), weight.detach(), None, None if bias is None else bias.detach(), False)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return yn.permute(0, 3, 1, 2)
@@ -508,13 +533,10 @@ class _Conv1x1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
-        Cout, Cin = weight.shape[0], weight.shape[1]
         gn = _nhwc(gy)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            w_t = weight.detach().reshape(Cout, Cin).t().contiguous()
-            gx = ops.conv1x1_nhwc(gn, lambda: ops.pack_conv1x1_nhwc_weights(w_t), Cin,
-                                  packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w_t)).permute(0, 3, 1, 2)
+            gx = _layer_dgrad(gn, weight.detach()).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             gw = _weight_grad(gn, _nhwc(x), weight, 1)
         if ctx.has_bias and ctx.needs_input_grad[2]:
@@ -526,8 +548,7 @@ def bn_eval(bn, y):
     """BatchNorm2d in eval mode under autograd (`norm_eval=True`: vovnet.py:371) as the affine map it is, y * s + t with
     s = gamma / sqrt(var + eps), t = beta - mean * s: the gradients of gamma and beta come out of two column sums instead of
     torch's channels-last batch-norm backward (0.36 ms per layer, 26 ms per step).  Anything else: the module."""
-    if (enabled() and torch.is_grad_enabled() and y.is_cuda and y.dtype == torch.float32 and isinstance(bn, nn.BatchNorm2d)
-            and not bn.training and bn.track_running_stats and bn.affine and not torch.is_autocast_enabled()):
+    if trains("bn_eval", y) and derived.foldable_bn(bn, nn.BatchNorm2d):
         s = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
         t = bn.bias - bn.running_mean * s
         return y * s.view(1, -1, 1, 1) + t.view(1, -1, 1, 1)

@@ -1,5 +1,5 @@
-"""derived.py, the one cache of tensors made from a module's parameters and buffers: its key (version, pointer), `invalidate`, and
-the eval-BatchNorm fold.  CPU only."""
+"""derived.py, the one cache of tensors made from a module's parameters and buffers: its key (version, pointer), `invalidate`, the
+eval-BatchNorm fold and the predicate for what it folds.  CPU only."""
 import pytest
 import torch
 from torch import nn
@@ -108,3 +108,20 @@ def test_invalidate_caches_reaches_the_batchnorm_fold(cls):
     got, want = derived.fold_bn(bn), _fold_by_definition(bn)
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
     assert not torch.equal(got[0], old[0])
+
+
+@pytest.mark.parametrize("cls,other", [(nn.BatchNorm1d, nn.BatchNorm2d), (nn.BatchNorm2d, nn.BatchNorm1d)])
+def test_foldable_bn_is_an_eval_mode_affine_batchnorm_of_the_class_asked_for(cls, other):
+    assert derived.foldable_bn(cls(8).eval(), cls)
+    assert not derived.foldable_bn(cls(8).eval(), other)
+    assert not derived.foldable_bn(cls(8).train(), cls)
+    assert not derived.foldable_bn(cls(8, affine=False).eval(), cls)
+    assert not derived.foldable_bn(cls(8, track_running_stats=False).eval(), cls)
+    assert not derived.foldable_bn(nn.GroupNorm(2, 8).eval(), cls) and not derived.foldable_bn(None, cls)
+
+
+def test_the_two_names_over_foldable_bn():
+    from srfdet3d_amd import dense, sparse
+    assert dense._foldable(nn.BatchNorm2d(8).eval()) and not dense._foldable(nn.BatchNorm1d(8).eval())
+    assert sparse._bn_foldable(nn.BatchNorm1d(8).eval()) and not sparse._bn_foldable(nn.BatchNorm2d(8).eval())
+    assert not dense._foldable(nn.BatchNorm2d(8)) and not sparse._bn_foldable(nn.BatchNorm1d(8))
