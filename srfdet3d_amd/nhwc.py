@@ -3,26 +3,28 @@ VoVNet (vovnet.py:269-374) -> FPN (configs/nus/srfdet_voxel_nusc_LC.py:55-64) ->
 
 The torch modules stay the owners of the parameters (state_dict names untouched); this file only EXECUTES them:
 
-* every 3x3 / stride 1 convolution runs on `srf_wino3x3` (Winograd F(2x2, 3x3) on the f32 MFMA) with the eval BatchNorm
+* every 3x3 / stride 1 convolution ("conv3x3") runs on `srf_wino3x3` (Winograd F(2x2, 3x3) on the f32 MFMA) with the eval BatchNorm
   (or the bias) and the ReLU as its epilogue;
-* an OSA block owns ONE pixel-major buffer of Cin + 5 w channels: the block input sits in slice 0, each 3x3 branch writes
-  its slice, and the 1x1 `concat` convolution (`srf_conv1x1_nhwc`) reads the buffer as a plain matrix -- the
+* an OSA block owns ONE pixel-major buffer of Cin + 5 w channels: the block input sits in slice 0, each 3x3 branch ("layer") writes
+  its slice, and the 1x1 `concat` convolution ("concat", `srf_conv1x1_nhwc`) reads the buffer as a plain matrix -- the
   torch.cat of vovnet.py:222 is never built;
-* eSE: pixel mean (epilogue of the concat convolution, `srf_conv1x1_nhwc_pooled`) -> fc + hard sigmoid (`srf_ese_gate`) -> gate multiply + identity add in one pass
-  that writes straight into slice 0 of the next block's buffer (`srf_nhwc_affine`);
-* the stride-2 stem layers: stem_1 (3 -> 64) is a streaming kernel from the NCHW images to channels-last
-  (`srf_stem_conv_nchw`), stem_3 an implicit-im2col GEMM (`srf_conv_gemm_nhwc`); nothing of the branch runs on MIOpen.
+* eSE ("ese"): pixel mean (epilogue of the concat convolution, `srf_conv1x1_nhwc_pooled`) -> fc + hard sigmoid (`srf_ese_gate`) -> gate multiply + identity add in one pass
+  that writes straight into slice 0 of the next block's buffer (`srf_nhwc_affine`), as the stage's "pool" or a "copy" does for its first block;
+* the stride-2 stem layers: stem_1 (3 -> 64, "stem") is a streaming kernel from the NCHW images to channels-last
+  (`srf_stem_conv_nchw`), stem_3 ("strided") an implicit-im2col GEMM (`srf_conv_gemm_nhwc`); nothing of the branch runs on MIOpen.
+A network is walked ONCE per call into these steps (`Step`; the quoted names are its kinds): the gate is "a plan exists and its shapes
+fit", the forward runs that plan.  Nothing is kept between calls: `_foldable` depends on each BatchNorm's mode.
 
 Opt-in, off by default: inside `mfma_dtype(torch.bfloat16)` (`SRFDet.img_mfma_dtype`) the GEMM-shaped layers of VoVNet and the FPN run
 on the bf16-product kernels of csrc/gemm_bf16.hip instead (f32 tensors, operands rounded to bf16 once, f32 accumulation and epilogue).
 
 Tensors handed to the rest of the model are logical NCHW views with channels_last strides, so every consumer that only
 looks at shapes keeps working and the RoI gather finds its channels-last operand without a copy.
-
 Taken only for fp32 CUDA inference with BatchNorm in eval mode (`dense.fusable` / `dense._foldable`); anything else goes
 through the modules as written.
 """
 import os
+from collections import OrderedDict, namedtuple
 
 import torch
 from torch import nn
@@ -30,11 +32,22 @@ from torch import nn
 from . import derived, ops
 from .dense import _foldable, fusable
 
+_SWITCHES = {"IMG_NHWC": "1", "WINO43": "1", "FPN_FORK": "2"}   # this file's switches, SRF_<name> in the environment, read at every call: name -> default
+
+
+def switch(name):
+    return os.environ.get("SRF_" + name, _SWITCHES[name])   # KeyError: not a switch of this file
+
 
 def enabled():
     """SRF_IMG_NHWC=0 sends the camera branch through torch / MIOpen as in round 1 (A/B switch for tests and benchmarks)."""
-    import os
-    return os.environ.get("SRF_IMG_NHWC", "1") != "0"
+    return switch("IMG_NHWC") != "0"
+
+
+def takes(x=None, channels_last=False):
+    """This tensor goes to the channels-last executor: the switch is on and x is an fp32 CUDA tensor outside autograd and autocast
+    (`dense.fusable`), with channels-last strides when that is asked.  x=None: the switch alone (`SRFDetHead.img_level_consumer`)."""
+    return enabled() and (x is None or (fusable(x) and (not channels_last or is_channels_last(x))))
 
 
 def nhwc_view(x):
@@ -50,18 +63,16 @@ def is_channels_last(x):
     return x.dim() == 4 and x.stride(1) == 1 and x.shape[1] > 1
 
 
-# kind -> the pack call of that operand; the packed images are held by `derived` under the kind's name
-_PACK = {
-    "wino": ops.pack_wino3x3_weights, "wino43": ops.pack_wino43_weights,
-    "gemm": ops.pack_conv1x1_nhwc_weights, "gemm_direct": ops.pack_conv1x1_nhwc_direct_weights,
-    "gemm_split": ops.pack_conv1x1_nhwc_split_weights, "gemm_bf16": ops.pack_conv1x1_nhwc_bf16_weights,
-    "cgemm": ops.pack_conv_gemm_weights, "cgemm_split": ops.pack_conv_gemm_split_weights, "cgemm_bf16": ops.pack_conv_gemm_bf16_weights,
-}
+# kind -> the name of that operand's pack call in `ops` (looked up at the call); the packed images are held by `derived` under the kind's name
+_PACK = {"wino": "pack_wino3x3_weights", "wino43": "pack_wino43_weights", "gemm": "pack_conv1x1_nhwc_weights",
+         "gemm_direct": "pack_conv1x1_nhwc_direct_weights", "gemm_split": "pack_conv1x1_nhwc_split_weights",
+         "gemm_bf16": "pack_conv1x1_nhwc_bf16_weights", "cgemm": "pack_conv_gemm_weights", "cgemm_split": "pack_conv_gemm_split_weights",
+         "cgemm_bf16": "pack_conv_gemm_bf16_weights"}
 
 
 def packed(conv, kind):
     """The `kind` operand of conv.weight, packed once and kept until the weight changes."""
-    return derived.get(conv, kind, (conv.weight,), lambda: _PACK[kind](conv.weight.detach()))
+    return derived.get(conv, kind, (conv.weight,), lambda: getattr(ops, _PACK[kind])(conv.weight.detach()))
 
 
 def invalidate_caches(model):
@@ -117,26 +128,18 @@ def _bf16_route(x, conv, out, form):
     m = _MFMA
     if m is None:
         return False
-    why = None
-    try:
-        x_ld = ops.nhwc_ld(x)
-        y_ld = ops.nhwc_ld(out) if out is not None else conv.out_channels
-    except RuntimeError:
-        x_ld = y_ld = 0
-        why = "not a channel slice of a pixel-major buffer"
     N, H, W, cin = x.shape
-    if why is None:
-        if not ops.gemm_k_ok(cin):
-            why = "input channels are no multiple of 32"
-        elif x_ld % 4 or x.data_ptr() % 16:
-            why = "operand alignment"
-        elif not ops.gemm_rows_ok(max(x_ld, y_ld)) or (form == "conv" and not ops.below_2gb(H * W, x_ld)):
-            why = "beyond the 32-bit ranges"
+    try:
+        x_ld, y_ld = ops.nhwc_ld(x), (ops.nhwc_ld(out) if out is not None else conv.out_channels)
+        why = ("input channels are no multiple of 32" if not ops.gemm_k_ok(cin) else "operand alignment" if not ops.operand_ok(x_ld, x.data_ptr())
+               else "beyond the 32-bit ranges" if not ops.gemm_rows_ok(max(x_ld, y_ld)) or (form == "conv" and not ops.below_2gb(H * W, x_ld))
+               else None)
+    except RuntimeError:
+        why = "not a channel slice of a pixel-major buffer"
     if m.routes is not None:
         k, st = conv.kernel_size[0], conv.stride[0]
         m.routes.append(dict(layer=f"{cin}->{conv.out_channels} {k}x{k}/s{st} @{N}x{H}x{W}", route="f32" if why else "bf16", why=why))
-    if why is None:
-        m.launches += 1
+    m.launches += why is None
     return why is None
 
 
@@ -157,7 +160,7 @@ def _affine_of(conv, bn):
 
 def wino43_enabled():
     """SRF_WINO43=0 keeps every 3x3 layer on Winograd F(2x2, 3x3) (A/B switch for tests and benchmarks)."""
-    return os.environ.get("SRF_WINO43", "1") != "0"
+    return switch("WINO43") != "0"
 
 
 def use_wino43(x, cout, out=None):
@@ -187,162 +190,19 @@ def conv1x1(x, conv, bn=None, relu=False, out=None, pool=False, top=None):
 
 
 def wino_ok(conv, cin):
-    return _is_conv(conv, 3) and cin % 8 == 0
+    return _is_conv(conv, 3) and ops.wino3x3_channels_ok(cin)
 
 
 def _img_fits(H, W, ld):
-    """One image of an (N, H, W, ld) f32 buffer inside the 2^30-byte per-image range of srf_wino3x3 (ops.wino3x3_supported)."""
-    return 4 * H * W * ld < (1 << 30)
-
-
-def gemm_ok(conv, cin):
-    return _is_conv(conv, 1) and cin % 32 == 0
-
-
-# ---- VoVNet ----------------------------------------------------------------------------------------------------------
-def _cbr(seq):
-    """[conv, bn, relu] children of an nn.Sequential built by vovnet._cbr; None if it has another form."""
-    mods = list(seq.children())
-    if len(mods) == 3 and isinstance(mods[0], nn.Conv2d) and _foldable(mods[1]) and isinstance(mods[2], nn.ReLU):
-        return mods[0], mods[1]
-    return None
-
-
-def vovnet_supported(net, x):
-    from .plugin.vovnet import OSAModule
-    if not (fusable(x) and x.dim() == 4):
-        return False
-    stem = list(net.stem.children())
-    if len(stem) != 9:
-        return False
-    for i in (0, 3, 6):
-        if not (isinstance(stem[i], nn.Conv2d) and _foldable(stem[i + 1]) and isinstance(stem[i + 2], nn.ReLU)):
-            return False
-    if not (wino_ok(stem[3], stem[3].in_channels) and stem[3].bias is None):
-        return False
-    c0, c6 = stem[0], stem[6]
-    if not (c0.kernel_size == (3, 3) and c0.stride == (2, 2) and c0.padding == (1, 1) and c0.groups == 1 and c0.in_channels <= 4
-            and c0.out_channels == 64 and c6.kernel_size == (3, 3) and c6.stride == (2, 2) and c6.padding == (1, 1)
-            and strided_ok(c6, c6.in_channels)):
-        return False
-    # every buffer the executor makes must fit the kernels' per-image 32-bit offsets (ops.wino3x3_supported: 4 H W ld < 2^30)
-    H, W = (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1          # after stem_1
-    if not _img_fits(H, W, 64):
-        return False
-    H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1                              # after stem_3
-    for name in net.stage_names:
-        for m in getattr(net, name).children():
-            if isinstance(m, nn.MaxPool2d):
-                H, W = ops.pool3s2_out(H), ops.pool3s2_out(W)
-            elif isinstance(m, OSAModule):
-                convs = [_cbr(layer) for layer in m.layers]
-                if any(c is None for c in convs):
-                    return False
-                if not _img_fits(H, W, convs[0][0].in_channels + sum(c[0].out_channels for c in convs)):
-                    return False
-    for name in net.stage_names:
-        for m in getattr(net, name).children():
-            if isinstance(m, nn.MaxPool2d):
-                if not (m.kernel_size == 3 and m.stride == 2 and m.padding == 0 and m.ceil_mode and m.dilation == 1):
-                    return False
-            elif isinstance(m, OSAModule):
-                if m.reduce is not None:
-                    return False
-                cin = None
-                for layer in m.layers:
-                    cb = _cbr(layer)
-                    if cb is None or not wino_ok(cb[0], cb[0].in_channels):
-                        return False
-                    cin = cin or cb[0].in_channels
-                cc = _cbr(m.concat)
-                if cc is None or not gemm_ok(cc[0], cc[0].in_channels) or cc[0].out_channels % 4 or cc[0].out_channels > 1024:
-                    return False
-            else:
-                return False
-    return True
-
-
-def _osa_forward(m, buf, cin, dst):
-    """One OSA block.  buf: (N, H, W, cin + L w) with the block input in [..., :cin]; dst: NHWC slice that receives the
-    block output (gate * concat (+ input))."""
-    off = cin
-    src = buf[..., :cin]
-    for layer in m.layers:
-        conv, bn = _cbr(layer)
-        w = conv.out_channels
-        out = buf[..., off:off + w]
-        conv3x3(src, conv, bn, True, out=out)
-        src, off = out, off + w
-    conv, bn = _cbr(m.concat)
-    t, mean = conv1x1(buf, conv, bn, True, pool=True)     # eSE average pool from the convolution's own epilogue
-    res = buf[..., :cin] if m.identity else None
-    gate = ops.ese_gate(mean, m.ese.fc.weight, m.ese.fc.bias)
-    ops.nhwc_affine(t, scale=gate, residual=res, out=dst)
-    return dst
-
-
-def vovnet_forward(net, x, upto=None):
-    """x (N, 3, H, W) f32 -> OrderedDict of the requested stage outputs (logical NCHW, channels_last strides).
-    upto = a stage name: stop after that stage and return (outputs so far, that stage's NHWC output) -- the frozen prefix
-    of the backbone during training (`VoVNet.forward`)."""
-    from collections import OrderedDict
-    from .plugin.vovnet import OSAModule
-    out = OrderedDict()
-    stem = list(net.stem.children())
-    # stem_1 (3 -> 64, stride 2): NCHW images -> channels-last, BatchNorm + ReLU in the same kernel
-    s1, b1 = _affine_of(stem[0], stem[1])
-    y = ops.stem_conv_nchw(x.contiguous(), stem[0].weight, s1, b1, True)
-    # stem_2 (64 -> 64) Winograd; stem_3 (64 -> 128, stride 2) implicit-im2col GEMM, written straight into the first block's buffer
-    y = conv3x3(y, stem[3], stem[4], True)
-    cur = None          # finished NHWC tensor (stage output) when not already inside a block buffer
-    pending = y         # stem_2 output: stem_3 runs when the first buffer exists
-    if "stem" in net._out_features:
-        cur = conv_strided(y, stem[6], stem[7], True)
-        pending = None
-        out["stem"] = nchw_view(cur)
-    for name in net.stage_names:
-        mods = list(getattr(net, name).children())
-        blocks = [m for m in mods if isinstance(m, OSAModule)]
-        pool = any(isinstance(m, nn.MaxPool2d) for m in mods)
-        first = blocks[0]
-        cin = _cbr(first.layers[0])[0].in_channels
-        width = sum(_cbr(l)[0].out_channels for l in first.layers)
-        src = pending if pending is not None else cur
-        N, H, W, _ = src.shape
-        if pending is not None:
-            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1   # stem_3: 3x3, stride 2, padding 1
-        elif pool:
-            H, W = ops.pool3s2_out(H), ops.pool3s2_out(W)
-        buf = torch.empty((N, H, W, cin + width), dtype=torch.float32, device=src.device)
-        if pending is not None:
-            conv_strided(pending, stem[6], stem[7], True, out=buf[..., :cin])
-            pending = None
-        elif pool:
-            ops.nhwc_maxpool3s2_ceil(src, out=buf[..., :cin])
-        else:
-            buf[..., :cin].copy_(src)
-        for i, m in enumerate(blocks):
-            cout = _cbr(m.concat)[0].out_channels
-            if i + 1 < len(blocks):
-                nxt = blocks[i + 1]
-                ncin = _cbr(nxt.layers[0])[0].in_channels
-                nwidth = sum(_cbr(l)[0].out_channels for l in nxt.layers)
-                nbuf = torch.empty((N, H, W, ncin + nwidth), dtype=torch.float32, device=src.device)
-                _osa_forward(m, buf, cin, nbuf[..., :cout])
-                buf, cin = nbuf, ncin
-            else:
-                cur = torch.empty((N, H, W, cout), dtype=torch.float32, device=src.device)
-                _osa_forward(m, buf, cin, cur)
-        if name in net._out_features:
-            out[name] = nchw_view(cur)
-        if upto is not None and name == upto:
-            return out, cur
-    return out
+    """One image of an (N, H, W, ld) f32 buffer inside the per-image range of srf_wino3x3 (`ops.wino3x3_range_ok`).  The gates hold
+    EVERY buffer a 3x3 layer reads to this bound, also where the layer runs on srf_wino43, whose own range is wider: deliberately --
+    which of the two kernels a layer takes is a switch and a threshold (`use_wino43`), the gate's verdict is neither."""
+    return ops.wino3x3_range_ok(H * W, ld)
 
 
 def strided_ok(conv, cin):
     return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.dilation == (1, 1) and conv.stride[0] == conv.stride[1]
-            and conv.padding[0] == conv.padding[1] and cin % 32 == 0)
+            and conv.padding[0] == conv.padding[1] and ops.gemm_k_ok(cin))
 
 
 def conv_strided(x, conv, bn=None, relu=False, out=None):
@@ -354,83 +214,222 @@ def conv_strided(x, conv, bn=None, relu=False, out=None):
                               packed_bf16=(lambda: packed(conv, "cgemm_bf16")) if _bf16_route(x, conv, out, "conv") else None)
 
 
-def to_nhwc(x):
-    """Contiguous NCHW f32 tensor -> NHWC tensor (LDS tile transpose)."""
-    return nhwc_view(ops.to_channels_last(x))
+# One step of a plan.  kind: a quoted name at the head of the file, "lateral" (FPN), "out"; arg: "ese" adds the block's input, an FPN step ends in a ReLU, the name of an "out"
+Step = namedtuple("Step", "kind conv bn arg", defaults=(None, None, None))
+Slot = namedtuple("Slot", "H W width lo hi")     # a step writes channels [lo, hi) of an (N, H, W, width) buffer
+
+
+def _cbr(mods):
+    """(conv, bn) of a [conv, bn, relu] triple (an nn.Sequential built by vovnet._cbr, or three modules); None if it has another form."""
+    mods = list(mods.children()) if isinstance(mods, nn.Module) else mods
+    ok = len(mods) == 3 and isinstance(mods[0], nn.Conv2d) and _foldable(mods[1]) and isinstance(mods[2], nn.ReLU)
+    return (mods[0], mods[1]) if ok else None
+
+
+# ---- VoVNet ----------------------------------------------------------------------------------------------------------
+def vovnet_plan(net):
+    """The steps of VoVNet.forward, or None when the net has another structure than stem_1 .. stem_3 and stages of [pool,] plain OSA
+    blocks whose layers the kernels take."""
+    from .plugin.vovnet import OSAModule
+    stem = list(net.stem.children())
+    cbr = [_cbr(stem[i:i + 3]) for i in (0, 3, 6)]
+    if len(stem) != 9 or None in cbr:
+        return None
+    (c0, b0), (c3, b3), (c6, b6) = cbr
+    if not (c0.kernel_size == (3, 3) and c0.stride == (2, 2) and c0.padding == (1, 1) and c0.groups == 1
+            and ops.stem_channels_ok(c0.in_channels, c0.out_channels) and wino_ok(c3, c3.in_channels) and c3.bias is None
+            and _is_conv(c6, 3, 2) and ops.gemm_k_ok(c6.in_channels)):
+        return None
+    plan = [Step("stem", c0, b0), Step("conv3x3", c3, b3), Step("strided", c6, b6)]
+    if "stem" in net._out_features:
+        plan.append(Step("out", arg="stem"))
+    for name in net.stage_names:
+        blocks = list(getattr(net, name).children())
+        if blocks and isinstance(blocks[0], nn.MaxPool2d):
+            m = blocks.pop(0)
+            if not (m.kernel_size == 3 and m.stride == 2 and m.padding == 0 and m.ceil_mode and m.dilation == 1):
+                return None
+            plan.append(Step("pool"))
+        elif plan[-1].kind == "out":
+            plan.append(Step("copy"))     # a finished tensor enters the block's buffer
+        if not blocks or not all(isinstance(m, OSAModule) and m.reduce is None and len(m.layers) for m in blocks):
+            return None
+        for m in blocks:
+            layers, cc = [_cbr(layer) for layer in m.layers], _cbr(m.concat)
+            if (cc is None or None in layers or not all(wino_ok(c, c.in_channels) for c, _ in layers)
+                    or not (_is_conv(cc[0], 1) and ops.gemm_k_ok(cc[0].in_channels) and ops.ese_channels_ok(cc[0].out_channels))):
+                return None
+            plan += [Step("layer", c, b) for c, b in layers] + [Step("concat", *cc), Step("ese", m.ese.fc, None, m.identity)]
+        plan.append(Step("out", arg=name))
+    return plan
+
+
+def plan_shapes(plan, H, W):
+    """Carries an (H, W) image through a VoVNet plan: every step with the Slot it writes, or None when a buffer that a 3x3 layer reads
+    does not fit (`_img_fits`).  The one place where the size after a stride or a pool and the width of an OSA block's buffer are computed:
+    every step but a block's "layer" opens a buffer, as wide as its own output plus the outputs of the layers that directly follow."""
+    slots = []
+    for i, s in enumerate(plan):
+        last = slots[-1] if slots else None
+        if s.kind == "out":
+            slots.append(last)
+        elif s.kind == "layer":
+            slots.append(Slot(last.H, last.W, last.width, last.hi, last.hi + s.conv.out_channels))
+        else:
+            if s.kind in ("stem", "strided"):
+                H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1       # 3x3, stride 2, padding 1
+            elif s.kind == "pool":
+                H, W = ops.pool3s2_out(H), ops.pool3s2_out(W)
+            c = s.conv.out_channels if s.conv is not None else last.hi - last.lo
+            n = next(j for j, t in enumerate(plan[i + 1:]) if t.kind != "layer")       # an OSA block's layers follow directly
+            width = c + sum(t.conv.out_channels for t in plan[i + 1:i + 1 + n])
+            if plan[i + 1].kind in ("conv3x3", "layer") and not _img_fits(H, W, width):
+                return None
+            slots.append(Slot(H, W, width, 0, c))
+    return list(zip(plan, slots))
+
+
+def _vovnet_steps(net, x):
+    plan = vovnet_plan(net) if x.dim() == 4 else None
+    return plan and plan_shapes(plan, x.shape[2], x.shape[3])
+
+
+def vovnet_forward(net, x, upto=None, steps=None):
+    """x (N, 3, H, W) f32 -> OrderedDict of the requested stage outputs (logical NCHW, channels_last strides).  upto = a stage name: stop after
+    that stage and return (outputs so far, that stage's NHWC output) -- the frozen prefix of the backbone during training (`VoVNet.forward`)."""
+    steps = steps or _vovnet_steps(net, x)
+    if not steps:
+        raise ValueError("nhwc.vovnet_forward: not a network or a shape the executor runs (vovnet_supported)")
+    out = OrderedDict()
+    buf = y = cin = t = mean = None       # the buffer being filled and the block input's width; what the last step wrote
+    for s, slot in steps:
+        alone = slot.width == slot.hi     # the step owns its tensor
+        if s.kind == "stem":              # BatchNorm + ReLU in the same kernel
+            y = ops.stem_conv_nchw(x.contiguous(), s.conv.weight, *_affine_of(s.conv, s.bn), True)
+        elif s.kind == "conv3x3" or (s.kind == "strided" and alone):
+            y = (conv3x3 if s.kind == "conv3x3" else conv_strided)(y, s.conv, s.bn, True)
+        elif s.kind == "layer":
+            y = conv3x3(y, s.conv, s.bn, True, out=buf[..., slot.lo:slot.hi])
+        elif s.kind == "concat":
+            t, mean = conv1x1(buf, s.conv, s.bn, True, pool=True)     # eSE average pool from the convolution's own epilogue
+        elif s.kind == "out":
+            if s.arg in net._out_features:
+                out[s.arg] = nchw_view(y)
+            if upto is not None and s.arg == upto:
+                return out, y
+        else:                             # into slice 0 of the buffer the next block fills: the torch.cat of vovnet.py:222 is never built
+            new = torch.empty((x.shape[0], slot.H, slot.W, slot.width), dtype=torch.float32, device=x.device)
+            dst = new if alone else new[..., :slot.hi]
+            if s.kind == "strided":
+                conv_strided(y, s.conv, s.bn, True, out=dst)
+            elif s.kind == "pool":
+                ops.nhwc_maxpool3s2_ceil(y, out=dst)
+            elif s.kind == "copy":
+                dst.copy_(y)
+            else:                         # eSE: gate * concat (+ the block's input)
+                gate = ops.ese_gate(mean, s.conv.weight, s.conv.bias)
+                ops.nhwc_affine(t, scale=gate, residual=buf[..., :cin] if s.arg else None, out=dst)
+            buf, y, cin = new, dst, slot.hi
+    return out
+
+
+def vovnet_supported(net, x):
+    return fusable(x) and bool(_vovnet_steps(net, x))
+
+
+def vovnet(net, x, upto=None):
+    """`vovnet_forward` when the executor takes the call, else None: one plan for the verdict and the run."""
+    steps = _vovnet_steps(net, x) if takes(x) else None
+    return vovnet_forward(net, x, upto, steps) if steps else None
 
 
 # ---- SECONDCustom ----------------------------------------------------------------------------------------------------
-def second_supported(net, x):
-    if not (fusable(x) and x.dim() == 4 and x.shape[1] % 8 == 0):
-        return False
-    widest = max([x.shape[1]] + [m.out_channels for st in net.blocks for m in st.children() if isinstance(m, nn.Conv2d)])
-    if not _img_fits(x.shape[2], x.shape[3], widest):
-        return False
+def second_plan(net):
+    """The steps of SECONDCustom.forward (second_custom.py:78-91): 3x3 / stride 1 layers on the Winograd kernels, the strided heads of
+    the blocks on srf_conv_gemm_nhwc; None when a stage is no chain of conv -> eval BatchNorm -> ReLU the kernels take."""
+    plan = []
     for stage in net.blocks:
         mods = list(stage.children())
-        if len(mods) % 3:
-            return False
         for j in range(0, len(mods), 3):
-            conv, bn, act = mods[j:j + 3]
-            if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.groups == 1
-                    and conv.dilation == (1, 1) and _foldable(bn) and isinstance(act, nn.ReLU)):
-                return False
-            if conv.stride == (1, 1) and conv.in_channels % 8:
-                return False
-            if conv.stride != (1, 1) and not strided_ok(conv, conv.in_channels):
-                return False
-    return True
+            cb = _cbr(mods[j:j + 3])
+            kind = cb and ("conv3x3" if wino_ok(cb[0], cb[0].in_channels) else "strided" if cb[0].stride != (1, 1) and cb[0].kernel_size == (3, 3)
+                           and cb[0].padding == (1, 1) and strided_ok(cb[0], cb[0].in_channels) else None)
+            if not kind:
+                return None
+            plan.append(Step(kind, *cb))
+        plan.append(Step("out"))
+    return plan
 
 
-def second_forward(net, x):
-    """SECONDCustom.forward (second_custom.py:78-91) on channels-last maps: 3x3 / stride 1 layers on srf_wino3x3, the
-    stride-2 heads of the later blocks on srf_conv_gemm_nhwc."""
-    y = nhwc_view(x) if is_channels_last(x) else to_nhwc(x)
+def _second_steps(net, x):
+    """The widest layer is held to `_img_fits` at the INPUT's size, the strides not followed: on the safe side, as the gate held it."""
+    plan = second_plan(net) if x.dim() == 4 and ops.wino3x3_channels_ok(x.shape[1]) else None
+    widest = plan and max([x.shape[1]] + [s.conv.out_channels for s in plan if s.conv is not None])
+    return plan if plan and _img_fits(x.shape[2], x.shape[3], widest) else None
+
+
+def second_forward(net, x, plan=None):
+    plan = plan or _second_steps(net, x)
+    if not plan:
+        raise ValueError("nhwc.second_forward: not a network or a shape the executor runs (second_supported)")
+    y = nhwc_view(x if is_channels_last(x) else ops.to_channels_last(x))
     outs = []
-    for stage in net.blocks:
-        mods = list(stage.children())
-        for j in range(0, len(mods), 3):
-            conv, bn = mods[j], mods[j + 1]
-            y = conv3x3(y, conv, bn, True) if conv.stride == (1, 1) else conv_strided(y, conv, bn, True)
-        outs.append(nchw_view(y))
+    for s in plan:
+        if s.kind == "out":
+            outs.append(nchw_view(y))
+        else:
+            y = (conv3x3 if s.kind == "conv3x3" else conv_strided)(y, s.conv, s.bn, True)
     return tuple(outs)
 
 
+def second_supported(net, x):
+    return fusable(x) and bool(_second_steps(net, x))
+
+
+def second(net, x):
+    """`second_forward` when the executor takes the call, else None."""
+    plan = _second_steps(net, x) if takes(x) else None
+    return second_forward(net, x, plan) if plan else None
+
+
 # ---- FPN -------------------------------------------------------------------------------------------------------------
-def fpn_supported(fpn, inputs):
+def fpn_plan(fpn, n_inputs):
+    """The layers `fpn_forward` runs for `n_inputs` levels -- laterals (1x1 GEMM, top-down add in the epilogue), output convolutions
+    (3x3 Winograd), extra stride-2 convolutions on the last output (srf_conv_gemm_nhwc) -- or None when the neck is another one."""
     n = len(fpn.lateral_convs)
-    if fpn.start_level != 0 or fpn.backbone_end_level != fpn.num_ins or len(inputs) != n:
+    if (fpn.start_level != 0 or fpn.backbone_end_level != fpn.num_ins or n_inputs != n
+            or (fpn.num_outs != n and not (fpn.num_outs > n and fpn.add_extra_convs == "on_output"))
+            or fpn.upsample_cfg.get("mode", "nearest") != "nearest" or len(fpn.upsample_cfg) != 1):
+        return None
+    takes_it = dict(lateral=lambda c: _is_conv(c, 1) and ops.gemm_k_ok(c.in_channels) and ops.quads_ok(c.out_channels),
+                    conv3x3=lambda c: wino_ok(c, c.in_channels), strided=lambda c: strided_ok(c, c.in_channels))
+    plan = []
+    for kind, cm in zip(["lateral"] * n + ["conv3x3"] * n + ["strided"] * (len(fpn.fpn_convs) - n), [*fpn.lateral_convs, *fpn.fpn_convs]):
+        bn = getattr(cm, cm.norm_name) if cm.with_norm else None
+        if ((cm.with_norm and not _foldable(bn)) or (cm.with_activation and not isinstance(cm.activate, nn.ReLU))
+                or not takes_it[kind](cm.conv)):
+            return None
+        plan.append(Step(kind, cm.conv, bn, cm.with_activation))
+    return plan
+
+
+def fpn_supported(fpn, inputs):
+    plan = fpn_plan(fpn, len(inputs))
+    if plan is None or not all(fusable(x) and is_channels_last(x) for x in inputs):
         return False
-    if fpn.num_outs != n and not (fpn.num_outs > n and fpn.add_extra_convs == "on_output"):
-        return False
-    for cm in list(fpn.fpn_convs)[n:]:   # extra stride-2 convolutions: srf_conv_gemm_nhwc
-        if cm.with_norm and not _foldable(getattr(cm, cm.norm_name)):
-            return False
-        if not strided_ok(cm.conv, cm.conv.in_channels):
-            return False
-        if cm.with_activation and not isinstance(cm.activate, nn.ReLU):
-            return False
-    if fpn.upsample_cfg.get("mode", "nearest") != "nearest" or len(fpn.upsample_cfg) != 1:
-        return False
-    for x, lat, fc in zip(inputs, fpn.lateral_convs, list(fpn.fpn_convs)[:n]):
-        if not (fusable(x) and is_channels_last(x)):
-            return False
+    for x, lat in zip(inputs, plan):
         try:   # a channels-last view that is not a channel slice of a pixel-major buffer (or too large) goes to the module path
             ld = ops.nhwc_ld(nhwc_view(x))
         except RuntimeError:
             return False
-        if ld % 4 or x.data_ptr() % 16 or not _img_fits(x.shape[2], x.shape[3], max(ld, lat.conv.out_channels)):
-            return False
-        for cm in (lat, fc):
-            if cm.with_activation and not isinstance(cm.activate, nn.ReLU):
-                return False
-            if cm.with_norm and not _foldable(getattr(cm, cm.norm_name)):
-                return False
-        if not (gemm_ok(lat.conv, lat.conv.in_channels) and wino_ok(fc.conv, fc.conv.in_channels)):
-            return False
-        if lat.conv.out_channels % 4:
+        if not (ops.operand_ok(ld, x.data_ptr()) and _img_fits(x.shape[2], x.shape[3], max(ld, lat.conv.out_channels))):
             return False
     return True
+
+
+def fpn(neck, inputs):
+    """`fpn_forward` when the executor takes the call, else None (the forward reads the modules itself: the plan is built once)."""
+    return fpn_forward(neck, inputs) if takes() and fpn_supported(neck, inputs) else None
 
 
 def _cm(cm, x, fn):
@@ -482,7 +481,7 @@ def fpn_forward(fpn, inputs):
     if len(convs) > n:
         consumer = None   # extra levels hang off the last output: one chain
     # under a graph capture the chain of every coarse level forks off as soon as its lateral is final
-    fork_from = int(os.environ.get("SRF_FPN_FORK", "2"))   # first level whose chain forks; 0: none
+    fork_from = int(switch("FPN_FORK"))   # first level whose chain forks; 0: none
     fork = consumer is not None and inputs[0].is_cuda and torch.cuda.is_current_stream_capturing() and fork_from > 0
     main = torch.cuda.current_stream() if fork else None
 

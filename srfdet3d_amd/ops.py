@@ -1200,9 +1200,41 @@ def pack_wino3x3_weights(weight):
     return packed
 
 
+def quads_ok(n):
+    """A channel count or pixel pitch in whole float4s: `x_ld & 3` of every channels-last entry (csrc/conv.hip:907, csrc/gemm_host.hpp:48,
+    :64), `C & 3` of the streaming kernels (csrc/nhwc.hip:65)."""
+    return n % 4 == 0
+
+
+def operand_ok(ld, addr):
+    """An operand the kernels read in float4s: pitch `ld` in quads from a 16-byte aligned address (csrc/conv.hip:907, csrc/gemm_host.hpp:48, :64)."""
+    return quads_ok(ld) and addr % 16 == 0
+
+
+def wino3x3_channels_ok(Cin):
+    """srf_wino3x3 packs its operand in chunks of 8 input channels (csrc/conv.hip:885, :907)."""
+    return Cin % 8 == 0
+
+
+def wino3x3_range_ok(pixels, ld):
+    """One image, `pixels` of pitch `ld` floats, inside the 2^30 bytes the per-lane offsets of srf_wino3x3 reach (csrc/conv.hip:909)."""
+    return 4 * pixels * ld < (1 << 30)
+
+
+def stem_channels_ok(Cin, Cout):
+    """srf_stem_conv_nchw: up to 4 image planes into exactly 64 channels (csrc/conv.hip:1352)."""
+    return Cin <= 4 and Cout == 64
+
+
+def ese_channels_ok(C):
+    """Channels of an eSE block's output: quads for srf_ese_gate (csrc/decoder.hip:427) and srf_nhwc_affine (csrc/nhwc.hip:65); C <= 1024
+    as the gate held it (the bound of srf_nhwc_colmean, csrc/nhwc.hip:137, which took the eSE mean before the GEMM's epilogue did)."""
+    return quads_ok(C) and C <= 1024
+
+
 def wino3x3_supported(x):
-    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.shape[3] % 8 == 0 and x.data_ptr() % 16 == 0
-            and x.stride(2) % 4 == 0 and 4 * x.shape[1] * x.shape[2] * x.stride(2) < (1 << 30))
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and wino3x3_channels_ok(x.shape[3]) and operand_ok(x.stride(2), x.data_ptr())
+            and wino3x3_range_ok(x.shape[1] * x.shape[2], x.stride(2)))
 
 
 def wino3x3(x, packed_weight, Cout, scale=None, shift=None, relu=False, out=None):
@@ -1259,15 +1291,14 @@ def wino43_tiles_ok(N, H, W):
 
 def wino43_supported(x, Cout, out=None):
     """Shape / layout limits of srf_wino43 (csrc/wino43.hip: w43_make_args, w43_slab_args)."""
-    if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and wino43_channels_ok(x.shape[3], Cout)
-            and x.data_ptr() % 16 == 0):
+    if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and wino43_channels_ok(x.shape[3], Cout)):
         return False
     try:
         ld = nhwc_ld(x)
         old = nhwc_ld(out) if out is not None else Cout
     except RuntimeError:
         return False
-    if ld % 4 or old % 4 or (out is not None and out.data_ptr() % 16):
+    if not (operand_ok(ld, x.data_ptr()) and operand_ok(old, 0 if out is None else out.data_ptr())):
         return False
     N, H, W, _ = x.shape
     # one slab = the whole layer below 2 GB of V: its images must span less than 4 GB of x and of y
@@ -1785,7 +1816,7 @@ def conv_gemm_nhwc_supported(x):
         ld = nhwc_ld(x)
     except RuntimeError:
         return False
-    return gemm_k_ok(x.shape[3]) and ld % 4 == 0 and x.data_ptr() % 16 == 0 and below_2gb(x.shape[1] * x.shape[2], ld)
+    return gemm_k_ok(x.shape[3]) and operand_ok(ld, x.data_ptr()) and below_2gb(x.shape[1] * x.shape[2], ld)
 
 
 # ---- modulated deformable convolution, DCNv2 (csrc/dcn.hip) ------------------------------------------------------------

@@ -28,8 +28,9 @@ class SECONDCustom(BaseModule):
 
     def forward(self, x):
         from .. import nhwc
-        if nhwc.enabled() and nhwc.second_supported(self, x):
-            return nhwc.second_forward(self, x)   # fp32 inference on the GPU: channels-last, 3x3 / stride-1 layers on srf_wino43 (F(4x4, 3x3)), stride-2 on srf_conv_gemm_nhwc
+        outs = nhwc.second(self, x)   # fp32 inference on the GPU: channels-last, 3x3 / stride-1 layers on srf_wino43 (F(4x4, 3x3)), stride-2 on srf_conv_gemm_nhwc
+        if outs is not None:
+            return outs
         outs = []
         for stage in self.blocks:
             x = run_sequential(stage, x)

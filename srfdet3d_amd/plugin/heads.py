@@ -571,7 +571,7 @@ class SRFDetHead(BaseModule):
 
     @staticmethod
     def _stair_fusable(convs, feats):
-        return (nhwc.enabled() and all(fusable(f) and nhwc.is_channels_last(f) and f.shape[1] % 4 == 0 for f in feats)
+        return (all(nhwc.takes(f, channels_last=True) and ops.quads_ok(f.shape[1]) for f in feats)
                 and all(SRFDetHead._dw_ok(c) for c in convs))
 
     @staticmethod
@@ -645,7 +645,7 @@ class SRFDetHead(BaseModule):
             bs, n_cam, C, H, W = f.shape
             f4 = f.reshape(bs * n_cam, C, H, W)
             conv = self.img_convs[i]
-            if nhwc.enabled() and fusable(f4) and nhwc.is_channels_last(f4) and nhwc.wino_ok(conv, C):
+            if nhwc.takes(f4, channels_last=True) and nhwc.wino_ok(conv, C):
                 g = nhwc.nchw_view(nhwc.conv3x3(nhwc.nhwc_view(f4), conv))  # Winograd on the f32 MFMA, bias in the epilogue
             else:
                 g = train_conv.conv2d(conv, f4)     # training: srf_wino43 forward + data gradient; else conv(f4)
@@ -655,7 +655,7 @@ class SRFDetHead(BaseModule):
     def img_level_consumer(self):
         """`img_convs` as a per-level consumer for nhwc.level_consumer (channels-last in, channels-last out), or None when the
         head has no `img_convs` or a level cannot run on the Winograd kernel."""
-        if not (self.use_img and self.hidden_dim != self.feat_channels_img and nhwc.enabled()):
+        if not (self.use_img and self.hidden_dim != self.feat_channels_img and nhwc.takes()):
             return None
         if not all(nhwc.wino_ok(conv, self.feat_channels_img) for conv in self.img_convs):
             return None

@@ -129,9 +129,9 @@ class VoVNet(BaseModule):
 
     def forward(self, x):
         from .. import nhwc
-        if nhwc.enabled() and nhwc.vovnet_supported(self, x):
-            # fp32 inference on the GPU: channels-last execution on the Winograd / GEMM kernels of csrc/conv.hip
-            return nhwc.vovnet_forward(self, x)
+        out = nhwc.vovnet(self, x)   # fp32 inference on the GPU: channels-last execution on the Winograd / GEMM kernels of csrc/conv.hip
+        if out is not None:
+            return out
         out = OrderedDict()
         done = self._frozen_prefix(x, out)   # training: the frozen stages on the inference kernels, without autograd
         if done is None:
@@ -168,9 +168,10 @@ class VoVNet(BaseModule):
         if any(p.requires_grad for m in frozen for p in m.parameters()) or any(m.training for m in frozen):
             return None
         with torch.no_grad():
-            if not nhwc.vovnet_supported(self, x):
+            done = nhwc.vovnet(self, x, upto=last)
+            if done is None:
                 return None
-            part, cur = nhwc.vovnet_forward(self, x, upto=last)
+            part, cur = done
             keep_cl = train_conv.enabled()       # the trainable remainder runs channels-last (train_conv.py): no copy at all
             for k, v in part.items():
                 out[k] = v if keep_cl else v.contiguous()   # else NCHW for the module path on MIOpen
