@@ -623,6 +623,24 @@ int srf_conv_wgrad_nhwc(const float *g, long long g_ld, const float *x, long lon
 int srf_conv1x1_nhwc_topdown(const float *x, int N, int H, int W, int K, long long x_ld, const float *W_packed, int Cout,
                              const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt, long long top_ld,
                              float *y, long long y_ld, srf_stream_t stream);
+/* srf_conv1x1_nhwc_residual / _direct_residual / _split_residual: conv3 of a ResNet bottleneck with the block's identity in the
+ * epilogue (mmdet Bottleneck.forward: `relu(bn3(conv3(out)) + identity)`), one entry per f32-accurate family:
+ *   y[p][co] = act(fl(fma(acc, scale[co], shift[co])) + res[p][co]),   act = the family's fmaxf ReLU (relu != 0) or nothing,
+ * i.e. the add comes BEFORE the ReLU (the _topdown forms add after it).  res: an (M, res_ld) row-major operand on the rows of y,
+ * res_ld >= Cout (SRF_EINVAL), res_ld % 4 == 0 and res 16-byte aligned (SRF_EUNSUPPORTED), not overlapping y (not checked).  res is read
+ * through a 32-bit buffer descriptor over the rows of one tile: res_ld * rows * 4 must stay below 2^31 bytes, rows = 256 for
+ * srf_conv1x1_nhwc_residual and 128 for the other two, else SRF_EUNSUPPORTED.  Otherwise the arguments, limits, codes and check order of
+ * the plain forms; the residual checks follow the plain ones of their class.  Same bits as the plain form without ReLU followed by one
+ * f32 add and the ReLU.  There is no bf16-product residual form. */
+int srf_conv1x1_nhwc_residual(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
+                              const float *shift, int relu, float *y, long long y_ld, const float *res, long long res_ld,
+                              srf_stream_t stream);
+int srf_conv1x1_nhwc_direct_residual(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout,
+                                     const float *scale, const float *shift, int relu, float *y, long long y_ld, const float *res,
+                                     long long res_ld, srf_stream_t stream);
+int srf_conv1x1_nhwc_split_residual(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout,
+                                    const float *scale, const float *shift, int relu, float *y, long long y_ld, const float *res,
+                                    long long res_ld, srf_stream_t stream);
 /* srf_conv1x1_nhwc_pooled: the same convolution on N images of HW pixels (rows n HW .. (n + 1) HW - 1), which also returns
  * mean[n][co] = the mean over the image's pixels of the stored outputs: VoVNet's eSE average pool (reference
  * mmdet3d_plugin/models/backbones/vovnet.py:165-177 eSEModule.avg_pool on the output of vovnet.py:223 `concat`) without a
@@ -645,6 +663,11 @@ int srf_conv_gemm_nhwc(const float *x, int N, int H, int W, int Cin, long long x
                        srf_stream_t stream);
 int srf_stem_conv_nchw(const float *x, int N, int Cin, int H, int W, const float *Wt, int Cout, const float *scale,
                        const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream);
+/* srf_stem_conv7_nchw: Conv2d(Cin <= 4, 64, 7, stride 2, padding 3) + scale / shift + ReLU from contiguous NCHW images to a
+ * channels-last slice (N, Ho, Wo, y_ld), Ho = (H - 1) / 2 + 1 (mmdet ResNet conv1 / bn1 / relu); Wt is the (64, Cin, 7, 7) weight.
+ * Arguments, codes and refusal order of srf_stem_conv_nchw; every output is one k-ordered fma chain (k = ci 49 + ky 7 + kx). */
+int srf_stem_conv7_nchw(const float *x, int N, int Cin, int H, int W, const float *Wt, int Cout, const float *scale,
+                        const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream);
 
 /* srf_dcnv2_nhwc (csrc/dcn.hip): modulated deformable convolution (DCNv2) forward on channels-last activations -- mmcv's
  * `modulated_deform_conv2d` under `ModulatedDeformConv2dPack`, the 3x3 convolution of the bottlenecks of stages 3 and 4 of
@@ -701,6 +724,10 @@ int srf_nhwc_colmean(const float *x, long long x_ld, int N, long long HW, int C,
 int srf_nhwc_colsum_prod(const float *a, long long a_ld, const float *b, long long b_ld, int N, long long HW, int C, float *out /*N x C*/,
                          void *workspace, size_t workspace_bytes, srf_stream_t stream);
 int srf_nhwc_maxpool3s2_ceil(const float *x, long long x_ld, int N, int H, int W, int C, float *y, long long y_ld,
+                             srf_stream_t stream);
+/* srf_nhwc_maxpool3s2_pad1: MaxPool2d(3, stride 2, padding 1), floor mode (the pool behind a ResNet stem) -> (N, Ho, Wo, C),
+ *   Ho = (H - 1) / 2 + 1; the padding is -inf.  Arguments, codes and NaN rule of srf_nhwc_maxpool3s2_ceil. */
+int srf_nhwc_maxpool3s2_pad1(const float *x, long long x_ld, int N, int H, int W, int C, float *y, long long y_ld,
                              srf_stream_t stream);
 int srf_nhwc_upsample_add(const float *lat, long long l_ld, const float *top, long long t_ld, int N, int H, int W, int Ht, int Wt,
                           int C, float *y, long long y_ld, srf_stream_t stream);

@@ -143,12 +143,18 @@ SIGNATURES = {
                                              c_size_t, _P]),
     "srf_conv1x1_nhwc_topdown": (c_int, [_P, c_int, c_int, c_int, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_longlong,
                                          _P, c_longlong, _P]),
+    "srf_conv1x1_nhwc_residual": (c_int, [_P, c_longlong, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_longlong, _P, c_longlong, _P]),
+    "srf_conv1x1_nhwc_direct_residual": (c_int, [_P, c_longlong, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_longlong, _P, c_longlong,
+                                                 _P]),
+    "srf_conv1x1_nhwc_split_residual": (c_int, [_P, c_longlong, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_longlong, _P, c_longlong,
+                                                _P]),
     "srf_conv1x1_nhwc_pooled_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int]),
     "srf_conv1x1_nhwc_pooled": (c_int, [_P, c_int, c_longlong, c_int, c_longlong, _P, c_int, _P, _P, c_int, _P, c_longlong, _P, _P,
                                         c_size_t, _P]),
     "srf_conv_gemm_nhwc": (c_int, [_P, c_int, c_int, c_int, c_int, c_longlong, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P,
                                    c_longlong, _P]),
     "srf_stem_conv_nchw": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, c_longlong, _P]),
+    "srf_stem_conv7_nchw": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, c_longlong, _P]),
     "srf_dcnv2_nhwc": (c_int, [_P, c_int, c_int, c_int, c_int, c_longlong, _P, c_longlong, _P, c_longlong, c_int, _P, c_int, c_int, c_int,
                                c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_longlong, _P]),
     "srf_nhwc_affine": (c_int, [_P, c_longlong, c_int, c_longlong, c_int, _P, c_int, _P, _P, c_longlong, c_int, _P, c_longlong, _P]),
@@ -156,6 +162,7 @@ SIGNATURES = {
     "srf_nhwc_colmean": (c_int, [_P, c_longlong, c_int, c_longlong, c_int, _P, _P, c_size_t, _P]),
     "srf_nhwc_colsum_prod": (c_int, [_P, c_longlong, _P, c_longlong, c_int, c_longlong, c_int, _P, _P, c_size_t, _P]),
     "srf_nhwc_maxpool3s2_ceil": (c_int, [_P, c_longlong, c_int, c_int, c_int, c_int, _P, c_longlong, _P]),
+    "srf_nhwc_maxpool3s2_pad1": (c_int, [_P, c_longlong, c_int, c_int, c_int, c_int, _P, c_longlong, _P]),
     "srf_nhwc_upsample_add": (c_int, [_P, c_longlong, _P, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_longlong, _P]),
     "srf_nhwc_dwconv3x3s2": (c_int, [_P, c_longlong, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_longlong, _P]),
     "srf_nhwc_dwconv3x3s2_cat": (c_int, [_P, c_longlong, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_longlong, _P, c_longlong,

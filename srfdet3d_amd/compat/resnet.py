@@ -1,8 +1,10 @@
 """mmdet `ResNet` stand-in for the r50 / r101 image-backbone configs (configs/nus/srfdet_*_r50_nusc_LC.py:`img_backbone`).
 
 Same constructor arguments the configs use and the same state_dict names as mmdet's ResNet (`conv1`, `bn1`,
-`layer{1-4}.{i}.conv{1-3}/bn{1-3}`, `layer*.0.downsample.{0,1}`), so `Pretrained` checkpoints load by key.  Plain dense
-convolutions on MIOpen; in inference every conv -> BN -> ReLU goes through dense.conv_bn_act (one fused BN + ReLU pass).
+`layer{1-4}.{i}.conv{1-3}/bn{1-3}`, `layer*.0.downsample.{0,1}`), so `Pretrained` checkpoints load by key.  fp32 GPU inference of a
+bottleneck net runs on the channels-last executor (`nhwc.resnet`: HIP kernels only, channels-last outputs, SRF_IMG_NHWC=0 switches it
+off).  Everything else -- autograd, CPU, autocast, BasicBlock nets -- is plain dense convolutions on MIOpen, where in inference every
+conv -> BN -> ReLU goes through dense.conv_bn_act (one fused BN + ReLU pass).
 Stages with `dcn=dict(type='DCNv2')` (only configs/others/srfdet_dvoxel_waymo_LC.py) use compat/dcn.py for the 3x3
 convolution of their bottlenecks.
 """
@@ -116,6 +118,10 @@ class ResNet(BaseModule):
                 p.requires_grad = False
 
     def forward(self, x):
+        from .. import nhwc
+        outs = nhwc.resnet(self, x)      # fp32 GPU inference of a bottleneck net: the channels-last executor; None: the modules as written
+        if outs is not None:
+            return outs
         x = self.maxpool(conv_bn_act(self.conv1, self.bn1, True, x))
         outs = []
         for i, name in enumerate(self.res_layers):

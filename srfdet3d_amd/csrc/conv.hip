@@ -598,6 +598,10 @@ struct GemmArgs {
     long long top_ld;
     int mapH, mapW, topH, topW;
     float sy, sx;
+    // residual form (RES kernels only): y = act(fl(fma(acc, scale, shift)) + res[row][co]) -- the identity of a ResNet bottleneck, added
+    // BEFORE the ReLU (the top-down form adds after it); res has the rows of y and res_ld floats per row
+    const float *res;
+    long long res_ld;
 };
 
 // W (Cout, K) row-major -> [chunk of 32][cout block of 256][channel 256][slot 8][4]; slot s of row co holds quad
@@ -620,7 +624,7 @@ __global__ __launch_bounds__(256) void srf_conv1x1_nhwc_pack_k(const float *__re
 //   <2, 2>: 128 x 128, 64 accumulator registers per wave, 32 KB of LDS (one stage + register prefetch) -> several
 //           workgroups per CU: the waves of different workgroups fill each other's barrier / staging gaps (an f32 MFMA
 //           overlaps with another wave's vector and LDS instructions, not with its own wave's);
-template <int RM, int RN, bool CONV>
+template <int RM, int RN, bool CONV, bool RES = false>
 __device__ __forceinline__ void srf_gemm_body(const GemmArgs &a, const unsigned bid)
 {
     constexpr int TM = 64 * RM, TN = 64 * RN;
@@ -815,14 +819,35 @@ __device__ __forceinline__ void srf_gemm_body(const GemmArgs &a, const unsigned 
     float csum[RN];
 #pragma unroll
     for (int j = 0; j < RN; ++j) csum[j] = 0.f;
+    // RES: the residual of this block's rows through a descriptor of its own (a row past the block and a channel past Cout read as
+    // zero and are never stored); the 16 x RN values of a row block are requested together, ahead of the stores they feed
+    __amdgpu_buffer_rsrc_t rrsrc;
+    unsigned rbase[RN];
+    unsigned rrow_b = 0;
+    if (RES) {
+        rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.res) + p0 * a.res_ld, 0, (int)(rows_here * a.res_ld * 4), 0x00020000);
+#pragma unroll
+        for (int j = 0; j < RN; ++j) rbase[j] = co_ok[j] ? (unsigned)((row_base * a.res_ld + co0 + j * 32) * 4) : 0x80000000u;
+        rrow_b = (unsigned)(a.res_ld * 4);
+    }
 #pragma unroll
     for (int i = 0; i < RM; ++i) {
+        float rv[RES ? 16 : 1][RES ? RN : 1];
+        if (RES) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int j = 0; j < RN; ++j)
+                    rv[r][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                        rrsrc, (int)(rbase[j] + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * rrow_b), 0, 0));
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int dr = i * 32 + (r & 3) + 8 * (r >> 2);
 #pragma unroll
             for (int j = 0; j < RN; ++j) {
                 float v = __fmaf_rn(acc[i][j][r], sc[j], sh[j]);
+                if (RES) v = __fadd_rn(v, rv[r][j]);
                 if (a.relu) v = fmaxf(v, 0.f);
                 if (want_top && co_ok[j]) v = __fadd_rn(v, a.top[s_top[row_base + dr] + co0 + j * 32]);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yrsrc, (int)(ybase[j] + (unsigned)dr * yrow_b), 0, 0);
@@ -858,6 +883,13 @@ __global__ __launch_bounds__(256, WPE) void srf_conv1x1_nhwc_k(GemmArgs a)
     srf_gemm_body<RM, RN, CONV>(a, blockIdx.x);
 }
 
+// the residual form (1x1 only): a kernel of its own, so that the instantiations above stay the code and the symbols they were
+template <int RM, int RN, int WPE>
+__global__ __launch_bounds__(256, WPE) void srf_conv1x1_nhwc_res_k(GemmArgs a)
+{
+    srf_gemm_body<RM, RN, false, true>(a, blockIdx.x);
+}
+
 // One launch, two tile sizes: the first `nbig` workgroups run 128 x 128 tiles over the head of the rows (whole rounds of three
 // workgroups per CU), the rest cover the tail of the rows with 64 x 64 tiles.  A last, partly filled round of 128 x 128 tiles
 // costs the full latency of a tile (~100 us at K = 1728: 2.125 rounds took 812 us against 720 us for 2.0); the small tiles
@@ -866,6 +898,13 @@ __global__ __launch_bounds__(256, 3) void srf_conv1x1_nhwc_mixed_k(GemmArgs big,
 {
     if (blockIdx.x < nbig) srf_gemm_body<2, 2, false>(big, blockIdx.x);
     else srf_gemm_body<1, 1, false>(tail, blockIdx.x - nbig);
+}
+
+// the mixed launch of the residual form
+__global__ __launch_bounds__(256, 3) void srf_conv1x1_nhwc_mixed_res_k(GemmArgs big, GemmArgs tail, unsigned nbig)
+{
+    if (blockIdx.x < nbig) srf_gemm_body<2, 2, false, true>(big, blockIdx.x);
+    else srf_gemm_body<1, 1, false, true>(tail, blockIdx.x - nbig);
 }
 
 static int srf_cu_count(int dev)
@@ -1057,12 +1096,13 @@ static GemmArgs gemm_args(const float *x, long long M, int K, long long x_ld, co
 // shared launcher: bpi == 0 -> flat row tiling; bpi > 0 -> per-image tiling with column sums into `colsum`
 static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
                           const float *shift, int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream,
-                          int *bpi_out = nullptr, const SrfGemmTop *td = nullptr)
+                          int *bpi_out = nullptr, const SrfGemmTop *td = nullptr, const SrfGemmRes *rd = nullptr)
 {
     GemmArgs a = gemm_args(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
     a.colsum = colsum;
     a.HW = HW;
     srf_gemm_set_top(a, td);
+    srf_gemm_set_res(a, rd);
     int dev = 0;
     SRF_HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
@@ -1106,7 +1146,8 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
             if (keep >= 1 && t.mblocks >= 1) {
                 const long long gb = ((b.mblocks + 7) / 8) * 8 * nct, gt = ((t.mblocks + 7) / 8) * 8 * srf_ceil_div(Cout, 64);
                 if (gb + gt >= (1ll << 31)) return SRF_EUNSUPPORTED;
-                hipLaunchKernelGGL(srf_conv1x1_nhwc_mixed_k, dim3((unsigned)(gb + gt)), dim3(256), LDS_STD, stream, b, t, (unsigned)gb);
+                if (rd) hipLaunchKernelGGL(srf_conv1x1_nhwc_mixed_res_k, dim3((unsigned)(gb + gt)), dim3(256), LDS_STD, stream, b, t, (unsigned)gb);
+                else hipLaunchKernelGGL(srf_conv1x1_nhwc_mixed_k, dim3((unsigned)(gb + gt)), dim3(256), LDS_STD, stream, b, t, (unsigned)gb);
                 SRF_LAUNCH_CHECK();
                 return SRF_OK;
             }
@@ -1115,8 +1156,12 @@ static int conv1x1_launch(const float *x, long long M, int K, long long x_ld, co
     }
     const long long blocks = ((a.mblocks + 7) / 8) * 8 * srf_ceil_div(Cout, 256 / ncs);
     if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    if (TM == 64)
+    if (TM == 64 && rd)
+        hipLaunchKernelGGL((srf_conv1x1_nhwc_res_k<1, 1, 4>), dim3((unsigned)blocks), dim3(256), (8 * 64 + 8 * 64) * 16, stream, a);
+    else if (TM == 64)
         hipLaunchKernelGGL((srf_conv1x1_nhwc_k<1, 1, 4, false>), dim3((unsigned)blocks), dim3(256), (8 * 64 + 8 * 64) * 16, stream, a);
+    else if (rd)
+        hipLaunchKernelGGL((srf_conv1x1_nhwc_res_k<2, 2, 3>), dim3((unsigned)blocks), dim3(256), LDS_STD, stream, a);
     else
         hipLaunchKernelGGL((srf_conv1x1_nhwc_k<2, 2, 3, false>), dim3((unsigned)blocks), dim3(256), LDS_STD, stream, a);
     SRF_LAUNCH_CHECK();
@@ -1129,6 +1174,19 @@ extern "C" int srf_conv1x1_nhwc(const float *x, long long M, int K, long long x_
     const int rc = srf_gemm_check_1x1(GEMM_LDS, M, K, x_ld, x, W_packed, Cout, y, y_ld);
     if (rc != SRF_OK || M == 0) return rc;
     return conv1x1_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream);
+}
+
+// srf_conv1x1_nhwc_residual: conv3 of a ResNet bottleneck with the block's identity in its epilogue: y = act(fl(fma(acc, scale, shift))
+// + res), the `relu(bn3(conv3(out)) + identity)` of mmdet's Bottleneck.forward in one pass.  res: (M, res_ld) on the rows of y, not
+// overlapping it.  Same bits as srf_conv1x1_nhwc without the ReLU followed by an f32 add and the ReLU.
+extern "C" int srf_conv1x1_nhwc_residual(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
+                                         const float *shift, int relu, float *y, long long y_ld, const float *res, long long res_ld,
+                                         srf_stream_t stream)
+{
+    const SrfGemmRes rd = {res, res_ld};
+    const int rc = srf_gemm_check_1x1(GEMM_LDS, M, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, nullptr, &rd);
+    if (rc != SRF_OK || M == 0) return rc;
+    return conv1x1_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, nullptr, &rd);
 }
 
 // srf_conv1x1_nhwc_topdown: the lateral 1x1 convolution of an FPN level with the top-down step in its epilogue:
@@ -1367,6 +1425,143 @@ extern "C" int srf_stem_conv_nchw(const float *x, int N, int Cin, int H, int W, 
     default: SRF_STEM(4); break;
     }
 #undef SRF_STEM
+    SRF_LAUNCH_CHECK();
+    return SRF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// srf_stem_conv7_nchw: the first layer of a ResNet image backbone, Conv2d(Cin <= 4, 64, 7, stride 2, padding 3) + scale / shift
+// + ReLU, reading the NCHW camera images and writing channels-last (mmdet ResNet.conv1 / bn1 / relu: 3 -> 64 on 6 x 928 x 1600;
+// 52 GFLOP).  The form of srf_stem_conv_nchw_k: a workgroup owns 4 x 64 output pixels, its 13 x 133 input patch per channel is read
+// once, row by row, into LDS with the even and the odd columns apart (P[ci][row 13][column parity][67]: the A operand of tap
+// (ky, kx) is a unit-stride read), the (K, 64) weights beside it.  Wave w multiplies the 64 pixels of output row w by the 64
+// channels on v_mfma_f32_32x32x2_f32: k = ci * 49 + ky * 7 + kx ascending, one fma chain per output, zero taps add +0.
+// LDS at Cin = 3: 148 x 65 weights (38.5 KB) + 3 x 13 x 134 patch (20.9 KB): two workgroups per CU.
+// ---------------------------------------------------------------------------------------------------------------------
+#define S7_ROWS 13      // patch rows of a tile: 2 * ST_R + 5
+#define S7_HALF 67      // columns of one parity: (2 * ST_C + 5 + 1) / 2
+#define S7_ROWP 134
+template <int CIN>
+__global__ __launch_bounds__(256) void srf_stem_conv7_nchw_k(const float *__restrict__ x, int N, int H, int W, int Ho, int Wo,
+                                                            const float *__restrict__ wt, const float *__restrict__ scale,
+                                                            const float *__restrict__ shift, int relu, float *__restrict__ y, long long y_ld,
+                                                            int tilesX, int tilesY)
+{
+    constexpr int K = CIN * 49, KP = (K + 1) & ~1;
+    __shared__ float s_p[CIN * S7_ROWS * S7_ROWP];  // [ci][patch row 0 .. 12][column parity][67]
+    __shared__ float s_w[KP][65];                   // [k][channel] (rows padded: the transposing copy below writes a column per lane group)
+    __shared__ int s_off[KP];                       // patch offset of tap k
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const int bx = blockIdx.x % tilesX, rest = blockIdx.x / tilesX;
+    const int by = rest % tilesY, n = rest / tilesY;
+    const int ox0 = bx * ST_C, oy0 = by * ST_R;
+    // weights (Cout, K) -> s_w[k][co]: consecutive lanes read consecutive k of one output channel
+    for (int e = tid; e < KP * 64; e += 256) {
+        const int co = e / KP, k = e - co * KP;
+        s_w[k][co] = k < K ? wt[(size_t)co * K + k] : 0.f;
+    }
+    if (tid < KP) {
+        const int k = tid < K ? tid : 0;
+        const int ci = k / 49, r = k - ci * 49, ky = r / 7, kx = r - ky * 7;
+        s_off[tid] = (ci * S7_ROWS + ky) * S7_ROWP + (kx & 1) * S7_HALF + (kx >> 1);
+    }
+    {
+        // the patch: all of a thread's loads first (a constant trip count, fully unrolled), then its LDS stores -- one memory latency
+        // per workgroup instead of one per element (see srf_stem_conv_nchw_k)
+        constexpr int cols = 2 * ST_C + 5, total = CIN * S7_ROWS * cols;
+        const float *xn = x + (size_t)n * CIN * H * W;
+        constexpr int NL = (total + 255) / 256;
+        float v[NL];
+        int dst[NL];
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const int e = tid + i * 256;
+            const int r = e / cols, c = e - r * cols;
+            const int ci = r / S7_ROWS, iyl = r - ci * S7_ROWS;
+            const int iy = 2 * oy0 - 3 + iyl, ix = 2 * ox0 - 3 + c;
+            const bool ok = e < total && iy >= 0 && iy < H && ix >= 0 && ix < W;
+            v[i] = ok ? xn[((size_t)ci * H + iy) * W + ix] : 0.f;
+            dst[i] = e < total ? r * S7_ROWP + (c & 1) * S7_HALF + (c >> 1) : -1;
+        }
+#pragma unroll
+        for (int i = 0; i < NL; ++i)
+            if (dst[i] >= 0) s_p[dst[i]] = v[i];
+    }
+    __syncthreads();
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    constexpr int ksteps = KP >> 1;
+    const int a_base = 2 * wave * S7_ROWP + li;   // output row `wave` of the tile: patch rows 2 wave + ky
+#pragma unroll 7
+    for (int s2 = 0; s2 < ksteps; ++s2) {
+        const int k = 2 * s2 + lh;
+        const int off = s_off[k] + a_base;
+        const bool live = k < K;
+        const float a0 = live ? s_p[off] : 0.f, a1 = live ? s_p[off + 32] : 0.f;
+        const float b0 = s_w[k][li], b1 = s_w[k][32 + li];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    float sc[2], sh[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        sc[j] = scale ? scale[j * 32 + li] : 1.f;
+        sh[j] = shift ? shift[j * 32 + li] : 0.f;
+    }
+    // stores through a buffer descriptor of image n: a pixel outside the map gets an offset beyond the range and is dropped
+    __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(y + (long long)n * Ho * Wo * y_ld, 0,
+                                                                     (int)((long long)Ho * Wo * y_ld * 4), 0x00020000);
+    const int oy = oy0 + wave;
+    const unsigned px_b = (unsigned)(y_ld * 4);
+    const unsigned row_off = (unsigned)(((long long)oy * Wo + ox0) * y_ld * 4) + (unsigned)(li * 4);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int px = i * 32 + 4 * lh + (r & 3) + 8 * (r >> 2);
+            const bool ok = oy < Ho && ox0 + px < Wo;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                float o = acc[i][j][r];
+                if (scale) o = __fmaf_rn(o, sc[j], sh[j]);
+                else if (shift) o = __fadd_rn(o, sh[j]);
+                if (relu) o = fmaxf(o, 0.f);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), yrsrc, ok ? (int)(row_off + (unsigned)px * px_b + j * 128) : (int)0x80000000, 0, 0);
+            }
+        }
+}
+
+// Arguments, return codes and refusal order of srf_stem_conv_nchw; Wt is the (64, Cin, 7, 7) weight.
+extern "C" int srf_stem_conv7_nchw(const float *x, int N, int Cin, int H, int W, const float *Wt, int Cout, const float *scale,
+                                   const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream)
+{
+    if (N < 0 || Cin <= 0 || H <= 0 || W <= 0 || y_ld < Cout) return SRF_EINVAL;
+    if (Cin > 4 || Cout != 64 || (y_ld & 3) || ((uintptr_t)y & 15)) return SRF_EUNSUPPORTED;
+    if (N == 0) return SRF_OK;
+    if (!x || !Wt || !y) return SRF_EINVAL;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    if ((long long)Ho * Wo * y_ld * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;   // buffer-descriptor range of one image's output
+    const int tilesX = srf_ceil_div(Wo, ST_C), tilesY = srf_ceil_div(Ho, ST_R);
+    const long long blocks = (long long)N * tilesX * tilesY;
+    if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
+#define SRF_STEM7(C)                                                                                                            \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_stem_conv7_nchw_k<C>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, N, H, W, Ho, Wo, \
+                       Wt, scale, shift, relu, y, y_ld, tilesX, tilesY)
+    switch (Cin) {
+    case 1: SRF_STEM7(1); break;
+    case 2: SRF_STEM7(2); break;
+    case 3: SRF_STEM7(3); break;
+    default: SRF_STEM7(4); break;
+    }
+#undef SRF_STEM7
     SRF_LAUNCH_CHECK();
     return SRF_OK;
 }

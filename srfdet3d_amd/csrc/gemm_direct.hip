@@ -40,10 +40,14 @@ struct GdArgs {
     long long top_ld;
     int mapH, mapW, topH, topW;
     float sy, sx;
+    // residual form (GD_RESID): y = act(fl(fma(acc, scale, shift)) + res[row][co]), the add BEFORE the ReLU (as srf_conv1x1_nhwc_residual)
+    const float *res;
+    long long res_ld;
 };
 #define GD_PLAIN 0
 #define GD_POOL 1
 #define GD_TOPDOWN 2
+#define GD_RESID 3
 
 // W (Cout, K) row-major -> Wd; channels >= Cout are zero
 __global__ __launch_bounds__(256) void srf_gemm_direct_pack_k(const float *__restrict__ Wt, int Cout, int K, int nct, float *__restrict__ P,
@@ -62,7 +66,7 @@ __global__ __launch_bounds__(256) void srf_gemm_direct_pack_k(const float *__res
 template <int MODE>
 __global__ __launch_bounds__(256, 3) void srf_gemm_direct_k(GdArgs a)
 {
-    constexpr bool POOL = MODE == GD_POOL, TOPDOWN = MODE == GD_TOPDOWN;
+    constexpr bool POOL = MODE == GD_POOL, TOPDOWN = MODE == GD_TOPDOWN, RESID = MODE == GD_RESID;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
     const int wm = wave & 1, wn = wave >> 1;
@@ -169,20 +173,41 @@ __global__ __launch_bounds__(256, 3) void srf_gemm_direct_k(GdArgs a)
         __syncthreads();
     }
     float csum[2] = {0.f, 0.f};
+    // RESID: the residual of this block's rows through a descriptor of its own (a row past the block and a channel past Cout read as
+    // zero and are never stored); the 32 values of a row block are requested together, ahead of the stores they feed
+    __amdgpu_buffer_rsrc_t rr;
+    unsigned rbase[2] = {0u, 0u}, rrow_b = 0;
+    if (RESID) {
+        rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.res) + p0 * a.res_ld, 0, (int)(rows_here * a.res_ld * 4), 0x00020000);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) rbase[j] = co_ok[j] ? (unsigned)((row_base * a.res_ld + co0 + j * 32) * 4) : 0x80000000u;
+        rrow_b = (unsigned)(a.res_ld * 4);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float rv[RESID ? 16 : 1][RESID ? 2 : 1];
+        if (RESID) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    rv[r][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                        rr, (int)(rbase[j] + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * rrow_b), 0, 0));
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int dr = i * 32 + (r & 3) + 8 * (r >> 2);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 float v = __fmaf_rn(acc[i][j][r], sc[j], sh[j]);
+                if (RESID) v = __fadd_rn(v, rv[r][j]);
                 if (a.relu) v = fmaxf(v, 0.f);
                 if (TOPDOWN && co_ok[j]) v = __fadd_rn(v, a.top[s_top[row_base + dr] + co0 + j * 32]);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, (int)(ybase[j] + (unsigned)dr * yrow_b), 0, 0);
                 if (POOL) csum[j] += dr < rows_left ? v : 0.f;
             }
         }
+    }
     if (POOL) {
         // column sums of the block: the two lane halves of a wave (shuffle), then the two waves that share the columns (LDS), in a
         // fixed order: reproducible bit for bit
@@ -221,7 +246,8 @@ extern "C" int srf_conv1x1_nhwc_direct_pack_weights(const float *W, int Cout, in
 static const SrfGemmFamily GEMM_DIRECT = {128, true, 128};   // x and y through descriptors of one 128-row tile
 
 static int gd_launch(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale, const float *shift,
-                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr)
+                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr,
+                     const SrfGemmRes *rd = nullptr)
 {
     GdArgs a = {};
     srf_gemm_set_base(a, x, M, K, x_ld, Cout, scale, shift, relu, y, y_ld);
@@ -230,6 +256,7 @@ static int gd_launch(const float *x, long long M, int K, long long x_ld, const f
     a.colsum = colsum;
     a.HW = HW;
     srf_gemm_set_top(a, td);
+    srf_gemm_set_res(a, rd);
     if (colsum) {
         a.bpi = (int)srf_ceil_div(HW, 128);
         a.mblocks = (M / HW) * a.bpi;
@@ -244,6 +271,8 @@ static int gd_launch(const float *x, long long M, int K, long long x_ld, const f
         hipLaunchKernelGGL((srf_gemm_direct_k<GD_POOL>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     else if (td)
         hipLaunchKernelGGL((srf_gemm_direct_k<GD_TOPDOWN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    else if (rd)
+        hipLaunchKernelGGL((srf_gemm_direct_k<GD_RESID>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL((srf_gemm_direct_k<GD_PLAIN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     SRF_LAUNCH_CHECK();
@@ -256,6 +285,17 @@ extern "C" int srf_conv1x1_nhwc_direct(const float *x, long long M, int K, long 
     const int rc = srf_gemm_check_1x1(GEMM_DIRECT, M, K, x_ld, x, W_packed, Cout, y, y_ld);
     if (rc != SRF_OK || M == 0) return rc;
     return gd_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr);
+}
+
+// the residual form: as srf_conv1x1_nhwc_residual (conv.hip)
+extern "C" int srf_conv1x1_nhwc_direct_residual(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
+                                               const float *shift, int relu, float *y, long long y_ld, const float *res, long long res_ld,
+                                               srf_stream_t stream)
+{
+    const SrfGemmRes rd = {res, res_ld};
+    const int rc = srf_gemm_check_1x1(GEMM_DIRECT, M, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, nullptr, &rd);
+    if (rc != SRF_OK || M == 0) return rc;
+    return gd_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, nullptr, &rd);
 }
 
 extern "C" int srf_conv1x1_nhwc_direct_topdown(const float *x, int N, int H, int W, int K, long long x_ld, const float *W_packed, int Cout,

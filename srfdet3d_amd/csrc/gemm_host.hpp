@@ -1,6 +1,6 @@
 // gemm_host.hpp -- the host front of the three dense GEMM families: srf_conv1x1_nhwc / srf_conv_gemm_nhwc (conv.hip, operands staged
 // through LDS), srf_conv1x1_nhwc_direct (gemm_direct.hip, LDS-free) and srf_conv1x1_nhwc_split / srf_conv_gemm_nhwc_split
-// (gemm_split.hip, bf16 split).  What the eleven entry points share lives here: the argument checks, the top-down descriptor, the fill
+// (gemm_split.hip, bf16 split).  What the entry points share lives here: the argument checks, the top-down descriptor, the fill
 // of the fields the three argument structs (GemmArgs, GdArgs, GsArgs) have in common, and the launch of the one pool-finish kernel.
 // What differs for a measured reason stays with each family: tile forms, grids, the mixed launch, the weight packing.
 #pragma once
@@ -20,6 +20,13 @@ struct SrfGemmTop {
     int mapH, mapW, topH, topW;
 };
 
+// the residual form's extra operand: an (M, res_ld) row-major matrix on the rows of y, added to the affine result BEFORE the ReLU
+// (the identity of a ResNet bottleneck; the top-down form adds after it).  Read through a buffer descriptor over the rows of one tile.
+struct SrfGemmRes {
+    const float *res;
+    long long res_ld;
+};
+
 // the pooled form's extra arguments
 struct SrfGemmPool {
     long long HW;
@@ -33,21 +40,24 @@ static inline size_t srf_gemm_pool_bytes(int N, long long HW, int Cout, int pool
     return (size_t)N * (size_t)srf_ceil_div(HW, pool_rows) * Cout * 4;
 }
 
-// The plain (batch = M rows), top-down and pooled (batch = N images) forms of every family.  Order: sizes (SRF_EINVAL), an empty batch
+// The plain (batch = M rows), top-down, pooled (batch = N images) and residual (batch = M rows) forms of every family.  Order: sizes (SRF_EINVAL), an empty batch
 // (SRF_OK: the caller returns without a launch), null pointers (SRF_EINVAL), shape and alignment, then 32-bit ranges (SRF_EUNSUPPORTED),
 // the workspace (SRF_EWORKSPACE).
 static inline int srf_gemm_check_1x1(const SrfGemmFamily &f, long long batch, int K, long long x_ld, const void *x, const void *W_packed,
                                      int Cout, const void *y, long long y_ld, const SrfGemmTop *td = nullptr,
-                                     const SrfGemmPool *pool = nullptr)
+                                     const SrfGemmPool *pool = nullptr, const SrfGemmRes *rd = nullptr)
 {
     if (batch < 0 || K <= 0 || Cout <= 0 || x_ld < K || y_ld < Cout) return SRF_EINVAL;
     if (td && (td->mapH <= 0 || td->mapW <= 0 || td->topH <= 0 || td->topW <= 0 || td->top_ld < Cout)) return SRF_EINVAL;
     if (pool && pool->HW <= 0) return SRF_EINVAL;
+    if (rd && rd->res_ld < Cout) return SRF_EINVAL;
     if (batch == 0) return SRF_OK;
-    if (!x || !W_packed || !y || (td && !td->top) || (pool && (!pool->mean || !pool->workspace))) return SRF_EINVAL;
+    if (!x || !W_packed || !y || (td && !td->top) || (pool && (!pool->mean || !pool->workspace)) || (rd && !rd->res)) return SRF_EINVAL;
     if ((K & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15) || (pool && batch > 65535)) return SRF_EUNSUPPORTED;
+    if (rd && ((rd->res_ld & 3) || ((uintptr_t)rd->res & 15))) return SRF_EUNSUPPORTED;
     if (x_ld * f.tile_rows * 4 >= (1ll << 31) || (f.y_range && y_ld * f.tile_rows * 4 >= (1ll << 31))) return SRF_EUNSUPPORTED;
     if (td && batch * td->topH * td->topW * td->top_ld >= (1ll << 31)) return SRF_EUNSUPPORTED;
+    if (rd && rd->res_ld * f.tile_rows * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;   // the rows of one tile inside res's descriptor
     if (pool && pool->workspace_bytes < srf_gemm_pool_bytes((int)batch, pool->HW, Cout, f.pool_rows)) return SRF_EWORKSPACE;
     return SRF_OK;
 }
@@ -102,6 +112,15 @@ static inline void srf_gemm_set_top(Args &a, const SrfGemmTop *td)
     a.topW = td->topW;
     a.sy = (float)td->topH / (float)td->mapH;
     a.sx = (float)td->topW / (float)td->mapW;
+}
+
+// residual fields; rd == nullptr leaves the zeros
+template <class Args>
+static inline void srf_gemm_set_res(Args &a, const SrfGemmRes *rd)
+{
+    if (!rd) return;
+    a.res = rd->res;
+    a.res_ld = rd->res_ld;
 }
 
 // strided-convolution fields of the implicit im2col (GemmArgs, GsArgs)

@@ -76,6 +76,9 @@ struct GsArgs {
     long long top_ld;
     int mapH, mapW, topH, topW;
     float sy, sx;
+    // residual form (GS_RESID): y = act(fl(fma(acc, scale, shift)) + res[row][co]), the add BEFORE the ReLU (as srf_conv1x1_nhwc_residual)
+    const float *res;
+    long long res_ld;
     // GS_CONV: rows are OUTPUT pixels (n, oy, ox) of a Conv2d(Cin, Cout, (kh, kw), stride, pad), k runs over (tap, input channel): implicit
     // im2col as in srf_conv_gemm_nhwc (conv.hip); a chunk of 32 channels lies inside one tap (Cin % 32 == 0)
     int H, W, Ho, Wo, kw, stride, pad, cin_chunks;
@@ -85,6 +88,7 @@ struct GsArgs {
 #define GS_POOL 1
 #define GS_TOPDOWN 2
 #define GS_CONV 3
+#define GS_RESID 4
 
 __device__ __forceinline__ unsigned gs_pk_bf16(float a, float b)
 {
@@ -126,7 +130,7 @@ __global__ __launch_bounds__(256) void srf_gemm_split_pack_k(const float *__rest
 template <int MODE>
 __global__ __launch_bounds__(256, MODE == GS_CONV ? 2 : 3) void srf_gemm_split_k(GsArgs a)
 {
-    constexpr bool POOL = MODE == GS_POOL, TOPDOWN = MODE == GS_TOPDOWN, CONV = MODE == GS_CONV;
+    constexpr bool POOL = MODE == GS_POOL, TOPDOWN = MODE == GS_TOPDOWN, CONV = MODE == GS_CONV, RESID = MODE == GS_RESID;
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * GS_IMG];   // A planes | B planes
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // work item -> (column tile, row block): items b and b + 8 share an XCD, the column tiles of a row block sit on one L2
@@ -308,20 +312,41 @@ __global__ __launch_bounds__(256, MODE == GS_CONV ? 2 : 3) void srf_gemm_split_k
         __syncthreads();
     }
     float csum[2] = {0.f, 0.f};
+    // RESID: the residual of this block's rows through a descriptor of its own (a row past the block and a channel past Cout read as
+    // zero and are never stored); the 32 values of a row block are requested together, ahead of the stores they feed
+    __amdgpu_buffer_rsrc_t rr;
+    unsigned rbase[2] = {0u, 0u}, rrow_b = 0;
+    if (RESID) {
+        rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.res) + p0 * a.res_ld, 0, (int)(rows_here * a.res_ld * 4), 0x00020000);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) rbase[j] = co_ok[j] ? (unsigned)((row_base * a.res_ld + co0 + j * 32) * 4) : 0x80000000u;
+        rrow_b = (unsigned)(a.res_ld * 4);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float rv[RESID ? 16 : 1][RESID ? 2 : 1];
+        if (RESID) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    rv[r][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                        rr, (int)(rbase[j] + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * rrow_b), 0, 0));
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int dr = i * 32 + (r & 3) + 8 * (r >> 2);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 float v = __fmaf_rn(acc[i][j][r], sc[j], sh[j]);
+                if (RESID) v = __fadd_rn(v, rv[r][j]);
                 if (a.relu) v = fmaxf(v, 0.f);
                 if (TOPDOWN && co_ok[j]) v = __fadd_rn(v, a.top[s_top[row_base + dr] + co0 + j * 32]);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, (int)(ybase[j] + (unsigned)dr * yrow_b), 0, 0);
                 if (POOL) csum[j] += dr < rows_left ? v : 0.f;
             }
         }
+    }
     if (POOL) {
         // column sums of the block: the two lane halves of a wave (shuffle), then the two waves that share the columns (LDS), in a
         // fixed order: reproducible bit for bit
@@ -371,12 +396,14 @@ static GsArgs gs_args(const float *x, long long M, int K, long long x_ld, const 
 }
 
 static int gs_launch(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale, const float *shift,
-                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr)
+                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr,
+                     const SrfGemmRes *rd = nullptr)
 {
     GsArgs a = gs_args(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
     a.colsum = colsum;
     a.HW = HW;
     srf_gemm_set_top(a, td);
+    srf_gemm_set_res(a, rd);
     if (colsum) {
         a.bpi = (int)srf_ceil_div(HW, 128);
         a.mblocks = (M / HW) * a.bpi;
@@ -390,6 +417,8 @@ static int gs_launch(const float *x, long long M, int K, long long x_ld, const v
         hipLaunchKernelGGL((srf_gemm_split_k<GS_POOL>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     else if (td)
         hipLaunchKernelGGL((srf_gemm_split_k<GS_TOPDOWN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    else if (rd)
+        hipLaunchKernelGGL((srf_gemm_split_k<GS_RESID>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL((srf_gemm_split_k<GS_PLAIN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     SRF_LAUNCH_CHECK();
@@ -424,6 +453,17 @@ extern "C" int srf_conv1x1_nhwc_split(const float *x, long long M, int K, long l
     const int rc = srf_gemm_check_1x1(GEMM_SPLIT, M, K, x_ld, x, W_packed, Cout, y, y_ld);
     if (rc != SRF_OK || M == 0) return rc;
     return gs_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr);
+}
+
+// the residual form: as srf_conv1x1_nhwc_residual (conv.hip)
+extern "C" int srf_conv1x1_nhwc_split_residual(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale,
+                                               const float *shift, int relu, float *y, long long y_ld, const float *res, long long res_ld,
+                                               srf_stream_t stream)
+{
+    const SrfGemmRes rd = {res, res_ld};
+    const int rc = srf_gemm_check_1x1(GEMM_SPLIT, M, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, nullptr, &rd);
+    if (rc != SRF_OK || M == 0) return rc;
+    return gs_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, nullptr, &rd);
 }
 
 extern "C" int srf_conv1x1_nhwc_split_topdown(const float *x, int N, int H, int W, int K, long long x_ld, const void *W_packed, int Cout,

@@ -171,6 +171,9 @@ extern "C" int srf_nhwc_colsum_prod(const float *a, long long a_ld, const float 
 // One thread = a 2 x 2 block of outputs x 4 channels: its 5 x 5 input pixels are loaded once (25 float4 instead of the 36 that
 // four independent windows read: the kernel is bound by the loads it issues, not by HBM) and reduced as three-tap maxima
 // along x, then along y -- max is exact, the result is the same whatever the order.
+// PAD = 1: the floor-mode MaxPool2d(3, stride 2, padding 1) of srf_nhwc_maxpool3s2_pad1 -- the same 5 x 5 pixels one up and one to the
+// left, the padding -inf like the taps past the bottom / right edge.
+template <int PAD>
 __global__ __launch_bounds__(256) void srf_nhwc_maxpool3s2_k(const float *__restrict__ x, long long x_ld, int N, int H, int W, int Cq, int Ho,
                                                              int Wo, float *__restrict__ y, long long y_ld)
 {
@@ -185,7 +188,7 @@ __global__ __launch_bounds__(256) void srf_nhwc_maxpool3s2_k(const float *__rest
     const int yb = (int)(r % Ho2), n = (int)(r / Ho2);
     const float NEG = -__builtin_inff();
     const f32x4n neg = {NEG, NEG, NEG, NEG};
-    const int yi0 = 4 * yb, xi0 = 4 * xb;
+    const int yi0 = 4 * yb - PAD, xi0 = 4 * xb - PAD;
     const float *base = x + ((long long)n * H * W) * x_ld + cq * 4;
     f32x4n h[5][2];
 #pragma unroll
@@ -195,7 +198,7 @@ __global__ __launch_bounds__(256) void srf_nhwc_maxpool3s2_k(const float *__rest
 #pragma unroll
         for (int dx = 0; dx < 5; ++dx) {
             const int xi = xi0 + dx;
-            v[dx] = (yi < H && xi < W) ? *reinterpret_cast<const f32x4n *>(base + ((long long)yi * W + xi) * x_ld) : neg;
+            v[dx] = ((PAD == 0 || (yi >= 0 && xi >= 0)) && yi < H && xi < W) ? *reinterpret_cast<const f32x4n *>(base + ((long long)yi * W + xi) * x_ld) : neg;
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -236,7 +239,24 @@ extern "C" int srf_nhwc_maxpool3s2_ceil(const float *x, long long x_ld, int N, i
     if ((C & 3) || (x_ld & 3) || (y_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return SRF_EUNSUPPORTED;
     const int Ho = srf_pool_out(H), Wo = srf_pool_out(W);
     const long long total = (long long)N * ((Ho + 1) / 2) * ((Wo + 1) / 2) * (C / 4);
-    hipLaunchKernelGGL(srf_nhwc_maxpool3s2_k, dim3(srf_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, x, x_ld, N, H, W, C / 4, Ho, Wo,
+    hipLaunchKernelGGL(srf_nhwc_maxpool3s2_k<0>, dim3(srf_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, x, x_ld, N, H, W, C / 4, Ho, Wo,
+                       y, y_ld);
+    SRF_LAUNCH_CHECK();
+    return SRF_OK;
+}
+
+// MaxPool2d(kernel 3, stride 2, padding 1) in floor mode (the pool behind the stem of a ResNet): Ho = (H - 1) / 2 + 1, the padding is
+// -inf, every window holds its centre pixel.  Arguments and codes as srf_nhwc_maxpool3s2_ceil; fmaxf drops a NaN as there.
+extern "C" int srf_nhwc_maxpool3s2_pad1(const float *x, long long x_ld, int N, int H, int W, int C, float *y, long long y_ld,
+                                        srf_stream_t stream)
+{
+    if (N < 0 || H < 1 || W < 1 || C <= 0 || x_ld < C || y_ld < C) return SRF_EINVAL;
+    if (N == 0) return SRF_OK;
+    if (!x || !y) return SRF_EINVAL;
+    if ((C & 3) || (x_ld & 3) || (y_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return SRF_EUNSUPPORTED;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const long long total = (long long)N * ((Ho + 1) / 2) * ((Wo + 1) / 2) * (C / 4);
+    hipLaunchKernelGGL(srf_nhwc_maxpool3s2_k<1>, dim3(srf_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, x, x_ld, N, H, W, C / 4, Ho, Wo,
                        y, y_ld);
     SRF_LAUNCH_CHECK();
     return SRF_OK;

@@ -1,5 +1,6 @@
 """Channels-last (NHWC) inference of the camera branch on the hand-written kernels of csrc/conv.hip and csrc/nhwc.hip:
-VoVNet (vovnet.py:269-374) -> FPN (configs/nus/srfdet_voxel_nusc_LC.py:55-64) -> `img_convs` (srfdet_head.py:404-416).
+VoVNet (vovnet.py:269-374) or a bottleneck ResNet (mmdet `ResNet`, compat/resnet.py) -> FPN (configs/nus/srfdet_voxel_nusc_LC.py:55-64)
+-> `img_convs` (srfdet_head.py:404-416).
 
 The torch modules stay the owners of the parameters (state_dict names untouched); this file only EXECUTES them:
 
@@ -12,6 +13,12 @@ The torch modules stay the owners of the parameters (state_dict names untouched)
   that writes straight into slice 0 of the next block's buffer (`srf_nhwc_affine`), as the stage's "pool" or a "copy" does for its first block;
 * the stride-2 stem layers: stem_1 (3 -> 64, "stem") is a streaming kernel from the NCHW images to channels-last
   (`srf_stem_conv_nchw`), stem_3 ("strided") an implicit-im2col GEMM (`srf_conv_gemm_nhwc`); nothing of the branch runs on MIOpen.
+* a bottleneck ResNet (`resnet_plan`): the 7x7 / stride 2 stem from the NCHW images ("stem7", `srf_stem_conv7_nchw`), the padded max pool
+  ("pool_p1", `srf_nhwc_maxpool3s2_pad1`), then per bottleneck "conv1" (1x1 GEMM; `srf_conv_gemm_nhwc` where a caffe-style block strides
+  it), "conv2" (Winograd at stride 1, `srf_conv_gemm_nhwc` at stride 2) or "dcn" (`conv_offset` on `srf_conv_gemm_nhwc`, then
+  `srf_dcnv2_nhwc` on the NHWC tensors: no transposing copy), "down" (the downsample branch, affine only) and "conv3": the 1x1 GEMM
+  whose epilogue folds bn3, adds the identity and applies the ReLU (`srf_conv1x1_nhwc_residual`).  f32 only: no bf16-product mode,
+  no frozen-prefix training route, no BasicBlock nets.
 A network is walked ONCE per call into these steps (`Step`; the quoted names are its kinds): the gate is "a plan exists and its shapes
 fit", the forward runs that plan.  Nothing is kept between calls: `_foldable` depends on each BatchNorm's mode.
 
@@ -189,6 +196,13 @@ def conv1x1(x, conv, bn=None, relu=False, out=None, pool=False, top=None):
                             packed_bf16=(lambda: packed(conv, "gemm_bf16")) if _bf16_route(x, conv, out, "1x1") else None)
 
 
+def conv1x1_residual(x, conv, bn, res, relu=True, out=None):
+    """conv3 of a bottleneck: relu(bn(conv(x)) + res) in the GEMM's epilogue; always on the f32-accurate families."""
+    scale, shift = _affine_of(conv, bn)
+    return ops.conv1x1_nhwc_residual(x, lambda: packed(conv, "gemm"), conv.out_channels, res, scale, shift, relu, out=out,
+                                     packed_direct=lambda: packed(conv, "gemm_direct"), packed_split=lambda: packed(conv, "gemm_split"))
+
+
 def wino_ok(conv, cin):
     return _is_conv(conv, 3) and ops.wino3x3_channels_ok(cin)
 
@@ -214,7 +228,8 @@ def conv_strided(x, conv, bn=None, relu=False, out=None):
                               packed_bf16=(lambda: packed(conv, "cgemm_bf16")) if _bf16_route(x, conv, out, "conv") else None)
 
 
-# One step of a plan.  kind: a quoted name at the head of the file, "lateral" (FPN), "out"; arg: "ese" adds the block's input, an FPN step ends in a ReLU, the name of an "out"
+# One step of a plan.  kind: a quoted name at the head of the file, "lateral" (FPN), "out"; arg: "ese" adds the block's input, an FPN step ends in a ReLU, the name of an "out",
+# a ResNet "conv3" adds the downsample branch
 Step = namedtuple("Step", "kind conv bn arg", defaults=(None, None, None))
 Slot = namedtuple("Slot", "H W width lo hi")     # a step writes channels [lo, hi) of an (N, H, W, width) buffer
 
@@ -341,6 +356,154 @@ def vovnet(net, x, upto=None):
     """`vovnet_forward` when the executor takes the call, else None: one plan for the verdict and the run."""
     steps = _vovnet_steps(net, x) if takes(x) else None
     return vovnet_forward(net, x, upto, steps) if steps else None
+
+
+# ---- ResNet (bottleneck) ---------------------------------------------------------------------------------------------
+def _pointwise_ok(conv):
+    """A bias-free 1x1 convolution at stride 1 (the GEMM) or 2 (`conv_strided`) whose input the GEMM families read."""
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.stride in ((1, 1), (2, 2))
+            and conv.bias is None and strided_ok(conv, conv.in_channels))
+
+
+def _dcn_ok(m):
+    """A DCNv2 pack `srf_dcnv2_nhwc` runs from NHWC tensors with `conv_offset` on srf_conv_gemm_nhwc: 3x3, padding 1, no dilation, no bias."""
+    co = m.conv_offset
+    return (ops.dcn_enabled() and m.kernel_size == (3, 3) and m.padding == 1 and m.dilation == 1 and m.stride in (1, 2) and m.bias is None
+            and ops.dcnv2_supported(1, m.in_channels, 2, 2, m.groups, m.deform_groups) and ops.gemm_k_ok(m.in_channels)
+            and co.kernel_size == (3, 3) and co.stride == (m.stride, m.stride) and co.padding == (1, 1) and strided_ok(co, co.in_channels))
+
+
+def resnet_plan(net):
+    """The steps of compat.resnet.ResNet.forward for a net of `_Bottleneck` blocks, or None: BasicBlock nets, a BatchNorm that is not
+    foldable, a bias where the module has none, channel counts the kernels refuse, a DCN with dilation (or any DCN with SRF_DCN=0)."""
+    from .compat.dcn import ModulatedDeformConv2dPack
+    from .compat.resnet import _Bottleneck
+    c, m = net.conv1, net.maxpool
+    if not (isinstance(c, nn.Conv2d) and c.kernel_size == (7, 7) and c.stride == (2, 2) and c.padding == (3, 3) and c.dilation == (1, 1)
+            and c.groups == 1 and c.bias is None and _foldable(net.bn1) and isinstance(net.relu, nn.ReLU)
+            and ops.stem7_channels_ok(c.in_channels, c.out_channels)
+            and isinstance(m, nn.MaxPool2d) and m.kernel_size == 3 and m.stride == 2 and m.padding == 1 and not m.ceil_mode and m.dilation == 1):
+        return None
+    plan = [Step("stem7", c, net.bn1), Step("pool_p1")]
+    for i, name in enumerate(net.res_layers):
+        for blk in getattr(net, name):
+            if not (isinstance(blk, _Bottleneck) and all(_foldable(bn) for bn in (blk.bn1, blk.bn2, blk.bn3)) and _pointwise_ok(blk.conv1)
+                    and _pointwise_ok(blk.conv3) and blk.conv3.stride == (1, 1) and ops.quads_ok(blk.conv3.out_channels)):
+                return None
+            c2 = blk.conv2
+            if isinstance(c2, ModulatedDeformConv2dPack):
+                kind = "dcn" if _dcn_ok(c2) else None
+            else:
+                kind = "conv2" if c2.bias is None and (wino_ok(c2, c2.in_channels) or (_is_conv(c2, 3, 2) and ops.gemm_k_ok(c2.in_channels))) else None
+            if kind is None:
+                return None
+            plan += [Step("conv1", blk.conv1, blk.bn1), Step(kind, c2, blk.bn2)]
+            if blk.downsample is not None:
+                down = list(blk.downsample.children())
+                if not (len(down) == 2 and _pointwise_ok(down[0]) and _foldable(down[1])):
+                    return None
+                plan.append(Step("down", *down))
+            plan.append(Step("conv3", blk.conv3, blk.bn3, blk.downsample is not None))     # arg: the identity is the downsample's output
+        plan.append(Step("out", arg=i))
+    return plan
+
+
+def resnet_shapes(plan, H, W, N=1):
+    """Carries an (H, W) image through a ResNet plan: every step with the Slot it writes (each step owns its tensor), or None when the
+    stem's output of one image leaves its descriptor (`ops.stem7_range_ok`), a buffer a 3x3 layer reads does not fit (`_img_fits`), an input of
+    srf_conv_gemm_nhwc (one image) or of srf_dcnv2_nhwc (the batch of N) reaches 2 GiB, or a DCN would read a map of fewer than 2 rows or
+    columns."""
+    slots, blk = [], None      # blk: (H, W) of the running block's input
+    half = lambda h, s: (h - 1) // s + 1      # noqa: E731  7x7 / padding 3, 3x3 / padding 1, 1x1 / padding 0: one formula
+    for s in plan:
+        cin = s.conv.in_channels if s.conv is not None else None
+        if s.kind == "out":
+            slots.append(slots[-1])
+            continue
+        if s.kind == "pool_p1":
+            H, W = ops.pool3s2p1_out(H), ops.pool3s2p1_out(W)
+            slots.append(Slot(H, W, slots[-1].width, 0, slots[-1].hi))
+            continue
+        if s.kind == "conv1":
+            blk = (H, W)
+        src = blk if s.kind == "down" else (H, W)
+        st = s.conv.stride if isinstance(s.conv.stride, int) else s.conv.stride[0]
+        if s.kind == "stem7":
+            st = 2
+            if not ops.stem7_range_ok(half(H, 2) * half(W, 2), s.conv.out_channels):
+                return None
+        elif s.kind == "dcn":
+            if not ops.dcnv2_supported(N, cin, *src, s.conv.groups, s.conv.deform_groups):
+                return None
+        elif s.conv.kernel_size == (3, 3) and not _img_fits(*src, cin):
+            return None
+        if s.kind in ("dcn", "conv2", "conv1", "down") and st != 1 and not ops.below_2gb(src[0] * src[1], cin):
+            return None
+        if s.kind == "dcn" and not ops.below_2gb(src[0] * src[1], cin):      # conv_offset reads the same input through srf_conv_gemm_nhwc
+            return None
+        out = (half(src[0], st), half(src[1], st))
+        if s.kind != "down":
+            H, W = out
+        c = s.conv.out_channels
+        slots.append(Slot(*out, c, 0, c))
+    return list(zip(plan, slots))
+
+
+def _resnet_steps(net, x):
+    plan = resnet_plan(net) if x.dim() == 4 and x.shape[1] == net.conv1.in_channels else None
+    return plan and resnet_shapes(plan, x.shape[2], x.shape[3], x.shape[0])
+
+
+def _dcn(x, m, bn, relu):
+    """DCNv2 on NHWC tensors, bn + ReLU as the epilogue: `forward_hip` of compat/dcn.py without its two transposing copies (the same
+    `dcn` / `dcn_offset` entries of `derived`)."""
+    scale, shift = derived.fold_bn(bn)
+    KG = 9 * m.deform_groups
+    co = m.conv_offset
+    om = ops.conv_gemm_nhwc(x, m._packed("dcn_offset", co.weight), 3 * KG, (3, 3), m.stride, m.padding, None,
+                            None if co.bias is None else co.bias.detach())
+    return ops.dcnv2_nhwc(x, om[..., :2 * KG], om[..., 2 * KG:], m._packed("dcn", m.weight), m.out_channels, (3, 3), m.stride, m.padding,
+                          m.dilation, m.deform_groups, True, scale, shift, relu)
+
+
+def resnet_forward(net, x, steps=None):
+    """x (N, Cin, H, W) f32 -> the tuple of stage outputs `ResNet.forward` returns (logical NCHW, channels_last strides).  Always on
+    the f32 routes: there is no bf16-product residual form, so an active `mfma_dtype` is switched off for the walk."""
+    steps = steps or _resnet_steps(net, x)
+    if not steps:
+        raise ValueError("nhwc.resnet_forward: not a network or a shape the executor runs (resnet_supported)")
+    outs = []
+    y = xin = idt = None        # what the last step wrote; the running block's input and its downsample branch
+    with mfma_dtype(None):
+        for s, _ in steps:
+            if s.kind == "stem7":         # BatchNorm + ReLU in the same kernel
+                y = ops.stem_conv7_nchw(x.contiguous(), s.conv.weight, *_affine_of(s.conv, s.bn), True)
+            elif s.kind == "pool_p1":
+                y = ops.nhwc_maxpool3s2_pad1(y)
+            elif s.kind == "conv1":
+                xin = y
+                y = (conv1x1 if s.conv.stride == (1, 1) else conv_strided)(y, s.conv, s.bn, True)
+            elif s.kind == "conv2":
+                y = (conv3x3 if s.conv.stride == (1, 1) else conv_strided)(y, s.conv, s.bn, True)
+            elif s.kind == "dcn":
+                y = _dcn(y, s.conv, s.bn, True)
+            elif s.kind == "down":
+                idt = (conv1x1 if s.conv.stride == (1, 1) else conv_strided)(xin, s.conv, s.bn, False)
+            elif s.kind == "conv3":
+                y = conv1x1_residual(y, s.conv, s.bn, idt if s.arg else xin, True)
+            elif s.arg in net.out_indices:      # "out"
+                outs.append(nchw_view(y))
+    return tuple(outs)
+
+
+def resnet_supported(net, x):
+    return fusable(x) and bool(_resnet_steps(net, x))
+
+
+def resnet(net, x):
+    """`resnet_forward` when the executor takes the call, else None: one plan for the verdict and the run."""
+    steps = _resnet_steps(net, x) if takes(x) else None
+    return resnet_forward(net, x, steps) if steps else None
 
 
 # ---- SECONDCustom ----------------------------------------------------------------------------------------------------

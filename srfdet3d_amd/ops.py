@@ -1201,29 +1201,40 @@ def pack_wino3x3_weights(weight):
 
 
 def quads_ok(n):
-    """A channel count or pixel pitch in whole float4s: `x_ld & 3` of every channels-last entry (csrc/conv.hip:907, csrc/gemm_host.hpp:48,
-    :64), `C & 3` of the streaming kernels (csrc/nhwc.hip:65)."""
+    """A channel count or pixel pitch in whole float4s: `x_ld & 3` of every channels-last entry (csrc/conv.hip:946, csrc/gemm_host.hpp:56,
+    :74), `C & 3` of the streaming kernels (csrc/nhwc.hip:65)."""
     return n % 4 == 0
 
 
 def operand_ok(ld, addr):
-    """An operand the kernels read in float4s: pitch `ld` in quads from a 16-byte aligned address (csrc/conv.hip:907, csrc/gemm_host.hpp:48, :64)."""
+    """An operand the kernels read in float4s: pitch `ld` in quads from a 16-byte aligned address (csrc/conv.hip:946, csrc/gemm_host.hpp:56, :74)."""
     return quads_ok(ld) and addr % 16 == 0
 
 
 def wino3x3_channels_ok(Cin):
-    """srf_wino3x3 packs its operand in chunks of 8 input channels (csrc/conv.hip:885, :907)."""
+    """srf_wino3x3 packs its operand in chunks of 8 input channels (csrc/conv.hip:924, :946)."""
     return Cin % 8 == 0
 
 
 def wino3x3_range_ok(pixels, ld):
-    """One image, `pixels` of pitch `ld` floats, inside the 2^30 bytes the per-lane offsets of srf_wino3x3 reach (csrc/conv.hip:909)."""
+    """One image, `pixels` of pitch `ld` floats, inside the 2^30 bytes the per-lane offsets of srf_wino3x3 reach (csrc/conv.hip:948)."""
     return 4 * pixels * ld < (1 << 30)
 
 
 def stem_channels_ok(Cin, Cout):
-    """srf_stem_conv_nchw: up to 4 image planes into exactly 64 channels (csrc/conv.hip:1352)."""
+    """srf_stem_conv_nchw: up to 4 image planes into exactly 64 channels (csrc/conv.hip:1410)."""
     return Cin <= 4 and Cout == 64
+
+
+def stem7_channels_ok(Cin, Cout):
+    """srf_stem_conv7_nchw: up to 4 image planes into exactly 64 channels (csrc/conv.hip:1547)."""
+    return Cin <= 4 and Cout == 64
+
+
+def stem7_range_ok(pixels, ld):
+    """One image of srf_stem_conv7_nchw's output, `pixels` of pitch `ld` floats, inside the 2^31 bytes of its buffer descriptor
+    (csrc/conv.hip:1551)."""
+    return 4 * pixels * ld < (1 << 31)
 
 
 def ese_channels_ok(C):
@@ -1352,35 +1363,38 @@ def wino43(x, packed_weight, Cout, scale=None, shift=None, relu=False, out=None)
 
 
 # The three dense GEMM families behind conv1x1_nhwc / conv_gemm_nhwc (csrc/gemm_host.hpp): the C entry points of each by name, the
-# element of its packed weight, what the error messages call that weight and what the timing labels add.
+# element of its packed weight, what the error messages call that weight and what the timing labels add.  residual: the form that adds
+# a bottleneck's identity before the ReLU (`conv1x1_nhwc_residual`); the bf16-product family has none.
 _GEMM_KINDS = {
     "lds": dict(packed_bytes="srf_conv1x1_nhwc_packed_weight_bytes", pack="srf_conv1x1_nhwc_pack_weights", esize=4, dtype=torch.float32,
                 plain="srf_conv1x1_nhwc", topdown="srf_conv1x1_nhwc_topdown", pooled="srf_conv1x1_nhwc_pooled", conv="srf_conv_gemm_nhwc",
-                what="packed", tag=""),
+                residual="srf_conv1x1_nhwc_residual", what="packed", tag=""),
     "direct": dict(packed_bytes="srf_conv1x1_nhwc_direct_packed_weight_bytes", pack="srf_conv1x1_nhwc_direct_pack_weights", esize=4,
                    dtype=torch.float32, plain="srf_conv1x1_nhwc_direct", topdown="srf_conv1x1_nhwc_direct_topdown",
-                   pooled="srf_conv1x1_nhwc_direct_pooled", conv=None, what="direct-packed", tag=" direct"),
+                   pooled="srf_conv1x1_nhwc_direct_pooled", conv=None, residual="srf_conv1x1_nhwc_direct_residual", what="direct-packed",
+                   tag=" direct"),
     "split": dict(packed_bytes="srf_conv1x1_nhwc_split_packed_weight_bytes", pack="srf_conv1x1_nhwc_split_pack_weights", esize=2,
                   dtype=torch.int16, plain="srf_conv1x1_nhwc_split", topdown="srf_conv1x1_nhwc_split_topdown",
-                  pooled="srf_conv1x1_nhwc_split_pooled", conv="srf_conv_gemm_nhwc_split", what="split-packed", tag=" split"),
+                  pooled="srf_conv1x1_nhwc_split_pooled", conv="srf_conv_gemm_nhwc_split", residual="srf_conv1x1_nhwc_split_residual",
+                  what="split-packed", tag=" split"),
     "bf16": dict(packed_bytes="srf_conv1x1_nhwc_bf16_packed_weight_bytes", pack="srf_conv1x1_nhwc_bf16_pack_weights", esize=2,
                  dtype=torch.int16, plain="srf_conv1x1_nhwc_bf16", topdown="srf_conv1x1_nhwc_bf16_topdown",
-                 pooled="srf_conv1x1_nhwc_bf16_pooled", conv="srf_conv_gemm_nhwc_bf16", what="bf16-packed", tag=" bf16"),
+                 pooled="srf_conv1x1_nhwc_bf16_pooled", conv="srf_conv_gemm_nhwc_bf16", residual=None, what="bf16-packed", tag=" bf16"),
 }
 
 
 def gemm_k_ok(K):
-    """Every family reads K in chunks of 32 (csrc/gemm_host.hpp:48, :64)."""
+    """Every family reads K in chunks of 32 (csrc/gemm_host.hpp:56, :74)."""
     return K % 32 == 0
 
 
 def gemm_rows_ok(ld):
-    """128 rows of pitch `ld` floats inside the 2^31-byte descriptor of the direct, split and bf16 families (csrc/gemm_host.hpp:49)."""
+    """128 rows of pitch `ld` floats inside the 2^31-byte descriptor of the direct, split and bf16 families (csrc/gemm_host.hpp:58)."""
     return ld * 512 < (1 << 31)
 
 
 def below_2gb(pixels, ld):
-    """`pixels` rows of `ld` floats below 2 GB: the implicit-im2col input (csrc/gemm_host.hpp:69), the weight gradient's operands (csrc/wgrad.hip:337)."""
+    """`pixels` rows of `ld` floats below 2 GB: the implicit-im2col input (csrc/gemm_host.hpp:79), the weight gradient's operands (csrc/wgrad.hip:337)."""
     return 4 * pixels * ld < (1 << 31)
 
 
@@ -1540,6 +1554,34 @@ def conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, out
     return (out, mean) if pool else out
 
 
+def conv1x1_nhwc_residual(x, packed_weight, Cout, res, scale=None, shift=None, relu=False, out=None, packed_direct=None, packed_split=None):
+    """conv3 of a ResNet bottleneck: out = act(conv1x1(x) * scale + shift + res), the identity `res` ((N, H, W, Cout) NHWC slice, not
+    overlapping out) added BEFORE the ReLU, in the GEMM's epilogue (`srf_conv1x1_nhwc_residual` / `_direct_residual` / `_split_residual`).
+    The family is chosen exactly as `conv1x1_nhwc` chooses it; bit for bit `conv1x1_nhwc(relu=False)` + res, then the ReLU.  There is
+    no bf16-product form."""
+    x_ld = nhwc_ld(x)
+    N, H, W, K = x.shape
+    if out is None:
+        out = _empty((N, H, W, Cout), torch.float32, x.device)
+    elif tuple(out.shape) != (N, H, W, Cout):
+        raise ValueError("conv1x1_nhwc_residual: out has the wrong shape")
+    if tuple(res.shape) != (N, H, W, Cout):
+        raise ValueError("conv1x1_nhwc_residual: res must be (N, H, W, Cout)")
+    y_ld, res_ld = nhwc_ld(out), nhwc_ld(res)
+    if not gemm_rows_ok(max(x_ld, y_ld, res_ld)):     # beyond the 128-row descriptors of the direct and the split family
+        packed_direct = packed_split = None
+    kind, k, packed = _choose_gemm("conv1x1_nhwc_residual", "(Cout, K)", N * H * W, Cout, K, packed_weight, packed_direct, packed_split)
+    split = kind == "split"
+    timing = _dense_timing("gsplit" if split else "gemm")
+    check(getattr(_lib.lib(), k["residual"])(_ptr(x), N * H * W, K, x_ld, _ptr(packed), Cout, _opt(scale, "scale"), _opt(shift, "shift"),
+                                             int(bool(relu)), _ptr(out), y_ld, _ptr(res), res_ld, _stream()), "conv1x1_nhwc_residual")
+    if timing is not None:
+        fl = 2.0 * K * Cout * N * H * W
+        _dense_timed(timing[1], timing[0], f"{K}->{Cout} @{N}x{H}x{W}" + k["tag"] + " +res", fl, 6.0 * fl if split else fl,
+                     4.0 * N * H * W * (K + 2 * Cout) + (6.0 if split else 4.0) * K * Cout)
+    return out
+
+
 def nhwc_affine(x, scale=None, shift=None, relu=False, residual=None, out=None):
     """out = x * scale + shift (+ residual), optional ReLU, on NHWC slices.  scale: (C,) or per sample (N, C)."""
     x_ld = nhwc_ld(x)
@@ -1589,6 +1631,24 @@ def nhwc_colsum_prod(a, b):
 def pool3s2_out(h):
     ho = 1 if h < 3 else (h - 3 + 1) // 2 + 1
     return ho - 1 if (ho - 1) * 2 >= h else ho
+
+
+def pool3s2p1_out(h):
+    """Output extent of MaxPool2d(3, stride 2, padding 1) in floor mode: (h + 2 - 3) // 2 + 1 (csrc/nhwc.hip:257)."""
+    return (h - 1) // 2 + 1
+
+
+def nhwc_maxpool3s2_pad1(x, out=None):
+    """MaxPool2d(3, stride 2, padding 1), floor mode, on an NHWC slice (`srf_nhwc_maxpool3s2_pad1`): the pool behind a ResNet stem."""
+    x_ld = nhwc_ld(x)
+    N, H, W, C = x.shape
+    Ho, Wo = pool3s2p1_out(H), pool3s2p1_out(W)
+    if out is None:
+        out = _empty((N, Ho, Wo, C), torch.float32, x.device)
+    elif tuple(out.shape) != (N, Ho, Wo, C):
+        raise ValueError("nhwc_maxpool3s2_pad1: out has the wrong shape")
+    check(_lib.lib().srf_nhwc_maxpool3s2_pad1(_ptr(x), x_ld, N, H, W, C, _ptr(out), nhwc_ld(out), _stream()), "nhwc_maxpool3s2_pad1")
+    return out
 
 
 def nhwc_maxpool3s2_ceil(x, out=None):
@@ -1913,6 +1973,25 @@ def stem_conv_nchw(x, weight, scale=None, shift=None, relu=False, out=None):
     check(_lib.lib().srf_stem_conv_nchw(_ptr(x), N, Cin, H, W, _ptr(_dev(weight.detach(), "weight", torch.float32)), Cout,
                                         _opt(scale, "scale"), _opt(shift, "shift"), int(bool(relu)), _ptr(out), nhwc_ld(out),
                                         _stream()), "stem_conv_nchw")
+    return out
+
+
+def stem_conv7_nchw(x, weight, scale=None, shift=None, relu=False, out=None):
+    """Conv2d(Cin <= 4, 64, 7, stride 2, padding 3) + affine + ReLU from contiguous NCHW images to an NHWC tensor (`srf_stem_conv7_nchw`:
+    the stem of a ResNet image backbone)."""
+    x = _dev(x, "x", torch.float32)
+    N, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if tuple(weight.shape[1:]) != (Cin, 7, 7):
+        raise ValueError("stem_conv7_nchw: weight must be (Cout, Cin, 7, 7)")
+    if out is None:
+        out = _empty((N, Ho, Wo, Cout), torch.float32, x.device)
+    elif tuple(out.shape) != (N, Ho, Wo, Cout):
+        raise ValueError("stem_conv7_nchw: out has the wrong shape")
+    check(_lib.lib().srf_stem_conv7_nchw(_ptr(x), N, Cin, H, W, _ptr(_dev(weight.detach(), "weight", torch.float32)), Cout,
+                                         _opt(scale, "scale"), _opt(shift, "shift"), int(bool(relu)), _ptr(out), nhwc_ld(out),
+                                         _stream()), "stem_conv7_nchw")
     return out
 
 
