@@ -47,7 +47,7 @@
 // 219-684 TFLOP/s of direct FLOPs where Winograd reaches 179-396; 0.05-0.27 of the 2.5 PFLOP/s dense peak, 15.9 ms against
 // 26.1 ms for the 106 layers of a frame; the finest FPN lateral (256 -> 256 on 232 x 400, memory-bound) gains nothing (1.01x).
 #include "common.hpp"
-#include "gemm_host.hpp"
+#include "gemm_tile128.hpp"
 
 typedef __bf16 gb_bf2 __attribute__((ext_vector_type(2)));
 typedef __bf16 gb_bf8 __attribute__((ext_vector_type(8)));
@@ -59,6 +59,10 @@ typedef unsigned gb_u4 __attribute__((ext_vector_type(4)));
 #define GB_IMG 16384              // bytes of one operand image: 128 rows x 64 bf16
 #define GB_STAGE (2 * GB_IMG)     // A | B
 
+// Not derived from SrfTile128Args: this family keeps its own argument struct and its own copy of the epilogue.  Its K loops are the
+// one place where the compiler's choice between two forms of the weight-load address arithmetic flips with anything that changes
+// around them (the struct's layout, a call that takes the accumulators): with the shared epilogue srf_gemm_bf16_k<GB_POOL> came out
+// with other loads and waits inside the loop.  The decode and the whole host side are the shared ones (gemm_tile128.hpp).
 struct GbArgs {
     const float *x;
     float *y;
@@ -115,20 +119,11 @@ __global__ __launch_bounds__(256, 2) void srf_gemm_bf16_k(GbArgs a)
     constexpr bool POOL = MODE == GB_POOL, TOPDOWN = MODE == GB_TOPDOWN, CONV = MODE == GB_CONV;
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * GB_STAGE];   // stage 0 (A | B), stage 1 (A | B)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // work item -> (column tile, row block): items b and b + 8 share an XCD, the column tiles of a row block sit on one L2
-    const int xcd = blockIdx.x & 7, jq = blockIdx.x >> 3;
-    const int ct = jq % a.nct;
-    const long long mb = (long long)(jq / a.nct) * 8 + xcd;
+    int ct;
+    const long long mb = srf_tile128_row_block(a.nct, ct);
     if (mb >= a.mblocks) return;
-    long long p0 = mb * 128, rows_blk = a.M - p0;
-    long long slot = mb;
-    if (POOL) {
-        const long long n = mb / a.bpi, lb = mb - n * a.bpi;
-        p0 = n * a.HW + lb * 128;
-        rows_blk = a.HW - lb * 128;
-        slot = n * a.bpi + lb;
-    }
-    const long long rows_here = rows_blk < 128 ? rows_blk : 128;
+    const SrfTile128Item it = srf_tile128_item<POOL>(ct, mb, a.M, a.HW, a.bpi);
+    const long long p0 = it.p0, rows_here = it.rows_here;
     __amdgpu_buffer_rsrc_t xr = CONV ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x), 0, (int)a.x_bytes, 0x00020000)
                                      : __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x) + p0 * a.x_ld, 0, (int)(rows_here * a.x_ld * 4), 0x00020000);
     const int nblk = a.nblk, nchunk = a.nchunk;
@@ -255,7 +250,8 @@ __global__ __launch_bounds__(256, 2) void srf_gemm_bf16_k(GbArgs a)
 #undef GB_LOAD
 #undef GB_STORE
 
-    // epilogue (that of srf_gemm_split_k): lane = channel li of block j, accumulator register = pixel row (r & 3) + 8 (r >> 2) + 4 lh of block i
+    const long long rows_blk = it.rows_blk, slot = it.slot;
+    // epilogue (a copy of srf_tile128_epilogue without the residual form, see GbArgs): lane = channel li of block j, accumulator register = pixel row (r & 3) + 8 (r >> 2) + 4 lh of block i
     float sc[2], sh[2];
     bool co_ok[2];
     const int co0 = ct * 128 + wn * 64 + li;
@@ -342,45 +338,19 @@ extern "C" int srf_conv1x1_nhwc_bf16_pack_weights(const float *W, int Cout, int 
     return SRF_OK;
 }
 
-static const SrfGemmFamily GEMM_BF16 = {128, true, 128};   // x and y through descriptors of one 128-row tile
-
-// the fields every launch of this family sets; the rest of GbArgs starts as zero
-static GbArgs gb_args(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale, const float *shift,
-                      int relu, float *y, long long y_ld)
-{
-    GbArgs a = {};
-    srf_gemm_set_base(a, x, M, K, x_ld, Cout, scale, shift, relu, y, y_ld);
-    a.Wp = (const unsigned char *)W_packed;
-    a.nct = srf_ceil_div(Cout, 128);
-    a.nblk = (a.nchunk + 1) / 2;
-    return a;
-}
-
-static int gb_launch(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale, const float *shift,
-                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr)
-{
-    GbArgs a = gb_args(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
-    a.colsum = colsum;
-    a.HW = HW;
-    srf_gemm_set_top(a, td);
-    if (colsum) {
-        a.bpi = (int)srf_ceil_div(HW, 128);
-        a.mblocks = (M / HW) * a.bpi;
-        if (bpi_out) *bpi_out = a.bpi;
-    } else {
-        a.mblocks = srf_ceil_div(M, 128);
+struct GbFamily {
+    typedef GbArgs Args;
+    static constexpr SrfGemmFamily limits = {128, true, 128};   // x and y through descriptors of one 128-row tile
+    static constexpr void (*plain)(GbArgs) = srf_gemm_bf16_k<GB_PLAIN>, (*pool)(GbArgs) = srf_gemm_bf16_k<GB_POOL>,
+                          (*topdown)(GbArgs) = srf_gemm_bf16_k<GB_TOPDOWN>, (*resid)(GbArgs) = nullptr,
+                          (*conv)(GbArgs) = srf_gemm_bf16_k<GB_CONV>;
+    static int set_weights(GbArgs &a, const void *W_packed)
+    {
+        a.Wp = (const unsigned char *)W_packed;
+        a.nblk = (a.nchunk + 1) / 2;
+        return SRF_OK;
     }
-    const long long blocks = ((a.mblocks + 7) / 8) * 8 * a.nct;
-    if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    if (colsum)
-        hipLaunchKernelGGL((srf_gemm_bf16_k<GB_POOL>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else if (td)
-        hipLaunchKernelGGL((srf_gemm_bf16_k<GB_TOPDOWN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((srf_gemm_bf16_k<GB_PLAIN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
-}
+};
 
 // srf_conv_gemm_nhwc_bf16: Conv2d(Cin, Cout, (kh, kw), stride, padding) on channels-last activations with an implicit im2col: in the
 // bf16 mode the 3x3 / stride 1 layers too (no Winograd there: products of bf16-rounded TRANSFORMED data are another, worse arithmetic
@@ -389,37 +359,20 @@ extern "C" int srf_conv_gemm_nhwc_bf16(const float *x, int N, int H, int W, int 
                                        int kw, int stride, int pad, const float *scale, const float *shift, int relu, float *y,
                                        long long y_ld, srf_stream_t stream)
 {
-    int Ho = 0, Wo = 0;
-    long long x_bytes = 0;
-    const int rc = srf_gemm_check_conv(GEMM_BF16, N, H, W, Cin, x_ld, x, W_packed, Cout, kh, kw, stride, pad, y, y_ld, &Ho, &Wo, &x_bytes);
-    if (rc != SRF_OK || N == 0) return rc;
-    if ((long long)kh * kw * Cin >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    GbArgs a = gb_args(x, (long long)N * Ho * Wo, kh * kw * Cin, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
-    srf_gemm_set_conv(a, H, W, Ho, Wo, kw, stride, pad, Cin, x_bytes);
-    a.mblocks = srf_ceil_div(a.M, 128);
-    const long long blocks = ((a.mblocks + 7) / 8) * 8 * a.nct;
-    if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    hipLaunchKernelGGL((srf_gemm_bf16_k<GB_CONV>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
+    return srf_tile128_conv<GbFamily>(x, N, H, W, Cin, x_ld, W_packed, Cout, kh, kw, stride, pad, scale, shift, relu, y, y_ld, stream);
 }
 
 extern "C" int srf_conv1x1_nhwc_bf16(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale,
                                      const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream)
 {
-    const int rc = srf_gemm_check_1x1(GEMM_BF16, M, K, x_ld, x, W_packed, Cout, y, y_ld);
-    if (rc != SRF_OK || M == 0) return rc;
-    return gb_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr);
+    return srf_tile128_plain<GbFamily>(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, stream);
 }
 
 extern "C" int srf_conv1x1_nhwc_bf16_topdown(const float *x, int N, int H, int W, int K, long long x_ld, const void *W_packed, int Cout,
                                              const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt,
                                              long long top_ld, float *y, long long y_ld, srf_stream_t stream)
 {
-    const SrfGemmTop td = {top, top_ld, H, W, Ht, Wt};
-    const int rc = srf_gemm_check_1x1(GEMM_BF16, N, K, x_ld, x, W_packed, Cout, y, y_ld, &td);
-    if (rc != SRF_OK || N == 0) return rc;
-    return gb_launch(x, (long long)N * H * W, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, &td);
+    return srf_tile128_topdown<GbFamily>(x, N, H, W, K, x_ld, W_packed, Cout, scale, shift, relu, top, Ht, Wt, top_ld, y, y_ld, stream);
 }
 
 // the pooled form: as srf_conv1x1_nhwc_split_pooled; workspace = srf_conv1x1_nhwc_pooled_workspace_bytes(N, HW, Cout)
@@ -427,12 +380,5 @@ extern "C" int srf_conv1x1_nhwc_bf16_pooled(const float *x, int N, long long HW,
                                             const float *scale, const float *shift, int relu, float *y, long long y_ld, float *mean,
                                             void *workspace, size_t workspace_bytes, srf_stream_t stream)
 {
-    const SrfGemmPool pool = {HW, mean, workspace, workspace_bytes};
-    int rc = srf_gemm_check_1x1(GEMM_BF16, N, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, &pool);
-    if (rc != SRF_OK || N == 0) return rc;
-    int bpi = 0;
-    rc = gb_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW, (hipStream_t)stream,
-                   &bpi);
-    if (rc != SRF_OK) return rc;
-    return srf_gemm_pool_finish((const float *)workspace, bpi, N, Cout, HW, mean, (hipStream_t)stream);
+    return srf_tile128_pooled<GbFamily>(x, N, HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, mean, workspace, workspace_bytes, stream);
 }

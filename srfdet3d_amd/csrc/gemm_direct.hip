@@ -17,39 +17,18 @@
 // The order of the fma chain of every output is the one of srf_conv1x1_nhwc_k (sub-step s of a chunk multiplies the channels
 // 8 s + i (lanes 0-31) and 8 s + 4 + i (lanes 32-63), i = 0..3): identical bits.
 #include "common.hpp"
-#include "gemm_host.hpp"
+#include "gemm_tile128.hpp"
 
 typedef float gd_f32x16 __attribute__((ext_vector_type(16)));
 typedef float gd_f32x4 __attribute__((ext_vector_type(4)));
 
-struct GdArgs {
-    const float *x;
-    float *y;
-    const float *Wd;
-    const float *scale, *shift;
-    long long x_ld, y_ld, M;
-    int K, Cout, nchunk, nct, relu;
-    long long mblocks;
-    // per-image row tiling + column sums of the stored outputs (eSE pooling): bpi > 0: image n owns row blocks [n bpi, (n + 1) bpi)
-    float *colsum;
-    long long HW;
-    int bpi;
-    // FPN top-down step in the epilogue (as srf_conv1x1_nhwc_topdown): y += top[n][floor(py sy)][floor(px sx)][co]; rows are the
-    // pixels (n, py, px) of an (N, mapH, mapW) map
-    const float *top;
-    long long top_ld;
-    int mapH, mapW, topH, topW;
-    float sy, sx;
-    // residual form (GD_RESID): y = act(fl(fma(acc, scale, shift)) + res[row][co]), the add BEFORE the ReLU (as srf_conv1x1_nhwc_residual)
-    const float *res;
-    long long res_ld;
-};
+struct GdArgs : SrfTile128Args<const float *> {};   // Wp: the packed image of srf_gemm_direct_pack_k; no fields of its own
 #define GD_PLAIN 0
 #define GD_POOL 1
 #define GD_TOPDOWN 2
 #define GD_RESID 3
 
-// W (Cout, K) row-major -> Wd; channels >= Cout are zero
+// W (Cout, K) row-major -> the packed image (GdArgs::Wp); channels >= Cout are zero
 __global__ __launch_bounds__(256) void srf_gemm_direct_pack_k(const float *__restrict__ Wt, int Cout, int K, int nct, float *__restrict__ P,
                                                              long long total)
 {
@@ -70,23 +49,14 @@ __global__ __launch_bounds__(256, 3) void srf_gemm_direct_k(GdArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
     const int wm = wave & 1, wn = wave >> 1;
-    // work item -> (column tile, row block): items b and b + 8 share an XCD, the column tiles of a row block sit on one L2
-    const int xcd = blockIdx.x & 7, jq = blockIdx.x >> 3;
-    const int ct = jq % a.nct;
-    const long long mb = (long long)(jq / a.nct) * 8 + xcd;
+    int ct;
+    const long long mb = srf_tile128_row_block(a.nct, ct);
     if (mb >= a.mblocks) return;
-    long long p0 = mb * 128, rows_blk = a.M - p0;
-    long long slot = mb;
-    if (POOL) {
-        const long long n = mb / a.bpi, lb = mb - n * a.bpi;
-        p0 = n * a.HW + lb * 128;
-        rows_blk = a.HW - lb * 128;
-        slot = n * a.bpi + lb;
-    }
-    const long long rows_here = rows_blk < 128 ? rows_blk : 128;
+    const SrfTile128Item it = srf_tile128_item<POOL>(ct, mb, a.M, a.HW, a.bpi);
+    const long long p0 = it.p0, rows_here = it.rows_here;
     __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x) + p0 * a.x_ld, 0, (int)(rows_here * a.x_ld * 4), 0x00020000);
     const size_t chunk_bytes = (size_t)a.nct * 16384;
-    __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.Wd) + ((size_t)ct * 16 + wn * 8) * 256, 0,
+    __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.Wp) + ((size_t)ct * 16 + wn * 8) * 256, 0,
                                                                  (int)((size_t)a.nchunk * chunk_bytes - ((size_t)ct * 16 + wn * 8) * 1024), 0x00020000);
     unsigned aoff[2];
 #pragma unroll
@@ -136,93 +106,9 @@ __global__ __launch_bounds__(256, 3) void srf_gemm_direct_k(GdArgs a)
 #undef GD_LOAD
 #undef GD_MFMA
 
-    // epilogue: lane = channel li of block j, accumulator register = pixel row (r & 3) + 8 (r >> 2) + 4 lh of block i
-    float sc[2], sh[2];
-    bool co_ok[2];
-    const int co0 = ct * 128 + wn * 64 + li;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int co = co0 + j * 32;
-        co_ok[j] = co < a.Cout;
-        sc[j] = (co_ok[j] && a.scale) ? a.scale[co] : 1.f;
-        sh[j] = (co_ok[j] && a.shift) ? a.shift[co] : 0.f;
-    }
-    __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(a.y + p0 * a.y_ld, 0, (int)(rows_here * a.y_ld * 4), 0x00020000);
-    const int row_base = wm * 64 + 4 * lh;
-    unsigned ybase[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) ybase[j] = co_ok[j] ? (unsigned)((row_base * a.y_ld + co0 + j * 32) * 4) : 0x80000000u;
-    const unsigned yrow_b = (unsigned)(a.y_ld * 4);
-    const long long rows_left = rows_blk - row_base;
-    __shared__ int s_top[TOPDOWN ? 128 : 1];   // offset (floats) of the top-level pixel each row of this block adds
-    if (TOPDOWN) {
-        if (tid < 128) {
-            const long long row = p0 + tid;
-            int off = 0;
-            if (row < a.M) {
-                const int hw = a.mapH * a.mapW;
-                const int n = (int)(row / hw), rem = (int)(row - (long long)n * hw);
-                const int yy = rem / a.mapW, xx = rem - yy * a.mapW;
-                int ys = (int)floorf((float)yy * a.sy), xs = (int)floorf((float)xx * a.sx);
-                if (ys > a.topH - 1) ys = a.topH - 1;
-                if (xs > a.topW - 1) xs = a.topW - 1;
-                off = (int)((((long long)n * a.topH + ys) * a.topW + xs) * a.top_ld);
-            }
-            s_top[tid] = off;
-        }
-        __syncthreads();
-    }
-    float csum[2] = {0.f, 0.f};
-    // RESID: the residual of this block's rows through a descriptor of its own (a row past the block and a channel past Cout read as
-    // zero and are never stored); the 32 values of a row block are requested together, ahead of the stores they feed
-    __amdgpu_buffer_rsrc_t rr;
-    unsigned rbase[2] = {0u, 0u}, rrow_b = 0;
-    if (RESID) {
-        rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.res) + p0 * a.res_ld, 0, (int)(rows_here * a.res_ld * 4), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) rbase[j] = co_ok[j] ? (unsigned)((row_base * a.res_ld + co0 + j * 32) * 4) : 0x80000000u;
-        rrow_b = (unsigned)(a.res_ld * 4);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float rv[RESID ? 16 : 1][RESID ? 2 : 1];
-        if (RESID) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    rv[r][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                        rr, (int)(rbase[j] + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * rrow_b), 0, 0));
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dr = i * 32 + (r & 3) + 8 * (r >> 2);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float v = __fmaf_rn(acc[i][j][r], sc[j], sh[j]);
-                if (RESID) v = __fadd_rn(v, rv[r][j]);
-                if (a.relu) v = fmaxf(v, 0.f);
-                if (TOPDOWN && co_ok[j]) v = __fadd_rn(v, a.top[s_top[row_base + dr] + co0 + j * 32]);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, (int)(ybase[j] + (unsigned)dr * yrow_b), 0, 0);
-                if (POOL) csum[j] += dr < rows_left ? v : 0.f;
-            }
-        }
-    }
-    if (POOL) {
-        // column sums of the block: the two lane halves of a wave (shuffle), then the two waves that share the columns (LDS), in a
-        // fixed order: reproducible bit for bit
-        __shared__ float red[2][128];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float o = __shfl_xor(csum[j], 32);
-            if (lh == 0) red[wm][wn * 64 + j * 32 + li] = csum[j] + o;
-        }
-        __syncthreads();
-        if (tid < 128) {
-            const int co = ct * 128 + tid;
-            if (co < a.Cout) a.colsum[slot * a.Cout + co] = red[0][tid] + red[1][tid];
-        }
-    }
+    // the frame's scratch LDS, sized by form: the top-down offsets [128] or the column-sum partials [2][128]
+    __shared__ int scratch[POOL ? 256 : TOPDOWN ? 128 : 1];
+    srf_tile128_epilogue<POOL, TOPDOWN, RESID>(SRF_TILE128_EPI(a), acc, it, scratch, tid, li, lh, wm, wn);
 }
 
 extern "C" size_t srf_conv1x1_nhwc_direct_packed_weight_bytes(int Cout, int K)
@@ -243,48 +129,23 @@ extern "C" int srf_conv1x1_nhwc_direct_pack_weights(const float *W, int Cout, in
     return SRF_OK;
 }
 
-static const SrfGemmFamily GEMM_DIRECT = {128, true, 128};   // x and y through descriptors of one 128-row tile
-
-static int gd_launch(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale, const float *shift,
-                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr,
-                     const SrfGemmRes *rd = nullptr)
-{
-    GdArgs a = {};
-    srf_gemm_set_base(a, x, M, K, x_ld, Cout, scale, shift, relu, y, y_ld);
-    a.Wd = W_packed;
-    a.nct = srf_ceil_div(Cout, 128);
-    a.colsum = colsum;
-    a.HW = HW;
-    srf_gemm_set_top(a, td);
-    srf_gemm_set_res(a, rd);
-    if (colsum) {
-        a.bpi = (int)srf_ceil_div(HW, 128);
-        a.mblocks = (M / HW) * a.bpi;
-        if (bpi_out) *bpi_out = a.bpi;
-    } else {
-        a.mblocks = srf_ceil_div(M, 128);
+struct GdFamily {
+    typedef GdArgs Args;
+    static constexpr SrfGemmFamily limits = {128, true, 128};   // x and y through descriptors of one 128-row tile
+    static constexpr void (*plain)(GdArgs) = srf_gemm_direct_k<GD_PLAIN>, (*pool)(GdArgs) = srf_gemm_direct_k<GD_POOL>,
+                          (*topdown)(GdArgs) = srf_gemm_direct_k<GD_TOPDOWN>, (*resid)(GdArgs) = srf_gemm_direct_k<GD_RESID>,
+                          (*conv)(GdArgs) = nullptr;
+    static int set_weights(GdArgs &a, const void *W_packed)
+    {
+        a.Wp = (const float *)W_packed;
+        return srf_conv1x1_nhwc_direct_packed_weight_bytes(a.Cout, a.K) >= ((size_t)1 << 31) ? SRF_EUNSUPPORTED : SRF_OK;   // descriptor range of Wp
     }
-    if (srf_conv1x1_nhwc_direct_packed_weight_bytes(Cout, K) >= ((size_t)1 << 31)) return SRF_EUNSUPPORTED;   // descriptor range of Wd
-    const long long blocks = ((a.mblocks + 7) / 8) * 8 * a.nct;
-    if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    if (colsum)
-        hipLaunchKernelGGL((srf_gemm_direct_k<GD_POOL>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else if (td)
-        hipLaunchKernelGGL((srf_gemm_direct_k<GD_TOPDOWN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else if (rd)
-        hipLaunchKernelGGL((srf_gemm_direct_k<GD_RESID>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((srf_gemm_direct_k<GD_PLAIN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
-}
+};
 
 extern "C" int srf_conv1x1_nhwc_direct(const float *x, long long M, int K, long long x_ld, const float *W_packed, int Cout, const float *scale,
                                        const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream)
 {
-    const int rc = srf_gemm_check_1x1(GEMM_DIRECT, M, K, x_ld, x, W_packed, Cout, y, y_ld);
-    if (rc != SRF_OK || M == 0) return rc;
-    return gd_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr);
+    return srf_tile128_plain<GdFamily>(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, stream);
 }
 
 // the residual form: as srf_conv1x1_nhwc_residual (conv.hip)
@@ -292,20 +153,14 @@ extern "C" int srf_conv1x1_nhwc_direct_residual(const float *x, long long M, int
                                                const float *shift, int relu, float *y, long long y_ld, const float *res, long long res_ld,
                                                srf_stream_t stream)
 {
-    const SrfGemmRes rd = {res, res_ld};
-    const int rc = srf_gemm_check_1x1(GEMM_DIRECT, M, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, nullptr, &rd);
-    if (rc != SRF_OK || M == 0) return rc;
-    return gd_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, nullptr, &rd);
+    return srf_tile128_residual<GdFamily>(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, res, res_ld, stream);
 }
 
 extern "C" int srf_conv1x1_nhwc_direct_topdown(const float *x, int N, int H, int W, int K, long long x_ld, const float *W_packed, int Cout,
                                                const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt,
                                                long long top_ld, float *y, long long y_ld, srf_stream_t stream)
 {
-    const SrfGemmTop td = {top, top_ld, H, W, Ht, Wt};
-    const int rc = srf_gemm_check_1x1(GEMM_DIRECT, N, K, x_ld, x, W_packed, Cout, y, y_ld, &td);
-    if (rc != SRF_OK || N == 0) return rc;
-    return gd_launch(x, (long long)N * H * W, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, &td);
+    return srf_tile128_topdown<GdFamily>(x, N, H, W, K, x_ld, W_packed, Cout, scale, shift, relu, top, Ht, Wt, top_ld, y, y_ld, stream);
 }
 
 // the pooled form: as srf_conv1x1_nhwc_pooled (conv.hip); workspace = srf_conv1x1_nhwc_pooled_workspace_bytes(N, HW, Cout)
@@ -313,12 +168,5 @@ extern "C" int srf_conv1x1_nhwc_direct_pooled(const float *x, int N, long long H
                                               const float *scale, const float *shift, int relu, float *y, long long y_ld, float *mean,
                                               void *workspace, size_t workspace_bytes, srf_stream_t stream)
 {
-    const SrfGemmPool pool = {HW, mean, workspace, workspace_bytes};
-    int rc = srf_gemm_check_1x1(GEMM_DIRECT, N, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, &pool);
-    if (rc != SRF_OK || N == 0) return rc;
-    int bpi = 0;
-    rc = gd_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW, (hipStream_t)stream,
-                   &bpi);
-    if (rc != SRF_OK) return rc;
-    return srf_gemm_pool_finish((const float *)workspace, bpi, N, Cout, HW, mean, (hipStream_t)stream);
+    return srf_tile128_pooled<GdFamily>(x, N, HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, mean, workspace, workspace_bytes, stream);
 }

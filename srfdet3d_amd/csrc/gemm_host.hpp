@@ -1,8 +1,11 @@
-// gemm_host.hpp -- the host front of the three dense GEMM families: srf_conv1x1_nhwc / srf_conv_gemm_nhwc (conv.hip, operands staged
-// through LDS), srf_conv1x1_nhwc_direct (gemm_direct.hip, LDS-free) and srf_conv1x1_nhwc_split / srf_conv_gemm_nhwc_split
-// (gemm_split.hip, bf16 split).  What the entry points share lives here: the argument checks, the top-down descriptor, the fill
-// of the fields the three argument structs (GemmArgs, GdArgs, GsArgs) have in common, and the launch of the one pool-finish kernel.
-// What differs for a measured reason stays with each family: tile forms, grids, the mixed launch, the weight packing.
+// gemm_host.hpp -- the host front of the four dense GEMM families: srf_conv1x1_nhwc / srf_conv_gemm_nhwc (conv.hip, operands staged
+// through LDS), srf_conv1x1_nhwc_direct (gemm_direct.hip, LDS-free), srf_conv1x1_nhwc_split / srf_conv_gemm_nhwc_split (gemm_split.hip,
+// bf16 split) and srf_conv1x1_nhwc_bf16 / srf_conv_gemm_nhwc_bf16 (gemm_bf16.hip, bf16 products).  What every family's entry points
+// share lives here: the argument checks, the top-down / residual / pooled descriptors, the fill of the fields the four argument structs
+// (GemmArgs, GdArgs, GsArgs, GbArgs) have in common, and the launch of the one pool-finish kernel.  gemm_tile128.hpp builds on it for
+// the direct, split and bf16 families, which share one tile shape: their common argument fields, work-item decode, epilogue, launch
+// function and entry-point bodies.  conv.hip keeps its own tile forms, grids and the mixed launch; every family keeps its K loop and
+// its weight packing.
 #pragma once
 #include "common.hpp"
 
@@ -80,7 +83,7 @@ static inline int srf_gemm_check_conv(const SrfGemmFamily &f, int N, int H, int 
     return SRF_OK;
 }
 
-// the fields GemmArgs, GdArgs and GsArgs share; the struct is value-initialised by the caller, which then adds its weight pointer and
+// the fields GemmArgs, GdArgs, GsArgs and GbArgs share; the struct is value-initialised by the caller, which then adds its weight pointer and
 // column-tile count
 template <class Args>
 static inline void srf_gemm_set_base(Args &a, const float *x, long long M, int K, long long x_ld, int Cout, const float *scale,
@@ -123,7 +126,7 @@ static inline void srf_gemm_set_res(Args &a, const SrfGemmRes *rd)
     a.res_ld = rd->res_ld;
 }
 
-// strided-convolution fields of the implicit im2col (GemmArgs, GsArgs)
+// strided-convolution fields of the implicit im2col (GemmArgs, GsArgs, GbArgs)
 template <class Args>
 static inline void srf_gemm_set_conv(Args &a, int H, int W, int Ho, int Wo, int kw, int stride, int pad, int Cin, long long x_bytes)
 {

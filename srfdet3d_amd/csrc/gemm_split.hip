@@ -47,7 +47,7 @@
 // First version measured (same shapes): 189-199 TFLOP/s f32-equivalent (1.13-1.20 PFLOP/s of bf16 issued) on the three large
 // layers against 122-135 for the f32 kernels.
 #include "common.hpp"
-#include "gemm_host.hpp"
+#include "gemm_tile128.hpp"
 
 typedef __bf16 gs_bf2 __attribute__((ext_vector_type(2)));
 typedef __bf16 gs_bf8 __attribute__((ext_vector_type(8)));
@@ -59,26 +59,7 @@ typedef unsigned gs_u4 __attribute__((ext_vector_type(4)));
 
 #define GS_IMG 24576   // bytes of one operand image: 3 planes x 128 rows x 64 B
 
-struct GsArgs {
-    const float *x;
-    float *y;
-    const unsigned char *Wp;
-    const float *scale, *shift;
-    long long x_ld, y_ld, M;
-    int K, Cout, nchunk, nct, relu;
-    long long mblocks;
-    // per-image row tiling + column sums of the stored outputs (eSE pooling): bpi > 0: image n owns row blocks [n bpi, (n + 1) bpi)
-    float *colsum;
-    long long HW;
-    int bpi;
-    // FPN top-down step in the epilogue (as srf_conv1x1_nhwc_topdown): y += top[n][floor(py sy)][floor(px sx)][co]
-    const float *top;
-    long long top_ld;
-    int mapH, mapW, topH, topW;
-    float sy, sx;
-    // residual form (GS_RESID): y = act(fl(fma(acc, scale, shift)) + res[row][co]), the add BEFORE the ReLU (as srf_conv1x1_nhwc_residual)
-    const float *res;
-    long long res_ld;
+struct GsArgs : SrfTile128Args<const unsigned char *> {
     // GS_CONV: rows are OUTPUT pixels (n, oy, ox) of a Conv2d(Cin, Cout, (kh, kw), stride, pad), k runs over (tap, input channel): implicit
     // im2col as in srf_conv_gemm_nhwc (conv.hip); a chunk of 32 channels lies inside one tap (Cin % 32 == 0)
     int H, W, Ho, Wo, kw, stride, pad, cin_chunks;
@@ -133,20 +114,11 @@ __global__ __launch_bounds__(256, MODE == GS_CONV ? 2 : 3) void srf_gemm_split_k
     constexpr bool POOL = MODE == GS_POOL, TOPDOWN = MODE == GS_TOPDOWN, CONV = MODE == GS_CONV, RESID = MODE == GS_RESID;
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * GS_IMG];   // A planes | B planes
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // work item -> (column tile, row block): items b and b + 8 share an XCD, the column tiles of a row block sit on one L2
-    const int xcd = blockIdx.x & 7, jq = blockIdx.x >> 3;
-    const int ct = jq % a.nct;
-    const long long mb = (long long)(jq / a.nct) * 8 + xcd;
+    int ct;
+    const long long mb = srf_tile128_row_block(a.nct, ct);
     if (mb >= a.mblocks) return;
-    long long p0 = mb * 128, rows_blk = a.M - p0;
-    long long slot = mb;
-    if (POOL) {
-        const long long n = mb / a.bpi, lb = mb - n * a.bpi;
-        p0 = n * a.HW + lb * 128;
-        rows_blk = a.HW - lb * 128;
-        slot = n * a.bpi + lb;
-    }
-    const long long rows_here = rows_blk < 128 ? rows_blk : 128;
+    const SrfTile128Item it = srf_tile128_item<POOL>(ct, mb, a.M, a.HW, a.bpi);
+    const long long p0 = it.p0, rows_here = it.rows_here;
     __amdgpu_buffer_rsrc_t xr = CONV ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x), 0, (int)a.x_bytes, 0x00020000)
                                      : __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x) + p0 * a.x_ld, 0, (int)(rows_here * a.x_ld * 4), 0x00020000);
     const int nchunk = a.nchunk;
@@ -274,94 +246,8 @@ __global__ __launch_bounds__(256, MODE == GS_CONV ? 2 : 3) void srf_gemm_split_k
 #undef GS_MM
 #undef GS_MFMA6
 
-    // epilogue (that of srf_gemm_direct_k): lane = channel li of block j, accumulator register = pixel row (r & 3) + 8 (r >> 2) + 4 lh of block i
-    float sc[2], sh[2];
-    bool co_ok[2];
-    const int co0 = ct * 128 + wn * 64 + li;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int co = co0 + j * 32;
-        co_ok[j] = co < a.Cout;
-        sc[j] = (co_ok[j] && a.scale) ? a.scale[co] : 1.f;
-        sh[j] = (co_ok[j] && a.shift) ? a.shift[co] : 0.f;
-    }
-    __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(a.y + p0 * a.y_ld, 0, (int)(rows_here * a.y_ld * 4), 0x00020000);
-    const int row_base = wm * 64 + 4 * lh;
-    unsigned ybase[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) ybase[j] = co_ok[j] ? (unsigned)((row_base * a.y_ld + co0 + j * 32) * 4) : 0x80000000u;
-    const unsigned yrow_b = (unsigned)(a.y_ld * 4);
-    const long long rows_left = rows_blk - row_base;
-    int *s_top = reinterpret_cast<int *>(lds);   // [128]: offset (floats) of the top-level pixel each row of this block adds
-    if (TOPDOWN) {
-        // (the loop's last barrier is behind every fragment read of this workgroup)
-        if (tid < 128) {
-            const long long row = p0 + tid;
-            int off = 0;
-            if (row < a.M) {
-                const int hw = a.mapH * a.mapW;
-                const int n = (int)(row / hw), rem = (int)(row - (long long)n * hw);
-                const int yy = rem / a.mapW, xx = rem - yy * a.mapW;
-                int ys = (int)floorf((float)yy * a.sy), xs = (int)floorf((float)xx * a.sx);
-                if (ys > a.topH - 1) ys = a.topH - 1;
-                if (xs > a.topW - 1) xs = a.topW - 1;
-                off = (int)((((long long)n * a.topH + ys) * a.topW + xs) * a.top_ld);
-            }
-            s_top[tid] = off;
-        }
-        __syncthreads();
-    }
-    float csum[2] = {0.f, 0.f};
-    // RESID: the residual of this block's rows through a descriptor of its own (a row past the block and a channel past Cout read as
-    // zero and are never stored); the 32 values of a row block are requested together, ahead of the stores they feed
-    __amdgpu_buffer_rsrc_t rr;
-    unsigned rbase[2] = {0u, 0u}, rrow_b = 0;
-    if (RESID) {
-        rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.res) + p0 * a.res_ld, 0, (int)(rows_here * a.res_ld * 4), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) rbase[j] = co_ok[j] ? (unsigned)((row_base * a.res_ld + co0 + j * 32) * 4) : 0x80000000u;
-        rrow_b = (unsigned)(a.res_ld * 4);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float rv[RESID ? 16 : 1][RESID ? 2 : 1];
-        if (RESID) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    rv[r][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                        rr, (int)(rbase[j] + (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * rrow_b), 0, 0));
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dr = i * 32 + (r & 3) + 8 * (r >> 2);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float v = __fmaf_rn(acc[i][j][r], sc[j], sh[j]);
-                if (RESID) v = __fadd_rn(v, rv[r][j]);
-                if (a.relu) v = fmaxf(v, 0.f);
-                if (TOPDOWN && co_ok[j]) v = __fadd_rn(v, a.top[s_top[row_base + dr] + co0 + j * 32]);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, (int)(ybase[j] + (unsigned)dr * yrow_b), 0, 0);
-                if (POOL) csum[j] += dr < rows_left ? v : 0.f;
-            }
-        }
-    }
-    if (POOL) {
-        // column sums of the block: the two lane halves of a wave (shuffle), then the two waves that share the columns (LDS), in a
-        // fixed order: reproducible bit for bit
-        float *red = reinterpret_cast<float *>(lds);   // [2][128]
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float o = __shfl_xor(csum[j], 32);
-            if (lh == 0) red[wm * 128 + wn * 64 + j * 32 + li] = csum[j] + o;
-        }
-        __syncthreads();
-        if (tid < 128) {
-            const int co = ct * 128 + tid;
-            if (co < a.Cout) a.colsum[slot * a.Cout + co] = red[tid] + red[128 + tid];
-        }
-    }
+    // the frame's scratch is the operand image: the loop's last barrier is behind every fragment read of this workgroup
+    srf_tile128_epilogue<POOL, TOPDOWN, RESID>(SRF_TILE128_EPI(a), acc, it, lds, tid, li, lh, wm, wn);
 }
 
 extern "C" size_t srf_conv1x1_nhwc_split_packed_weight_bytes(int Cout, int K)
@@ -382,48 +268,18 @@ extern "C" int srf_conv1x1_nhwc_split_pack_weights(const float *W, int Cout, int
     return SRF_OK;
 }
 
-static const SrfGemmFamily GEMM_SPLIT = {128, true, 128};   // x and y through descriptors of one 128-row tile
-
-// the fields every launch of this family sets; the rest of GsArgs starts as zero
-static GsArgs gs_args(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale, const float *shift,
-                      int relu, float *y, long long y_ld)
-{
-    GsArgs a = {};
-    srf_gemm_set_base(a, x, M, K, x_ld, Cout, scale, shift, relu, y, y_ld);
-    a.Wp = (const unsigned char *)W_packed;
-    a.nct = srf_ceil_div(Cout, 128);
-    return a;
-}
-
-static int gs_launch(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale, const float *shift,
-                     int relu, float *y, long long y_ld, float *colsum, long long HW, hipStream_t stream, int *bpi_out, const SrfGemmTop *td = nullptr,
-                     const SrfGemmRes *rd = nullptr)
-{
-    GsArgs a = gs_args(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
-    a.colsum = colsum;
-    a.HW = HW;
-    srf_gemm_set_top(a, td);
-    srf_gemm_set_res(a, rd);
-    if (colsum) {
-        a.bpi = (int)srf_ceil_div(HW, 128);
-        a.mblocks = (M / HW) * a.bpi;
-        if (bpi_out) *bpi_out = a.bpi;
-    } else {
-        a.mblocks = srf_ceil_div(M, 128);
+struct GsFamily {
+    typedef GsArgs Args;
+    static constexpr SrfGemmFamily limits = {128, true, 128};   // x and y through descriptors of one 128-row tile
+    static constexpr void (*plain)(GsArgs) = srf_gemm_split_k<GS_PLAIN>, (*pool)(GsArgs) = srf_gemm_split_k<GS_POOL>,
+                          (*topdown)(GsArgs) = srf_gemm_split_k<GS_TOPDOWN>, (*resid)(GsArgs) = srf_gemm_split_k<GS_RESID>,
+                          (*conv)(GsArgs) = srf_gemm_split_k<GS_CONV>;
+    static int set_weights(GsArgs &a, const void *W_packed)
+    {
+        a.Wp = (const unsigned char *)W_packed;
+        return SRF_OK;
     }
-    const long long blocks = ((a.mblocks + 7) / 8) * 8 * a.nct;
-    if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    if (colsum)
-        hipLaunchKernelGGL((srf_gemm_split_k<GS_POOL>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else if (td)
-        hipLaunchKernelGGL((srf_gemm_split_k<GS_TOPDOWN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else if (rd)
-        hipLaunchKernelGGL((srf_gemm_split_k<GS_RESID>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((srf_gemm_split_k<GS_PLAIN>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
-}
+};
 
 // srf_conv_gemm_nhwc_split: Conv2d(Cin, Cout, (kh, kw), stride, padding) on channels-last activations as the split GEMM with an
 // implicit im2col (the stride-2 3x3 layers: VoVNet stem_3, SECONDCustom's second block, the BEV FPN extras -- the layers
@@ -433,26 +289,13 @@ extern "C" int srf_conv_gemm_nhwc_split(const float *x, int N, int H, int W, int
                                         int kw, int stride, int pad, const float *scale, const float *shift, int relu, float *y,
                                         long long y_ld, srf_stream_t stream)
 {
-    int Ho = 0, Wo = 0;
-    long long x_bytes = 0;
-    const int rc = srf_gemm_check_conv(GEMM_SPLIT, N, H, W, Cin, x_ld, x, W_packed, Cout, kh, kw, stride, pad, y, y_ld, &Ho, &Wo, &x_bytes);
-    if (rc != SRF_OK || N == 0) return rc;
-    GsArgs a = gs_args(x, (long long)N * Ho * Wo, kh * kw * Cin, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld);
-    srf_gemm_set_conv(a, H, W, Ho, Wo, kw, stride, pad, Cin, x_bytes);
-    a.mblocks = srf_ceil_div(a.M, 128);
-    const long long blocks = ((a.mblocks + 7) / 8) * 8 * a.nct;
-    if (blocks >= (1ll << 31)) return SRF_EUNSUPPORTED;
-    hipLaunchKernelGGL((srf_gemm_split_k<GS_CONV>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    SRF_LAUNCH_CHECK();
-    return SRF_OK;
+    return srf_tile128_conv<GsFamily>(x, N, H, W, Cin, x_ld, W_packed, Cout, kh, kw, stride, pad, scale, shift, relu, y, y_ld, stream);
 }
 
 extern "C" int srf_conv1x1_nhwc_split(const float *x, long long M, int K, long long x_ld, const void *W_packed, int Cout, const float *scale,
                                       const float *shift, int relu, float *y, long long y_ld, srf_stream_t stream)
 {
-    const int rc = srf_gemm_check_1x1(GEMM_SPLIT, M, K, x_ld, x, W_packed, Cout, y, y_ld);
-    if (rc != SRF_OK || M == 0) return rc;
-    return gs_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr);
+    return srf_tile128_plain<GsFamily>(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, stream);
 }
 
 // the residual form: as srf_conv1x1_nhwc_residual (conv.hip)
@@ -460,20 +303,14 @@ extern "C" int srf_conv1x1_nhwc_split_residual(const float *x, long long M, int 
                                                const float *shift, int relu, float *y, long long y_ld, const float *res, long long res_ld,
                                                srf_stream_t stream)
 {
-    const SrfGemmRes rd = {res, res_ld};
-    const int rc = srf_gemm_check_1x1(GEMM_SPLIT, M, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, nullptr, &rd);
-    if (rc != SRF_OK || M == 0) return rc;
-    return gs_launch(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, nullptr, &rd);
+    return srf_tile128_residual<GsFamily>(x, M, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, res, res_ld, stream);
 }
 
 extern "C" int srf_conv1x1_nhwc_split_topdown(const float *x, int N, int H, int W, int K, long long x_ld, const void *W_packed, int Cout,
                                               const float *scale, const float *shift, int relu, const float *top, int Ht, int Wt,
                                               long long top_ld, float *y, long long y_ld, srf_stream_t stream)
 {
-    const SrfGemmTop td = {top, top_ld, H, W, Ht, Wt};
-    const int rc = srf_gemm_check_1x1(GEMM_SPLIT, N, K, x_ld, x, W_packed, Cout, y, y_ld, &td);
-    if (rc != SRF_OK || N == 0) return rc;
-    return gs_launch(x, (long long)N * H * W, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, nullptr, 0, (hipStream_t)stream, nullptr, &td);
+    return srf_tile128_topdown<GsFamily>(x, N, H, W, K, x_ld, W_packed, Cout, scale, shift, relu, top, Ht, Wt, top_ld, y, y_ld, stream);
 }
 
 // the pooled form: as srf_conv1x1_nhwc_pooled (conv.hip); workspace = srf_conv1x1_nhwc_pooled_workspace_bytes(N, HW, Cout)
@@ -481,12 +318,5 @@ extern "C" int srf_conv1x1_nhwc_split_pooled(const float *x, int N, long long HW
                                              const float *scale, const float *shift, int relu, float *y, long long y_ld, float *mean,
                                              void *workspace, size_t workspace_bytes, srf_stream_t stream)
 {
-    const SrfGemmPool pool = {HW, mean, workspace, workspace_bytes};
-    int rc = srf_gemm_check_1x1(GEMM_SPLIT, N, K, x_ld, x, W_packed, Cout, y, y_ld, nullptr, &pool);
-    if (rc != SRF_OK || N == 0) return rc;
-    int bpi = 0;
-    rc = gs_launch(x, (long long)N * HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, (float *)workspace, HW, (hipStream_t)stream,
-                   &bpi);
-    if (rc != SRF_OK) return rc;
-    return srf_gemm_pool_finish((const float *)workspace, bpi, N, Cout, HW, mean, (hipStream_t)stream);
+    return srf_tile128_pooled<GsFamily>(x, N, HW, K, x_ld, W_packed, Cout, scale, shift, relu, y, y_ld, mean, workspace, workspace_bytes, stream);
 }

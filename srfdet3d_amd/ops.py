@@ -1201,13 +1201,14 @@ def pack_wino3x3_weights(weight):
 
 
 def quads_ok(n):
-    """A channel count or pixel pitch in whole float4s: `x_ld & 3` of every channels-last entry (csrc/conv.hip:946, csrc/gemm_host.hpp:56,
-    :74), `C & 3` of the streaming kernels (csrc/nhwc.hip:65)."""
+    """A channel count or pixel pitch in whole float4s: `x_ld & 3` of every channels-last entry (csrc/conv.hip:946; csrc/gemm_host.hpp,
+    `srf_gemm_check_1x1` and `srf_gemm_check_conv`: `x_ld & 3`), `C & 3` of the streaming kernels (csrc/nhwc.hip:65)."""
     return n % 4 == 0
 
 
 def operand_ok(ld, addr):
-    """An operand the kernels read in float4s: pitch `ld` in quads from a 16-byte aligned address (csrc/conv.hip:946, csrc/gemm_host.hpp:56, :74)."""
+    """An operand the kernels read in float4s: pitch `ld` in quads from a 16-byte aligned address (csrc/conv.hip:946; csrc/gemm_host.hpp,
+    `srf_gemm_check_1x1` and `srf_gemm_check_conv`: `x_ld & 3`, `(uintptr_t)x & 15`)."""
     return quads_ok(ld) and addr % 16 == 0
 
 
@@ -1384,17 +1385,19 @@ _GEMM_KINDS = {
 
 
 def gemm_k_ok(K):
-    """Every family reads K in chunks of 32 (csrc/gemm_host.hpp:56, :74)."""
+    """Every family reads K in chunks of 32 (csrc/gemm_host.hpp, `srf_gemm_check_1x1`: `K & 31`; `srf_gemm_check_conv`: `Cin & 31`)."""
     return K % 32 == 0
 
 
 def gemm_rows_ok(ld):
-    """128 rows of pitch `ld` floats inside the 2^31-byte descriptor of the direct, split and bf16 families (csrc/gemm_host.hpp:58)."""
+    """128 rows of pitch `ld` floats inside the 2^31-byte descriptor of the direct, split and bf16 families (csrc/gemm_host.hpp,
+    `srf_gemm_check_1x1`: `x_ld * f.tile_rows * 4 >= 2^31`)."""
     return ld * 512 < (1 << 31)
 
 
 def below_2gb(pixels, ld):
-    """`pixels` rows of `ld` floats below 2 GB: the implicit-im2col input (csrc/gemm_host.hpp:79), the weight gradient's operands (csrc/wgrad.hip:337)."""
+    """`pixels` rows of `ld` floats below 2 GB: the implicit-im2col input (csrc/gemm_host.hpp, `srf_gemm_check_conv`: `*x_bytes >= 2^31`), the weight
+    gradient's operands (csrc/wgrad.hip:337)."""
     return 4 * pixels * ld < (1 << 31)
 
 

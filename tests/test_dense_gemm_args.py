@@ -109,6 +109,22 @@ def test_first_y_ld_at_the_range_limit(L):
         assert call(L, form, fam, y_ld=1 << 22) == EUNSUPPORTED, (form, fam)
 
 
+def test_conv_reduction_length_past_the_int_range(L):
+    """kh * kw * Cin is the K of the implicit im2col and an int in the kernels' arguments: 64 * 64 * 2^20 = 2^32 is refused by the split
+    and the bf16-product form (one shared body, csrc/gemm_tile128.hpp `srf_tile128_conv`), after every check of `srf_gemm_check_conv`
+    has passed (4 MiB of input, 2 x 2 output pixels); one tap less in each direction of a 2^19-channel input (63 * 63 * 2^19 < 2^31)
+    is not what this row refuses, and a null pointer is still answered first."""
+    big = dict(N=1, H=1, W=1, K=1 << 20, x_ld=1 << 20, kh=64, kw=64, stride=1, pad=32)
+    a = dict(BASE, **big)
+    for name in ("srf_conv_gemm_nhwc_split", "srf_conv_gemm_nhwc_bf16"):
+        fn = getattr(L, name)
+        args = lambda a: (a["x"], a["N"], a["H"], a["W"], a["K"], a["x_ld"], a["Wp"], a["Cout"], a["kh"], a["kw"], a["stride"], a["pad"],  # noqa: E731
+                          None, None, 0, a["y"], a["y_ld"], None)
+        assert fn(*args(a)) == EUNSUPPORTED, name
+        assert fn(*args(dict(a, x=None))) == EINVAL, name
+        assert fn(*args(dict(a, N=0))) == OK, name
+
+
 def test_workspace_one_byte_below_the_bound_of_each_family(L):
     """N * ceil(HW / block rows) * Cout * 4 bytes: blocks of 64 rows in the LDS family (srf_conv1x1_nhwc_pooled_workspace_bytes),
     of 128 in the other two."""

@@ -66,10 +66,10 @@ def test_gate_verdict_is_the_recorded_one(row):
 # (function, arguments, verdict, reason)
 LIMITS = [
     (ops.quads_ok, (64,), True, "csrc/conv.hip:907"),
-    (ops.quads_ok, (66,), False, "66 & 3 (csrc/conv.hip:907, csrc/gemm_host.hpp:48, csrc/nhwc.hip:65)"),
-    (ops.operand_ok, (64, 4096), True, "csrc/gemm_host.hpp:48"),
-    (ops.operand_ok, (64, 4104), False, "8 bytes past a 16-byte boundary: (uintptr_t)x & 15 (csrc/conv.hip:907, csrc/gemm_host.hpp:48, :64)"),
-    (ops.operand_ok, (62, 4096), False, "x_ld & 3 (csrc/conv.hip:907, csrc/gemm_host.hpp:48, :64)"),
+    (ops.quads_ok, (66,), False, "66 & 3 (csrc/conv.hip:907; srf_gemm_check_1x1: x_ld & 3, csrc/gemm_host.hpp; csrc/nhwc.hip:65)"),
+    (ops.operand_ok, (64, 4096), True, "srf_gemm_check_1x1: x_ld & 3, (uintptr_t)x & 15 (csrc/gemm_host.hpp)"),
+    (ops.operand_ok, (64, 4104), False, "8 bytes past a 16-byte boundary: (uintptr_t)x & 15 (csrc/conv.hip:907; srf_gemm_check_1x1 and srf_gemm_check_conv, csrc/gemm_host.hpp)"),
+    (ops.operand_ok, (62, 4096), False, "x_ld & 3 (csrc/conv.hip:907; srf_gemm_check_1x1 and srf_gemm_check_conv, csrc/gemm_host.hpp)"),
     (ops.wino3x3_channels_ok, (8,), True, "csrc/conv.hip:885"),
     (ops.wino3x3_channels_ok, (12,), False, "12 & 7: srf_wino3x3_packed_weight_bytes answers 0 (csrc/conv.hip:885), the launch refuses (:907)"),
     (ops.wino3x3_range_ok, ((1 << 22) - 1, 64), True, "256 (2^22 - 1) = 2^30 - 256 (csrc/conv.hip:909)"),
@@ -81,8 +81,8 @@ LIMITS = [
     (ops.ese_channels_ok, (1024,), True, "as the gate held it: out_channels <= 1024"),
     (ops.ese_channels_ok, (1028,), False, "as the gate held it: out_channels > 1024 (the bound of srf_nhwc_colmean, csrc/nhwc.hip:137)"),
     (ops.ese_channels_ok, (1022,), False, "C & 3: srf_ese_gate (csrc/decoder.hip:427), srf_nhwc_affine (csrc/nhwc.hip:65)"),
-    (ops.gemm_k_ok, (768,), True, "the 768-wide buffer of a stage-2 block of V-99-eSE (csrc/gemm_host.hpp:48)"),
-    (ops.gemm_k_ok, (720,), False, "the stage-5 buffer of V-19-slim-eSE: 720 & 31 (csrc/gemm_host.hpp:48)"),
+    (ops.gemm_k_ok, (768,), True, "the 768-wide buffer of a stage-2 block of V-99-eSE (srf_gemm_check_1x1: K & 31, csrc/gemm_host.hpp)"),
+    (ops.gemm_k_ok, (720,), False, "the stage-5 buffer of V-19-slim-eSE: 720 & 31 (srf_gemm_check_1x1: K & 31, csrc/gemm_host.hpp)"),
     # the executor applies the range of srf_wino3x3 to every buffer a 3x3 layer reads, whichever Winograd kernel runs the layer
     (nhwc._img_fits, (1024, 1024, 255), True, "`4 * H * W * ld < (1 << 30)`, as the gates held it"),
     (nhwc._img_fits, (1024, 1024, 256), False, "2^30 (csrc/conv.hip:909)"),

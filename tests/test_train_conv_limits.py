@@ -38,18 +38,18 @@ WINO43 = [
 ]
 
 GEMM = [
-    (ops.gemm_k_ok, (48,), False, "K & 31 (csrc/gemm_host.hpp:48)"),
-    (ops.gemm_k_ok, (32,), True, "csrc/gemm_host.hpp:48"),
+    (ops.gemm_k_ok, (48,), False, "srf_gemm_check_1x1: K & 31 (csrc/gemm_host.hpp)"),
+    (ops.gemm_k_ok, (32,), True, "srf_gemm_check_1x1: K & 31 (csrc/gemm_host.hpp)"),
     (ops.gemm_k_ok, (1056,), True, "33 * 32"),
-    (ops.gemm_rows_ok, ((1 << 22) - 1,), True, "128 rows x (2^22 - 1) floats x 4 B < 2^31 (csrc/gemm_host.hpp:49)"),
-    (ops.gemm_rows_ok, (1 << 22,), False, "128 rows x 2^22 floats x 4 B = 2^31 (csrc/gemm_host.hpp:49)"),
-    (ops.below_2gb, ((1 << 29) - 1, 1), True, "4 (2^29 - 1) < 2^31 (csrc/wgrad.hip:337, csrc/gemm_host.hpp:69)"),
-    (ops.below_2gb, (1 << 29, 1), False, "4 * 2^29 = 2^31 (csrc/wgrad.hip:337, csrc/gemm_host.hpp:69)"),
+    (ops.gemm_rows_ok, ((1 << 22) - 1,), True, "128 rows x (2^22 - 1) floats x 4 B < 2^31 (srf_gemm_check_1x1: x_ld * f.tile_rows * 4 >= 2^31, csrc/gemm_host.hpp)"),
+    (ops.gemm_rows_ok, (1 << 22,), False, "128 rows x 2^22 floats x 4 B = 2^31 (srf_gemm_check_1x1: x_ld * f.tile_rows * 4 >= 2^31, csrc/gemm_host.hpp)"),
+    (ops.below_2gb, ((1 << 29) - 1, 1), True, "4 (2^29 - 1) < 2^31 (csrc/wgrad.hip:337; srf_gemm_check_conv: *x_bytes >= 2^31, csrc/gemm_host.hpp)"),
+    (ops.below_2gb, (1 << 29, 1), False, "4 * 2^29 = 2^31 (csrc/wgrad.hip:337; srf_gemm_check_conv: *x_bytes >= 2^31, csrc/gemm_host.hpp)"),
     # a 1x1 layer on the GEMMs in three directions: the predicates held Cin % 32, Cout % 32, Cout <= 1024, H W > 1 and
     # N H W max(Cin, Cout) 512 < (1 << 31) 128
     (train_conv.gemm_layer_ok, (2, 8, 8, 32, 32), True, "`fused_eligible`, `conv2d`"),
-    (train_conv.gemm_layer_ok, (2, 8, 8, 48, 32), False, "K = 48 forward (csrc/gemm_host.hpp:48)"),
-    (train_conv.gemm_layer_ok, (2, 8, 8, 32, 48), False, "K = 48 in the data gradient (csrc/gemm_host.hpp:48)"),
+    (train_conv.gemm_layer_ok, (2, 8, 8, 48, 32), False, "K = 48 forward (srf_gemm_check_1x1: K & 31, csrc/gemm_host.hpp)"),
+    (train_conv.gemm_layer_ok, (2, 8, 8, 32, 48), False, "K = 48 in the data gradient (srf_gemm_check_1x1: K & 31, csrc/gemm_host.hpp)"),
     (train_conv.gemm_layer_ok, (2, 8, 8, 32, 1024), True, "Cout <= 1024"),
     (train_conv.gemm_layer_ok, (2, 8, 8, 32, 1056), False, "Cout <= 1024 (`fused_eligible`, `conv2d`)"),
     (train_conv.gemm_layer_ok, (1, 1 << 12, (1 << 12) - 1, 32, 32), True, "(2^24 - 2^12) 32 512 < 2^31 128"),
