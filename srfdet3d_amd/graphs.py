@@ -260,16 +260,8 @@ class GraphedFrame:
         else:
             p, pc = m.voxelize([pts])
             vf, coors = m.pts_voxel_encoder(p, pc)
-        enc = m.pts_middle_encoder
-        from .sparse import SparseConvTensor, _SparseConv
-        sizes = {}
-        hooks = []
-        for mod in enc.modules():
-            if isinstance(mod, _SparseConv) and not mod.subm:
-                hooks.append(mod.register_forward_hook(lambda mm, a, out: sizes.__setitem__(mm.indice_key, out.indices.shape[0])))
-        bev = enc(vf, coors, 1)
-        for h in hooks:
-            h.remove()
+        bev, level = m.pts_middle_encoder.forward_levels(vf, coors, 1)
+        sizes = {key: out.indices.shape[0] for key, out in level.chain()}
         if m.pts_voxel_layer.max_num_points == -1:
             sizes["__voxels__"] = coors.shape[0]
         return bev, sizes

@@ -1,14 +1,16 @@
 """`SparseEncoderCustom` (mmdet3d_plugin/models/middle_encoders/sparse_encoder_custom.py:19-216): the 3-D sparse
 conv encoder that turns voxel features into the dense BEV map.  Same constructor arguments, same module names
 (conv_input / encoder_layers.encoder_layer{i} / conv_out), so checkpoints load by key."""
+import os
+
 import torch
 
 from ..compat.cnn import BaseModule
 from ..compat.registry import MIDDLE_ENCODERS
-from ..sparse import SparseBasicBlock, SparseConvTensor, SparseSequential, make_sparse_convmodule
+from ..sparse import SparseBasicBlock, SparseConvTensor, SparseSequential, _SparseConv, make_sparse_convmodule
 
 
-_INDEX_STREAMS = {}   # device index -> the stream the index-only dry pass of `_layers` runs on
+_INDEX_STREAMS = {}   # device index -> the stream the index pass of `_layers` runs on
 
 
 @MIDDLE_ENCODERS.register_module()
@@ -74,29 +76,41 @@ class SparseEncoderCustom(BaseModule):
         static_caps ({indice_key of a strided conv: rows}): fixed-shape execution for hipGraph replay -- `coors` may hold
         padding rows (b < 0), every level is padded to its capacity, nothing is read back to the host; returns
         (bev, [(indice_key, device count, capacity), ...]) and the caller checks the counts afterwards."""
+        bev, level = self.forward_levels(voxel_features, coors, batch_size, static_caps)
+        return bev if static_caps is None else (bev, [(key, out.rows_dev, static_caps[key]) for key, out in level.chain()])
+
+    def forward_levels(self, voxel_features, coors, batch_size, static_caps=None):
+        """-> (BEV map, the input sparse.Level): its `chain()` holds the level every strided conv produced."""
         coors = coors.int()
-        if static_caps is not None:
-            x = SparseConvTensor.sorted_by_bitmap(voxel_features, coors, self.sparse_shape, int(batch_size), static_caps)
-            static = x.indice_dict["static"]
-            return self._layers(x).dense_bev(), static["counts"]
-        if self.spatial_sort and coors.is_cuda and coors.shape[0] > 0:
+        if static_caps is not None or (self.spatial_sort and coors.is_cuda and coors.shape[0] > 0):
             # rows into (b, y, x, z) order + the level's occupancy bitmap: all rulebooks below are built by bitmap rank
-            x = SparseConvTensor.sorted_by_bitmap(voxel_features, coors, self.sparse_shape, int(batch_size))
+            x = SparseConvTensor.sorted_by_bitmap(voxel_features, coors, self.sparse_shape, int(batch_size), static_caps)
         else:
             x = SparseConvTensor(voxel_features, coors, self.sparse_shape, int(batch_size))
-        return self._layers(x).dense_bev()
+        return self._layers(x).dense_bev(), x.level
+
+    def _modules_in_order(self):
+        return [self.conv_input] + list(self.encoder_layers._modules.values()) + [self.conv_out]
+
+    def index_pass(self, level):
+        """Builds the rulebooks and row plans of every layer from `level` down, one step per top-level module (`modules()` gives the
+        convolutions of a SparseSequential or SparseBasicBlock in the order their forward runs them)."""
+        for m in self._modules_in_order():
+            for conv in m.modules():
+                if isinstance(conv, _SparseConv):
+                    level = conv.index(level)[2]
+            yield
 
     def _layers(self, x):
         """conv_input -> encoder stages -> conv_out.  Static-shape inference on the GPU: the rulebooks of ALL levels depend on the
-        coordinates alone, so an index-only dry pass builds them on a second stream (~40 launches of ~5 us: marks, rank scans,
-        emits, pair tables, row ranges) while this stream runs the convolutions of the levels already indexed; each module waits
-        for the event behind its own rulebooks.  (Eager levels read their sizes back to the host inside the rulebook calls: no
-        overlap to gain there.)  Measured: nusc_L 252.3 -> 256.0 frames/s (same box, alternating); on LC, where the BEV half replays beside
-        the camera graph, the forked graph LOST 3 % (29.9 -> 29.0), so graphs.GraphedFrame switches it off there
-        (`self.index_stream = False`).  SRF_SPARSE_INDEX_STREAM=0 keeps everything on one stream."""
-        import os
-        mods = [self.conv_input] + list(self.encoder_layers._modules.values()) + [self.conv_out]
-        if not (x.features.is_cuda and "static" in x.indice_dict and not torch.is_grad_enabled()
+        coordinates alone, so `index_pass` builds them on a second stream (~40 launches of ~5 us: marks, rank scans, emits, pair tables,
+        row ranges) while this stream runs the convolutions of the levels already indexed; each module waits for the event behind its
+        own rulebooks.  (Eager levels read their sizes back to the host inside the rulebook calls: no overlap to gain there.)  Measured:
+        nusc_L 252.3 -> 256.0 frames/s (same box, alternating); on LC, where the BEV half replays beside the camera graph, the forked graph
+        LOST 3 % (29.9 -> 29.0), so graphs.GraphedFrame switches it off there (`self.index_stream = False`).
+        SRF_SPARSE_INDEX_STREAM=0 keeps everything on one stream."""
+        mods = self._modules_in_order()
+        if not (x.features.is_cuda and x.level.caps is not None and not torch.is_grad_enabled()
                 and getattr(self, "index_stream", True) and os.environ.get("SRF_SPARSE_INDEX_STREAM", "1") != "0"):
             for m in mods:
                 x = m(x)
@@ -108,9 +122,7 @@ class SparseEncoderCustom(BaseModule):
         side.wait_stream(cur)
         events = []
         with torch.cuda.stream(side):
-            xi = SparseConvTensor(None, x.indices, x.spatial_shape, x.batch_size, x.indice_dict, x.num_rows)
-            for m in mods:
-                xi = m(xi)
+            for _ in self.index_pass(x.level):
                 ev = torch.cuda.Event()
                 ev.record(side)
                 events.append(ev)

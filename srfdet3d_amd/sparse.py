@@ -8,10 +8,12 @@ bias=False, indice_key)`, `SparseSequential`, and mmdet3d's `SparseBasicBlock` /
 checkpoints load by key; spconv 2.x layout (Cout,kD,kH,kW,Cin) is converted on load.
 
 What is different from spconv, by design:
-  * rulebooks are output-stationary neighbour tables (K, A_out) and are cached per coordinate set, so the 16
-    un-keyed SubM convs of the basic blocks (which the reference rebuilds from scratch) share one table per level;
+  * a SparseConvTensor is features on a `Level`, one active coordinate set, which owns its bitmap or hash table, a `Rulebook`
+    (output-stationary neighbour table (K, A_out), pair counts, row plans) per SubM kernel size and, per strided conv, the rulebook
+    and the Level it produces: the 16 un-keyed SubM convs of the basic blocks (rebuilt from scratch by the reference) share one;
   * in eval mode conv -> BatchNorm1d -> ReLU (and the residual add of SparseBasicBlock) run as ONE kernel.
 """
+import functools
 import math
 
 import torch
@@ -29,60 +31,100 @@ def _triple(v):
     return [int(v)] * 3
 
 
-class SparseConvTensor:
-    def __init__(self, features, indices, spatial_shape, batch_size, indice_dict=None, num_rows=None):
-        # num_rows: device int with the number of real rows when the arrays are padded to a capacity (static shapes)
-        self.num_rows = num_rows
-        self.features = features
+class Rulebook:
+    """The neighbour table `nbr` (K, A_out) of one kernel on one level, its pair counts, and the row plans its layers asked for."""
+
+    def __init__(self, nbr, counts):
+        self.nbr, self.counts, self._plans = nbr, counts, {}
+
+    def plan(self, cin, cout, K, subm, rows_dev):
+        """What a packed-weight layer passes as `tiles=`, built once per rulebook: balanced row ranges, shared by the SubM layers of a
+        level (a 27-offset strided conv gains more from them than they cost: 64 -> 128 on the nuScenes encoder 92 -> 76 us; conv_out, 3
+        offsets, runs on equal-height tiles); 32-channel layers: a mask-sorted row order, from ~100k rows up (Waymo's levels); or None."""
+        if not (ops.spconv_tiles_wanted(cin, cout) and self.nbr.shape[1] > 0 and (subm or K == 27)):
+            return None
+        kind = "tiles" if cout != 32 else "order" if ops.spconv_order_wanted(cin, cout, rows=self.nbr.shape[1]) else None
+        if kind is not None and kind not in self._plans:
+            self._plans[kind] = getattr(ops, "spconv_" + kind)(self.nbr, rows_dev)
+        return self._plans.get(kind)
+
+
+class Level:
+    """One active coordinate set `indices` (A, 4) int32 (b, z, y, x) and what is derived from it: its occupancy `bitmap` (ops.BitmapLevel)
+    if the rows are sorted by (b, y, x, z), else a hash table built on first use; its rulebooks; the levels of its strided convs.  Static
+    shapes (whole-frame hipGraph; `caps`: {indice_key of a strided conv: rows}): `indices` is padded with rows of -1 to a capacity,
+    `rows_dev` is the device count of the real ones, every strided conv gives caps[indice_key] rows, nothing is read back to the host."""
+
+    def __init__(self, indices, spatial_shape, batch_size, bitmap=None, table=None, rows_dev=None, caps=None):
         self.indices = indices if indices.dtype == torch.int32 else indices.int()
-        self.spatial_shape = [int(s) for s in spatial_shape]
-        self.batch_size = int(batch_size)
-        self.indice_dict = indice_dict if indice_dict is not None else {}
+        self.spatial_shape, self.batch_size = [int(s) for s in spatial_shape], int(batch_size)
+        self.bitmap, self.rows_dev, self.caps = bitmap, rows_dev, caps
+        self._table, self._subm, self._strided = table, {}, {}
+
+    @staticmethod
+    def sorted(indices, spatial_shape, batch_size, static_caps=None):
+        """Distinct active sites -> (their Level in (b, y, x, z) order with its bitmap, `order`: sorted row r is given row order[r]).
+        static_caps: the capacities of the levels below plus "__rows__", the device count of the rows of `indices` that are no padding."""
+        bitmap, order, sorted_idx = ops.bitmap_build(indices if indices.dtype == torch.int32 else indices.int(), spatial_shape,
+                                                     batch_size, padded=static_caps is not None)
+        caps = None if static_caps is None else {k: v for k, v in static_caps.items() if k != "__rows__"}
+        return Level(sorted_idx, spatial_shape, batch_size, bitmap, rows_dev=(static_caps or {}).get("__rows__"), caps=caps), order
+
+    def subm(self, ksize):
+        """The SubM rulebook of this level, shared by all its layers of that kernel size."""
+        rb = self._subm.get(tuple(ksize))
+        if rb is None:
+            if self.bitmap is not None:   # (static shapes: nobody reads the pair counts)
+                rb = Rulebook(*ops.rulebook_subm_bitmap(self.indices, self.bitmap, ksize, want_counts=self.caps is None))
+            else:
+                if self._table is None:
+                    self._table = ops.coord_table_build(self.indices, self.spatial_shape, self.batch_size)
+                rb = Rulebook(*ops.rulebook_subm(self.indices, self.spatial_shape, ksize, self._table))
+            self._subm[tuple(ksize)] = rb
+        return rb
+
+    def strided(self, indice_key, ksize, stride, pad):
+        """-> (Rulebook, output Level) of a strided conv on this level."""
+        key = (indice_key, tuple(ksize), tuple(stride), tuple(pad))
+        if key not in self._strided:
+            if self.bitmap is not None and self.caps is not None:
+                out_idx, nbr, counts, bitmap, oshape, rows_dev = ops.rulebook_strided_bitmap(
+                    self.indices, self.bitmap, ksize, stride, pad, out_capacity=self.caps[indice_key])
+                out = Level(out_idx, oshape, self.batch_size, bitmap, rows_dev=rows_dev, caps=self.caps)
+            elif self.bitmap is not None:
+                out_idx, nbr, counts, bitmap, oshape = ops.rulebook_strided_bitmap(self.indices, self.bitmap, ksize, stride, pad)
+                out = Level(out_idx, oshape, self.batch_size, bitmap)
+            else:
+                out_idx, nbr, counts, table, oshape = ops.rulebook_strided(self.indices, self.spatial_shape, self.batch_size, ksize, stride, pad)
+                out = Level(out_idx, oshape, self.batch_size, table=table)
+            self._strided[key] = Rulebook(nbr, counts), out
+        return self._strided[key]
+
+    def chain(self):
+        """(indice_key, output Level) of every strided conv run from here down, in the order they ran."""
+        for key, (_, out) in self._strided.items():
+            yield key[0], out
+            yield from out.chain()
+
+
+class SparseConvTensor:
+    def __init__(self, features, indices=None, spatial_shape=None, batch_size=None, level=None):
+        self.features, self.level = features, level if level is not None else Level(indices, spatial_shape, batch_size)
+
+    indices = property(lambda self: self.level.indices)
+    spatial_shape = property(lambda self: self.level.spatial_shape)
+    batch_size = property(lambda self: self.level.batch_size)
 
     def replace_feature(self, features):
-        return SparseConvTensor(features, self.indices, self.spatial_shape, self.batch_size, self.indice_dict, self.num_rows)
-
-    # coordinate table / SubM rulebook of this tensor's active set, built once and shared along the layer chain
-    def _level_key(self):
-        return (self.indices.data_ptr(), self.indices.shape[0], tuple(self.spatial_shape))
-
-    def coord_table(self):
-        key = ("table",) + self._level_key()
-        if key not in self.indice_dict:
-            self.indice_dict[key] = ops.coord_table_build(self.indices, self.spatial_shape, self.batch_size)
-        return self.indice_dict[key]
-
-    def bitmap_level(self):
-        """The level's occupancy bitmap if the rows are known to be sorted by (b, y, x, z) (see `sorted_by_bitmap`)."""
-        return self.indice_dict.get(("bitmap",) + self._level_key())
+        return SparseConvTensor(features, level=self.level)
 
     @staticmethod
     def sorted_by_bitmap(features, indices, spatial_shape, batch_size, static_caps=None):
-        """Reorders distinct active sites into (b, y, x, z) order and attaches the level's bitmap: every rulebook down the
+        """Reorders distinct active sites into (b, y, x, z) order on a Level with a bitmap: every rulebook down the
         layer chain is then built by bitmap rank (ops.rulebook_*_bitmap) instead of hash tables, and every active
         set stays sorted.  The dense result of an encoder does not depend on the row order."""
-        lvl, order, sorted_idx = ops.bitmap_build(indices if indices.dtype == torch.int32 else indices.int(), spatial_shape,
-                                                  batch_size, padded=static_caps is not None)
-        t = SparseConvTensor(torch.index_select(features, 0, order), sorted_idx, spatial_shape, batch_size)  # int32 index: one launch
-        t.indice_dict[("bitmap",) + t._level_key()] = lvl
-        if static_caps is not None:
-            # static-shape mode (whole-frame hipGraph): `indices` may carry padding rows (b < 0); every strided conv
-            # below produces static_caps[indice_key] rows, the surplus being padding, and appends its device-side
-            # output count to "counts" for the caller's overflow check
-            t.indice_dict["static"] = dict(caps={k: v for k, v in static_caps.items() if k != "__rows__"}, counts=[])
-            t.num_rows = static_caps.get("__rows__")
-        return t
-
-    def subm_rulebook(self, ksize):
-        key = ("subm", tuple(ksize)) + self._level_key()
-        if key not in self.indice_dict:
-            lvl = self.bitmap_level()
-            if lvl is not None:
-                self.indice_dict[key] = ops.rulebook_subm_bitmap(self.indices, lvl, ksize,
-                                                                 want_counts="static" not in self.indice_dict)
-            else:
-                self.indice_dict[key] = ops.rulebook_subm(self.indices, self.spatial_shape, ksize, self.coord_table())
-        return self.indice_dict[key]
+        level, order = Level.sorted(indices, spatial_shape, batch_size, static_caps)
+        return SparseConvTensor(torch.index_select(features, 0, order), level=level)  # int32 index: one launch
 
     def dense(self, channels_first=True):
         out = ops.densify(self.features, self.indices, self.batch_size, self.spatial_shape)
@@ -91,8 +133,7 @@ class SparseConvTensor:
     def dense_bev(self):
         """dense() viewed as (N, C * D, H, W) (sparse_encoder_custom.py:144-147).  GPU inference on a bitmap-ranked level: one pass that
         writes the map channels-last for the dense backbone (ops.densify_bev); same values, other strides."""
-        lvl = self.bitmap_level()
-        C = self.features.shape[1]
+        lvl, C = self.level.bitmap, self.features.shape[1]
         if (lvl is not None and self.features.is_cuda and not (torch.is_grad_enabled() and self.features.requires_grad)
                 and (C * self.spatial_shape[0]) % 4 == 0 and self.features.dtype == torch.float32):
             return ops.densify_bev(self.features, lvl, self.batch_size, self.spatial_shape)
@@ -123,8 +164,7 @@ class _SparseConv(SparseModule):
         assert groups == 1 and _triple(dilation) == [1, 1, 1], "only what the reference encoders use"
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding = _triple(kernel_size), _triple(stride), _triple(padding)
-        self.subm = subm
-        self.indice_key = indice_key
+        self.subm, self.indice_key = subm, indice_key
         self.weight = nn.Parameter(torch.empty(*self.kernel_size, in_channels, out_channels))
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
         self.reset_parameters()
@@ -132,7 +172,7 @@ class _SparseConv(SparseModule):
     def reset_parameters(self):
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
         if self.bias is not None:
-            fan_in = self.in_channels * self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
+            fan_in = self.in_channels * math.prod(self.kernel_size)
             bound = 1 / math.sqrt(fan_in)
             nn.init.uniform_(self.bias, -bound, bound)
 
@@ -143,63 +183,21 @@ class _SparseConv(SparseModule):
             state_dict[prefix + "weight"] = w.permute(1, 2, 3, 4, 0).contiguous()  # spconv 2.x -> 1.x layout
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    def _rulebook(self, x):
-        if self.subm:
-            nbr, counts = x.subm_rulebook(self.kernel_size)
-            return nbr, counts, x.indices, x.spatial_shape, x.num_rows
-        key = ("strided", self.indice_key, tuple(self.kernel_size), tuple(self.stride), tuple(self.padding)) + \
-            x._level_key()
-        if key not in x.indice_dict:
-            lvl = x.bitmap_level()
-            static = x.indice_dict.get("static")
-            if lvl is not None and static is not None:
-                cap = static["caps"][self.indice_key]
-                out_idx, nbr, counts, out_lvl, oshape, num_out = ops.rulebook_strided_bitmap(
-                    x.indices, lvl, self.kernel_size, self.stride, self.padding, out_capacity=cap)
-                static["counts"].append((self.indice_key, num_out, cap))
-                x.indice_dict[("rows", out_idx.data_ptr())] = num_out
-                x.indice_dict[("bitmap", out_idx.data_ptr(), out_idx.shape[0], tuple(oshape))] = out_lvl
-            elif lvl is not None:
-                out_idx, nbr, counts, out_lvl, oshape = ops.rulebook_strided_bitmap(x.indices, lvl, self.kernel_size, self.stride,
-                                                                                   self.padding)
-                x.indice_dict[("bitmap", out_idx.data_ptr(), out_idx.shape[0], tuple(oshape))] = out_lvl
-            else:
-                out_idx, nbr, counts, table, oshape = ops.rulebook_strided(x.indices, x.spatial_shape, x.batch_size,
-                                                                           self.kernel_size, self.stride, self.padding)
-                x.indice_dict[("table", out_idx.data_ptr(), out_idx.shape[0], tuple(oshape))] = table
-            x.indice_dict[key] = (out_idx, nbr, counts, oshape)
-        out_idx, nbr, counts, oshape = x.indice_dict[key]
-        return nbr, counts, out_idx, oshape, x.indice_dict.get(("rows", out_idx.data_ptr()))
+    @functools.cached_property
+    def _packable(self):   # (a shape rule of the library: asked once per layer, not twice per call)
+        return ops.spconv_packed_supported(math.prod(self.kernel_size), self.in_channels, self.out_channels)
+
+    def index(self, level):
+        """-> (Rulebook, row plan or None, output Level): what this layer needs of the coordinates alone, built on first use, kept on `level`."""
+        rb, out = (level.subm(self.kernel_size), level) if self.subm else level.strided(self.indice_key, self.kernel_size, self.stride, self.padding)
+        plan = None if self.training or not self._packable else \
+            rb.plan(self.in_channels, self.out_channels, rb.nbr.shape[0], self.subm, out.rows_dev)
+        return rb, plan, out
 
     def forward(self, x, bn=None, relu=False, residual=None):
-        """conv, optionally with an eval-mode BatchNorm1d, residual rows and ReLU fused into the same kernel.
-        An index-only tensor (`x.features is None`) gets the layer's rulebook (and row ranges) built and cached and comes back
-        index-only: the encoder runs that dry pass on a second stream, ahead of the convolutions (middle_encoders.py)."""
-        nbr, counts, out_idx, oshape, rows_dev = self._rulebook(x)
-        K = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
-        use_packed = not self.training and ops.spconv_packed_supported(K, self.in_channels, self.out_channels)
-        tiles = None
-        if (use_packed and ops.spconv_tiles_wanted(self.in_channels, self.out_channels) and nbr.shape[1] > 0
-                and (self.subm or K == 27)):
-            # balanced row ranges, one set per rulebook: shared by the SubM layers of a level; a 27-offset strided conv gains more
-            # from them than they cost (64 -> 128 on the nuScenes encoder: 92 -> 76 us, its steps 36 +- 37 -> 35 +- 19 per workgroup;
-            # the three small launches of the cut run on the index stream of the graph, ahead of the convolutions); conv_out (3
-            # offsets) runs on equal-height tiles
-            if self.out_channels == 32:
-                # 32-channel layers: a mask-sorted row order instead of ranges, from ~100k rows up (Waymo's levels)
-                if ops.spconv_order_wanted(self.in_channels, self.out_channels, rows=nbr.shape[1]):
-                    tkey = ("order", nbr.data_ptr(), nbr.shape[1])
-                    tiles = x.indice_dict.get(tkey)
-                    if tiles is None:
-                        tiles = x.indice_dict[tkey] = ops.spconv_order(nbr, rows_dev)
-            else:
-                tkey = ("tiles", nbr.data_ptr(), nbr.shape[1])
-                tiles = x.indice_dict.get(tkey)
-                if tiles is None:
-                    tiles = x.indice_dict[tkey] = ops.spconv_tiles(nbr, rows_dev)
-        if x.features is None:
-            return SparseConvTensor(None, out_idx, oshape, x.batch_size, x.indice_dict, rows_dev)
-        w = self.weight.view(K, self.in_channels, self.out_channels)
+        """conv, optionally with an eval-mode BatchNorm1d, residual rows and ReLU fused into the same kernel."""
+        rb, plan, out = self.index(x.level)
+        w = self.weight.view(-1, self.in_channels, self.out_channels)
         alpha = beta = None
         if bn is not None:
             alpha, beta = derived.fold_bn(bn)
@@ -207,10 +205,11 @@ class _SparseConv(SparseModule):
                 beta = beta + self.bias * alpha
         elif self.bias is not None:
             alpha, beta = torch.ones_like(self.bias), self.bias
-        packed = derived.get(self, "spconv", (self.weight,), lambda: ops.pack_spconv_weights(w.detach())) if use_packed else None
-        feats = ops.spconv_fwd(x.features, w, nbr, alpha, beta, residual, relu, pair_counts=counts, packed=packed,
-                               rows_dev=rows_dev, tiles=tiles, subm=self.subm)
-        return SparseConvTensor(feats, out_idx, oshape, x.batch_size, x.indice_dict, rows_dev)
+        packed = None if self.training or not self._packable else \
+            derived.get(self, "spconv", (self.weight,), lambda: ops.pack_spconv_weights(w.detach()))
+        feats = ops.spconv_fwd(x.features, w, rb.nbr, alpha, beta, residual, relu, pair_counts=rb.counts, packed=packed,
+                               rows_dev=out.rows_dev, tiles=plan, subm=self.subm)
+        return SparseConvTensor(feats, level=out)
 
 
 @CONV_LAYERS.register_module("SubMConv3d")
@@ -263,8 +262,7 @@ class SparseSequential(SparseModule):
                 x = m(x)
                 i += 1
             else:
-                if not (isinstance(x, SparseConvTensor) and x.features is None):   # (an index-only dry pass has nothing for it)
-                    x = x.replace_feature(m(x.features)) if isinstance(x, SparseConvTensor) else m(x)
+                x = x.replace_feature(m(x.features)) if isinstance(x, SparseConvTensor) else m(x)
                 i += 1
         return x
 
@@ -286,8 +284,6 @@ class SparseBasicBlock(SparseModule):
 
     def forward(self, x):
         identity = x.features
-        if identity is None:   # index-only dry pass: both layers share the level's rulebook
-            return self.conv2(self.conv1(x))
         if _bn_foldable(self.bn1) and _bn_foldable(self.bn2):
             out = self.conv1(x, bn=self.bn1, relu=True)
             return self.conv2(out, bn=self.bn2, relu=True, residual=identity)

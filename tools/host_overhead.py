@@ -1,5 +1,5 @@
-import sys, time, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from srfdet3d_amd import ops, synthetic, workloads
 from srfdet3d_amd.sparse import SparseConvTensor
 torch.manual_seed(0)
