@@ -88,6 +88,26 @@ int srf_bitmap_strided_pairs(const int *out_indices, const int *num_out, int max
 int srf_densify_bev(const float *feats, int A, int C, const void *bitmap, const int *prefix, int B, int D, int H, int W, float *out,
                     srf_stream_t stream);
 
+/* The encoder of the pillar configs (csrc/pillar.hip, whose header holds the exact definition of both).
+ *
+ * srf_pillar_vfe: PillarFeatureNetCustom with one PFNLayer, mode="max", in eval mode (pillar_encoder_custom.py:108-161, utils.py:63-146)
+ * in one launch.  voxels (rows, P, nf) zero-padded, num (rows), coors4 (rows, 4) (b, z, y, x) as srf_hard_voxelize[_static] writes them;
+ * rows_dev: device count of live rows, or NULL (all rows); voxel_size / offset: host[3] (x, y, z), offset = v / 2 + range_lo rounded to
+ * f32; W (Cout, K) row-major, K = nf + 3 * cluster_center + 3 * voxel_center; scale / shift (Cout): the folded eval BatchNorm;
+ * out (rows, Cout).  Padding rows (r >= *rows_dev, b < 0 or num <= 0) are written as zeros.  Deterministic.
+ * Limits (SRF_EUNSUPPORTED): Cout % 64 == 0 and Cout <= 256, 3 <= nf <= 8, P <= 64, voxels and out below 2^31 bytes.  Null pointers and
+ * non-positive sizes: SRF_EINVAL.  Both are checked before any HIP call; rows == 0 is SRF_OK with no launch.
+ *
+ * srf_pillar_scatter_nhwc: PointPillarsScatter with the canvas channels-last: out (B, H, W, C) is zero-filled, then row r of feats
+ * (rows, C), C % 4 == 0, is copied to pixel (b, y, x) of coors4[r] (z is ignored) in 16-byte stores; feats and out 16-byte aligned.
+ * Rows with b < 0 or r >= *rows_dev (rows_dev may be NULL) are skipped, as srf_densify skips them.  The coordinates are distinct by
+ * construction (one pillar per occupied cell).  A bit copy.  Limits: feats and out below 2^31 bytes. */
+int srf_pillar_vfe(const float *voxels, const int *num, const int *coors4, const int *rows_dev, int rows, int P, int nf,
+                   const float *voxel_size /*host[3]*/, const float *offset /*host[3]*/, int cluster_center, int voxel_center, int legacy,
+                   const float *W, const float *scale, const float *shift, int Cout, float *out, srf_stream_t stream);
+int srf_pillar_scatter_nhwc(const float *feats, const int *coors4, const int *rows_dev, int rows, int C, int B, int H, int W, float *out,
+                            srf_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * f-4  the step before the path: the CPU transforms of the reference's test pipeline between the decoded
  * sensor data and SRFDet.forward (configs/nus/srfdet_voxel_nusc_LC.py:253-283), on the device.

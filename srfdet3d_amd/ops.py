@@ -659,6 +659,75 @@ def densify_bev(feats, level, batch, spatial_shape):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- pillar encoder
+def pillar_enabled():
+    """SRF_PILLAR=0 keeps `plugin.pillar.PillarFeatureNetCustom` and `PointPillarsScatter` on their torch / `densify` route on the GPU as
+    well: what the pillar configs ran before csrc/pillar.hip, the route the tests and tools/bench_pillar.py alternate against.  Read at
+    every call."""
+    return os.environ.get("SRF_PILLAR", "1") != "0"
+
+
+def pillar_vfe_ok(rows, P, nf, Cout):
+    """The shapes `srf_pillar_vfe` takes (csrc/pillar.hip, the SRF_EUNSUPPORTED line of the entry point): a lane per output channel in
+    waves of 64 and at most 4 channel groups, the point features in registers, a pillar's points in one LDS slab, `voxels` and `out`
+    inside 32-bit byte ranges."""
+    return Cout % 64 == 0 and 0 < Cout <= 256 and 3 <= nf <= 8 and 1 <= P <= 64 and below_2gb(rows, P * nf) and below_2gb(rows, Cout)
+
+
+def pillar_scatter_ok(rows, C, B, H, W):
+    """The shapes `srf_pillar_scatter_nhwc` takes: whole float4s per pillar, `feats` and the canvas inside 32-bit byte ranges."""
+    return quads_ok(C) and below_2gb(rows, C) and below_2gb(B * H * W, C)
+
+
+def pillar_vfe(voxels, num, coors4, weight, scale, shift, voxel_size, offset, cluster_center=True, voxel_center=True, legacy=True,
+               rows_dev=None):
+    """The single-layer, mode="max" pillar feature net in one launch (`srf_pillar_vfe`; definition in csrc/pillar.hip and, as numpy, in
+    tests/pillar_ref.py).  voxels (rows, P, nf) zero-padded, num (rows) int32, coors4 (rows, 4) int32 (b, z, y, x), weight (Cout, K) with
+    K = nf + 3 * cluster + 3 * centre, scale / shift (Cout) the folded eval BatchNorm, voxel_size / offset three host floats (x, y, z);
+    rows_dev: device count of live rows (None: all).  -> (rows, Cout); padding rows are zeros."""
+    voxels = _dev(voxels, "voxels", torch.float32)
+    num = _dev(num, "num", torch.int32)
+    coors4 = _dev(coors4, "coors4", torch.int32)
+    weight = _dev(weight, "weight", torch.float32)
+    scale = _dev(scale, "scale", torch.float32)
+    shift = _dev(shift, "shift", torch.float32)
+    rows, P, nf = voxels.shape
+    Cout, K = weight.shape
+    if K != nf + 3 * bool(cluster_center) + 3 * bool(voxel_center) or scale.numel() != Cout or shift.numel() != Cout:
+        raise ValueError("pillar_vfe: weight must be (Cout, nf + 3 * cluster + 3 * centre), scale and shift (Cout)")
+    if num.numel() != rows or tuple(coors4.shape) != (rows, 4):
+        raise ValueError("pillar_vfe: num must be (rows,), coors4 (rows, 4)")
+    if rows_dev is not None:
+        rows_dev = _dev(rows_dev, "rows_dev", torch.int32)
+    out = _empty((rows, Cout), torch.float32, voxels.device)
+    check(_lib.lib().srf_pillar_vfe(_ptr(voxels), _ptr(num), _ptr(coors4), _ptr(rows_dev), rows, P, nf, hf(voxel_size), hf(offset),
+                                    int(bool(cluster_center)), int(bool(voxel_center)), int(bool(legacy)), _ptr(weight), _ptr(scale),
+                                    _ptr(shift), Cout, _ptr(out), _stream()), "pillar_vfe")
+    return out
+
+
+def pillar_scatter_nhwc(feats, coors4, batch, ny, nx, rows_dev=None, out=None):
+    """PointPillarsScatter: pillar features (rows, C) + coors4 (rows, 4) int32 (b, z, y, x) -> the canvas (batch, C, ny, nx) with
+    CHANNELS-LAST strides (`srf_pillar_scatter_nhwc`: zero fill and a 16-byte copy per quad, no transpose).  Rows with b < 0 or past
+    `rows_dev` (a device count, None: all rows) are skipped.  `out`: a canvas of that shape and layout to write into.  Inference only."""
+    feats = _dev(feats, "feats", torch.float32)
+    coors4 = _dev(coors4, "coors4", torch.int32)
+    rows, C = feats.shape
+    if tuple(coors4.shape) != (rows, 4):
+        raise ValueError("pillar_scatter_nhwc: coors4 must be (rows, 4)")
+    if rows_dev is not None:
+        rows_dev = _dev(rows_dev, "rows_dev", torch.int32)
+    batch, ny, nx = int(batch), int(ny), int(nx)
+    if out is None:
+        out = torch.empty((batch, C, ny, nx), dtype=torch.float32, device=feats.device, memory_format=torch.channels_last)
+    elif (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (batch, C, ny, nx)
+          or not out.permute(0, 2, 3, 1).is_contiguous()):
+        raise ValueError("pillar_scatter_nhwc: `out` must be an f32 GPU tensor (batch, C, ny, nx) with channels-last strides")
+    check(_lib.lib().srf_pillar_scatter_nhwc(_ptr(feats), _ptr(coors4), _ptr(rows_dev), rows, C, batch, ny, nx, _ptr(out), _stream()),
+          "pillar_scatter_nhwc")
+    return out
+
+
 def _densify(feats, indices, batch, spatial_shape):
     feats = _dev(feats, "feats", torch.float32)
     indices = _dev(indices, "indices", torch.int32)

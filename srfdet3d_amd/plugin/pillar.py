@@ -1,14 +1,20 @@
 """Pillar-config encoder: `PillarFeatureNetCustom` / `PFNLayer`
 (mmdet3d_plugin/models/voxel_encoders/pillar_encoder_custom.py:13-160, utils.py:63-146) and mmdet3d's
 `PointPillarsScatter` (configs/nus/srfdet_pillar_nusc_L.py:53-54).  Pillars come from the hard-voxelization kernel with
-20 points per pillar on a 512 x 512 grid; the scatter to the BEV canvas is the densify kernel with D = 1."""
+20 points per pillar on a 512 x 512 grid.
+
+In inference on f32 GPU tensors the single-layer, mode="max" net is ONE kernel (`ops.pillar_vfe`, csrc/pillar.hip) and the scatter writes
+the canvas channels-last (`ops.pillar_scatter_nhwc`), the layout `nhwc.second_forward` takes without a copy.  Everything else -- training,
+CPU tensors, several PFN layers, mode="avg", with_distance, SRF_PILLAR=0 -- runs the torch code below as written, with the densify kernel
+(D = 1) as the scatter."""
 import torch
 from torch import nn
 from torch.nn import functional as F
 
-from .. import ops
+from .. import derived, ops
 from ..compat.cnn import BaseModule, build_norm_layer
 from ..compat.registry import MIDDLE_ENCODERS, VOXEL_ENCODERS
+from ..dense import fusable
 
 
 class PFNLayer(nn.Module):
@@ -61,8 +67,25 @@ class PillarFeatureNetCustom(BaseModule):
         self.z_offset = self.vz / 2 + point_cloud_range[2]
         self.point_cloud_range = point_cloud_range
 
+    def hip_route(self, features):
+        """`ops.pillar_vfe` computes this net: SRF_PILLAR is on, the input is an f32 GPU tensor outside autograd and autocast, and the net is
+        one bias-free linear layer, an eval BatchNorm1d, ReLU and a max over the pillar (no distance feature), in a shape the kernel takes."""
+        if not (ops.pillar_enabled() and features.dim() == 3 and fusable(features)) or self._with_distance or len(self.pfn_layers) != 1:
+            return False
+        pfn = self.pfn_layers[0]
+        rows, P, nf = features.shape
+        return (pfn.mode == "max" and pfn.last_vfe and derived.foldable_bn(pfn.norm, nn.BatchNorm1d) and pfn.linear.bias is None
+                and pfn.linear.in_features == nf + 3 * bool(self._with_cluster_center) + 3 * bool(self._with_voxel_center)
+                and ops.pillar_vfe_ok(rows, P, nf, pfn.units))
+
     def forward(self, features, num_points, coors):
         """(N, M, C) zero-padded pillar points, (N,) counts, (N, 4) (b,z,y,x) -> (N, C_out) pillar features."""
+        if self.hip_route(features):
+            pfn = self.pfn_layers[0]
+            scale, shift = derived.fold_bn(pfn.norm)
+            return ops.pillar_vfe(features, num_points.int(), coors.int(), pfn.linear.weight, scale, shift, (self.vx, self.vy, self.vz),
+                                  (self.x_offset, self.y_offset, self.z_offset), self._with_cluster_center, self._with_voxel_center,
+                                  self.legacy)
         parts = [features]
         if self._with_cluster_center:
             mean = features[:, :, :3].sum(dim=1, keepdim=True) / num_points.type_as(features).view(-1, 1, 1)
@@ -99,6 +122,9 @@ class PointPillarsScatter(nn.Module):
     def forward(self, voxel_features, coors, batch_size=None):
         if batch_size is None:
             batch_size = int(coors[:, 0].max().item()) + 1
+        if (ops.pillar_enabled() and fusable(voxel_features) and coors.is_cuda
+                and ops.pillar_scatter_ok(voxel_features.shape[0], self.in_channels, int(batch_size), self.ny, self.nx)):
+            return ops.pillar_scatter_nhwc(voxel_features, coors.int(), batch_size, self.ny, self.nx)
         c = coors.int().clone()
         c[:, 1] = 0  # pillars: a single z slab
         return ops.densify(voxel_features, c.contiguous(), int(batch_size), [1, self.ny, self.nx]).view(
