@@ -711,6 +711,31 @@ int srf_dcnv2_nhwc(const float *x, int N, int H, int W, int Cin, long long x_ld,
                    int stride, int pad, int dilation, int groups, int deform_groups, const float *scale, const float *shift,
                    int relu, float *y, long long y_ld, srf_stream_t stream);
 
+/* srf_msda_fwd (csrc/msda.hip): multi-scale deformable attention, forward -- the sampling core of mmcv's
+ * `MultiScaleDeformableAttention` (Zhu et al., "Deformable DETR", eq. 3) under the two layers of `encoder_lidar`
+ * (srfdet_head.py:241-263, :657-758, `with_lidar_encoder=True`).  mmcv is not part of the reference tree: this text is the definition.
+ *   value:  (B S, value_ld) rows of heads * head_dim channels [head][d], S = sum_l H_l W_l, the L levels of a batch element one after
+ *           the other in the order of `shapes`, row h W_l + w inside a level: a flattened channels-last pyramid.
+ *   shapes: host[L][2] = (H_l, W_l); a level starts at the prefix sum of the products.
+ *   ref:    (B Q, L, 2) contiguous, normalised (x, y) per query and level.
+ *   offs:   (B Q, offs_ld) rows of (heads, L, P, 2) = (dx, dy) in pixels of level l;  logits: (B Q, logits_ld) rows of (heads, L, P), raw.
+ *           Both may point into one row buffer of width 3 heads L P (offsets first, the same pitch): the output of ONE GEMM.
+ *   out:    (B Q, out_ld) rows of heads * head_dim channels.
+ *   a[q,h,:,:]  = softmax over the L P logits of (q, h)   (float32, max-subtracted)
+ *   px = ref_x W_l + dx - 0.5,  py = ref_y H_l + dy - 0.5  (grid_sample's align_corners=False)
+ *   out[q,h,:]  = sum_{l,p} a[q,h,l,p] * bilinear(value_l[b, ., ., h, :], py, px)
+ * A corner outside the map contributes 0.  A sample whose position is not inside (-1, H_l) x (-1, W_l) contributes 0 as a whole; the
+ * comparisons are false for NaN and +-inf, so such offsets contribute 0 too.  This is the rule of mmcv's CUDA operator and NOT
+ * grid_sample's, which lets a NaN position through; on finite positions the two agree.  Non-finite logits propagate as a float32
+ * softmax propagates them.  Deterministic: the sum runs over l, then p, then the corners (y0 x0), (y0 x1), (y1 x0), (y1 x1) as one
+ * fma chain; no atomics.  Forward only.
+ * SRF_EINVAL: a negative B or Q, L, P, heads or head_dim <= 0, no shapes, a level with H or W <= 0, a pitch below its row's width, a null
+ * tensor with B Q > 0.  SRF_EUNSUPPORTED (before any launch): head_dim not 16 or 32, L > 4, P > 4, a tensor of 2 GiB or more, a pitch
+ * that is no multiple of 4 floats, a base that is not 16-byte aligned.  B Q == 0 is nothing to do (SRF_OK). */
+int srf_msda_fwd(const float *value, long long value_ld, int B, const int *shapes /*host[L][2]*/, int L, const float *ref,
+                 const float *offs, long long offs_ld, const float *logits, long long logits_ld, int Q, int heads, int head_dim, int P,
+                 float *out, long long out_ld, srf_stream_t stream);
+
 /* ---- streaming layers of the channels-last camera branch (csrc/nhwc.hip); all take (N, H, W, ld) channel slices, C % 4 == 0,
  * 16-byte aligned pointers, ld % 4 == 0 ---------------------------------------------------------------------------------
  * Defined exactly by tests/nhwc_ref.py.  Checks, in this order: sizes (negative count, C <= 0, map extent < 1, ld < C: SRF_EINVAL);

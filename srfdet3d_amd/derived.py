@@ -13,6 +13,10 @@ Everything held for a module lives in `mod.__dict__["_srf_derived"]`, a plain di
   dcn, dcn_offset                       the two GEMM operands of a DCNv2 pack                     (compat/dcn.py)
   bn_fold                               (scale, shift) of an eval BatchNorm                       (fold_bn)
   linear_padded                         an nn.Linear weight zero-padded to K % 4 == 0             (dense.linear_graph_safe)
+  msda_qproj                            `sampling_offsets` and `attention_weights` as one GEMM operand and its bias
+                                                                                                  (compat/transformer.py)
+  lidar_pos                             position + level embedding of every pixel of the BEV pyramid, an eval-mode function of the
+                                        weights alone                                             (plugin/heads.py `_lidar_pos`)
 """
 import torch
 

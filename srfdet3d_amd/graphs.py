@@ -327,13 +327,24 @@ class GraphedFrame:
         x = m.pts_backbone(bev)
         if m.pts_neck is not None:
             x = m.pts_neck(x)
+        if self._encodes():
+            # the head's LiDAR encoder belongs to the BEV half: `dpg_lidar_logits` must read encoded maps (srfdet_head.py:399-420), and
+            # beside the camera graph the encoder is hidden; `_run_head` tells the head the pyramid is encoded already
+            x = m.bbox_head.encode_lidar(x)
         dev_counts = torch.cat([c[1].view(1) for c in counts])
         limits = [c[2] for c in counts]
         return tuple(x), (dev_counts, limits)
 
+    def _encodes(self):
+        return bool(getattr(self.model.bbox_head, "with_lidar_encoder", False))
+
     def _run_head(self, x, img_metas, img_feats=None, dpg_lidar=None):
+        """x: the pyramid `_run_bev` returned (encoded there when the head has a LiDAR encoder)."""
         m = self.model
-        scores, dec = m.bbox_head.forward_decode(img_feats, x, img_metas, dpg_lidar)
+        if self._encodes():
+            scores, dec = m.bbox_head.forward_decode(img_feats, x, img_metas, dpg_lidar, lidar_encoded=True)
+        else:
+            scores, dec = m.bbox_head.forward_decode(img_feats, x, img_metas, dpg_lidar)
         sel = m.bbox_head.select_static(scores, dec) if getattr(m.bbox_head, "use_nms", False) else None
         return scores, dec, sel
 

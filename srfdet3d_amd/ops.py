@@ -2034,6 +2034,75 @@ def modulated_deform_conv2d(x, offset, mask, weight, bias=None, stride=1, paddin
     return y.permute(0, 3, 1, 2).contiguous()
 
 
+# ---- multi-scale deformable attention (csrc/msda.hip) ------------------------------------------------------------------
+def msda_enabled():
+    """SRF_MSDA=0 keeps `compat.transformer.MultiScaleDeformableAttention` (and the encoder around it) on its torch route (one
+    grid_sample per level) on the GPU as well: the parity reference the tests and tools/bench_msda.py alternate against, as SRF_DCN=0 is
+    for the DCNv2 kernel.  Read at every call."""
+    return os.environ.get("SRF_MSDA", "1") != "0"
+
+
+def msda_supported(B, S, Q, heads, head_dim, levels, points, value_ld=None, offs_ld=None, logits_ld=None, out_ld=None):
+    """Shapes `srf_msda_fwd` takes, from the shapes alone: head_dim 16 or 32, 1 <= levels <= 4, 1 <= points <= 4, every pitch (floats per
+    row; the row's width when None) at least the row's width and a multiple of 4, and each of value (B S rows), offs, logits, out and
+    ref (B Q rows) below 2 GiB.  The 16-byte alignment of the bases is checked at the call."""
+    if not (B >= 0 and S > 0 and Q >= 0 and heads > 0 and head_dim in (16, 32) and 1 <= levels <= 4 and 1 <= points <= 4):
+        return False
+    C, ns = heads * head_dim, heads * levels * points
+    lds = ((C if value_ld is None else value_ld, C, B * S), (2 * ns if offs_ld is None else offs_ld, 2 * ns, B * Q),
+           (ns if logits_ld is None else logits_ld, ns, B * Q), (C if out_ld is None else out_ld, C, B * Q))
+    if any(ld < width or ld % 4 for ld, width, _ in lds):
+        return False
+    lim = (1 << 31) // 4 - 1
+    return S < (1 << 31) and all(rows <= lim // ld for ld, _, rows in lds) and B * Q <= lim // (2 * levels)
+
+
+def _rows(t, name, width):
+    """A 2-d float32 GPU tensor (or view) with unit inner stride and `width` columns -> its row pitch."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"srfdet3d_amd: `{name}` must be a GPU tensor (no CPU fallback exists)")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"msda: `{name}` must be float32 rows of {width} columns with unit inner stride, got {tuple(t.shape)} "
+                         f"strides {tuple(t.stride())} {t.dtype}")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), width)
+
+
+def msda(value, shapes, ref, offs, logits, heads, points, out=None):
+    """Multi-scale deformable attention forward (`srf_msda_fwd`, definition in include/srfdet3d.h).  value (B S, heads d) rows of the
+    flattened channels-last pyramid, shapes [(H_l, W_l)] host list, ref (B Q, L, 2) normalised (x, y), offs (B Q, heads L P 2) pixel
+    offsets, logits (B Q, heads L P) raw; value, offs, logits and out may be column slices of wider row buffers (offs and logits of one).
+    -> out (B Q, heads d).  B is B S / S.  No host synchronisation, no allocation outside torch's allocator: capturable."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    L, P, heads = len(shapes), int(points), int(heads)
+    S = sum(h * w for h, w in shapes)
+    for t, name in ((value, "value"), (ref, "ref"), (offs, "offs"), (logits, "logits")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"srfdet3d_amd: `{name}` must be a GPU tensor (no CPU fallback exists)")
+    if value.dim() != 2 or heads <= 0 or value.shape[1] % heads or S <= 0 or value.shape[0] % S:
+        raise ValueError(f"msda: value {tuple(value.shape)} is not (B S, heads d) rows for S = {S}, heads = {heads}")
+    C = value.shape[1]
+    d, B = C // heads, value.shape[0] // S
+    rows = offs.shape[0]
+    ns = heads * L * P
+    value_ld, offs_ld, logits_ld = _rows(value, "value", C), _rows(offs, "offs", 2 * ns), _rows(logits, "logits", ns)
+    ref = _dev(ref, "ref", torch.float32)
+    if tuple(ref.shape) != (rows, L, 2) or logits.shape[0] != rows or (B and rows % B) or (B == 0 and rows):
+        raise ValueError(f"msda: ref {tuple(ref.shape)} / logits {tuple(logits.shape)} do not match {rows} query rows, {L} levels, B = {B}")
+    Q = rows // B if B else 0
+    if out is None:
+        out = _empty((rows, C), torch.float32, value.device)
+    out_ld = _rows(out, "out", C)
+    if out.shape[0] != rows:
+        raise ValueError("msda: out has the wrong number of rows")
+    if not msda_supported(B, S, Q, heads, d, L, P, value_ld, offs_ld, logits_ld, out_ld):
+        raise RuntimeError(f"srfdet3d_amd: msda does not take B {B}, S {S}, Q {Q}, heads {heads}, head_dim {d}, levels {L}, points {P}, "
+                           f"pitches {(value_ld, offs_ld, logits_ld, out_ld)} (see ops.msda_supported)")
+    flat = [v for hw in shapes for v in hw]
+    check(_lib.lib().srf_msda_fwd(_ptr(value), value_ld, B, hi(flat), L, _ptr(ref), _ptr(offs), offs_ld, _ptr(logits), logits_ld, Q, heads, d,
+                                  P, _ptr(out), out_ld, _stream()), "msda_fwd")
+    return out
+
+
 def stem_conv_nchw(x, weight, scale=None, shift=None, relu=False, out=None):
     """Conv2d(Cin <= 4, 64, 3, stride 2, padding 1) + affine + ReLU from contiguous NCHW images to an NHWC tensor."""
     x = _dev(x, "x", torch.float32)

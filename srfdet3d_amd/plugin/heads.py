@@ -25,7 +25,9 @@ from torch import nn
 from .. import nhwc, ops, train_conv
 from ..compat.cnn import BaseModule, ConvModule, ModuleList, build_activation_layer, build_conv_layer
 from ..compat.registry import HEADS, LOSSES, BBOX_ASSIGNERS, build_head, build_roi_extractor
+from ..compat.transformer import MultiScaleDeformableAttention, PositionEmbeddingLearned, build_transformer_layer_sequence
 from ..dense import _foldable, fusable, linear_graph_safe
+from .. import derived
 from ..derived import fold_bn
 from ..roi import SingleRoIExtractor
 from .bbox_util import denormalize_bbox
@@ -437,7 +439,6 @@ class SRFDetHead(BaseModule):
                  single_head_img=None, roi_extractor_lidar=None, roi_extractor_img=None, sync_cls_avg_factor=True,
                  loss_cls=None, loss_bbox=None, train_cfg=None, test_cfg=None, init_cfg=None, pretrained=None):
         super().__init__(init_cfg)
-        assert not with_lidar_encoder, "with_lidar_encoder=False in every SRFDet3D config (SURVEY.md finding 8)"
         self.num_classes = num_classes
         self.use_img = use_img
         self.feat_channels_lidar = feat_channels_lidar
@@ -458,10 +459,13 @@ class SRFDetHead(BaseModule):
         self.grid_size = grid_size
         self.out_size_factor = out_size_factor
         self.sync_cls_avg_factor = sync_cls_avg_factor
-        self.with_lidar_encoder = False
+        self.with_lidar_encoder = bool(with_lidar_encoder)
+        self.lidar_encoder_cfg = lidar_encoder_cfg
         self.use_fed_loss, self.use_focal_loss = False, True
         self._code_size = len(code_weights)
 
+        if self.with_lidar_encoder:
+            self._build_lidar_encoder()
         if with_dpg:
             self._build_dynamic_prop_gen()
         else:
@@ -525,6 +529,137 @@ class SRFDetHead(BaseModule):
                 nn.init.xavier_uniform_(p)
             if p.shape[-1] in (self.num_classes, self.num_classes + 1):
                 nn.init.constant_(p, bias_value)
+        if self.with_lidar_encoder:   # after the xavier pass, so the attention's own initialisation wins (srfdet_head.py:225-229)
+            nn.init.normal_(self.bev_level_embeds)
+            for m in self.modules():
+                if isinstance(m, MultiScaleDeformableAttention):
+                    m.init_weights()
+
+    # ---- LiDAR BEV encoder (with_lidar_encoder=True) --------------------------------------------------------------
+    @staticmethod
+    def create_2D_grid(x_size, y_size):
+        """(1, x_size * y_size, 2) pixel centres, (x, y) with x fastest (srfdet_head.py:231-239)."""
+        batch_y, batch_x = torch.meshgrid(torch.linspace(0, x_size - 1, x_size), torch.linspace(0, y_size - 1, y_size), indexing="ij")
+        coord_base = torch.cat([batch_x[None] + 0.5, batch_y[None] + 0.5], dim=0)[None]
+        return coord_base.view(1, 2, -1).permute(0, 2, 1)
+
+    def _build_lidar_encoder(self):
+        """srfdet_head.py:241-263: the encoder, one learned position embedding per level, the level embeddings and the per-level position
+        grids.  The level sizes are int(x_size / 2**lvl), the reference's rule; `encode_lidar` checks the maps against them."""
+        self.encoder_lidar = build_transformer_layer_sequence(self.lidar_encoder_cfg)
+        self.bev_pos_encoder_mlvl_embed = ModuleList([PositionEmbeddingLearned(2, self.feat_channels_lidar)
+                                                      for _ in range(self.lidar_feat_lvls)])
+        self.bev_level_embeds = nn.Parameter(torch.empty(self.lidar_feat_lvls, self.feat_channels_lidar))
+        x_size, y_size = self.grid_size[0] // self.out_size_factor, self.grid_size[1] // self.out_size_factor
+        self.bev_level_sizes = [(int(x_size / (2 ** lvl)), int(y_size / (2 ** lvl))) for lvl in range(self.lidar_feat_lvls)]
+        self.bev_pos_mlvl = [self.create_2D_grid(xs, ys) for xs, ys in self.bev_level_sizes]
+        self._bev_consts = {}
+
+    def _bev_pos(self, idx, like):
+        """`bev_pos_mlvl[idx]` on `like`'s device, uploaded once (a host -> device copy per call is illegal inside a graph capture)."""
+        key = ("pos", idx, like.device)
+        t = self._bev_consts.get(key)
+        if t is None:
+            t = self._bev_consts[key] = self.bev_pos_mlvl[idx].to(like.device)
+        return t
+
+    def _bev_shapes(self, lidar_feats):
+        """[(H, W)] of the maps, checked against the level sizes the position grids were built for."""
+        if len(lidar_feats) != self.lidar_feat_lvls:
+            raise ValueError(f"encode_lidar: {len(lidar_feats)} BEV maps for lidar_feat_lvls = {self.lidar_feat_lvls}")
+        shapes = [(int(f.shape[2]), int(f.shape[3])) for f in lidar_feats]
+        for lvl, ((H, W), (xs, ys)) in enumerate(zip(shapes, self.bev_level_sizes)):
+            if H * W != xs * ys or sorted((H, W)) != sorted((xs, ys)):
+                raise ValueError(f"encode_lidar: BEV map {lvl} is {H} x {W}, but the position grid of level {lvl} was built for "
+                                 f"{xs} x {ys} = int(grid_size / out_size_factor / 2**{lvl})")
+        return shapes
+
+    def encode_lidar(self, point_feats):
+        """`_get_lidar_encoder_feats` (srfdet_head.py:657-758): the BEV pyramid [(bs, C, H, W)] through the two deformable-attention layers
+        of `encoder_lidar` -> the pyramid again.  Reproduced literally, with two quirks kept: the positions are normalised x / H and y / W
+        (:701-702; it matters on a non-square grid), always in float32 (`.float()`, :700), and the position grids come from
+        int(x_size / 2**lvl).  GPU inference in float32 runs on channels-last rows instead (`_encode_lidar_rows`), same arithmetic."""
+        lidar_feats = list(point_feats)[:self.lidar_feat_lvls]
+        rest = list(point_feats)[self.lidar_feat_lvls:]
+        shapes = self._bev_shapes(lidar_feats)
+        if self._encode_rows_ok(lidar_feats, shapes):
+            return self._encode_lidar_rows(lidar_feats, shapes) + rest
+        batch_size = lidar_feats[0].shape[0]
+        norm_mlvl, embed_mlvl, feat_mlvl = [], [], []
+        for idx, lidar_feat in enumerate(lidar_feats):
+            bev_pos_lvl = self._bev_pos(idx, lidar_feat).repeat(batch_size, 1, 1)                       # (bs, H*W, 2)
+            embed = self.bev_pos_encoder_mlvl_embed[idx](bev_pos_lvl).permute(0, 2, 1)
+            embed_mlvl.append(embed + self.bev_level_embeds[idx].view(1, 1, -1))                        # (bs, H*W, C)
+            H, W = shapes[idx]
+            feat_mlvl.append(lidar_feat.flatten(2).permute(0, 2, 1))
+            norm = bev_pos_lvl.float()
+            if norm is bev_pos_lvl:
+                norm = norm.clone()
+            norm[..., 0] /= H
+            norm[..., 1] /= W
+            norm_mlvl.append(norm)
+        feat = torch.cat(feat_mlvl, dim=1).permute(1, 0, 2)                                             # (sum H*W, bs, C)
+        ref = torch.cat(norm_mlvl, dim=1).unsqueeze(2).repeat(1, 1, len(lidar_feats), 1)                # (bs, sum H*W, lvls, 2)
+        embed = torch.cat(embed_mlvl, dim=1).permute(1, 0, 2)
+        starts = [0]
+        for H, W in shapes[:-1]:
+            starts.append(starts[-1] + H * W)
+        # spatial_shapes / level_start_index as host lists: the tensors the reference builds here would be read back by the attention
+        memory = self.encoder_lidar(query=feat, key=None, value=None, query_pos=embed, spatial_shapes=shapes, reference_points=ref,
+                                    level_start_index=starts)
+        bs, C = lidar_feats[0].shape[:2]
+        return [m.permute(1, 2, 0).reshape(bs, C, H, W) for m, (H, W) in zip(memory.split([H * W for H, W in shapes], dim=0), shapes)] + rest
+
+    def _encode_rows_ok(self, lidar_feats, shapes):
+        """GPU inference in float32 with SRF_MSDA on and shapes the kernel takes; everything else is the torch route."""
+        if self.training or torch.is_grad_enabled() or not ops.msda_enabled():
+            return False
+        if not all(fusable(f) for f in lidar_feats) or self.bev_level_embeds.dtype != torch.float32:
+            return False
+        if not all(derived.foldable_bn(e.position_embedding_head[1], nn.BatchNorm1d) for e in self.bev_pos_encoder_mlvl_embed):
+            return False
+        return self.encoder_lidar.rows_supported(lidar_feats[0].shape[0], shapes)
+
+    def _lidar_pos(self, like):
+        """(sum H*W, C): position embedding + level embedding of every pixel of the pyramid.  In eval it is a function of the weights
+        alone, so it is held in derived.py (`lidar_pos`): `weights_changed()` drops it."""
+        tensors = [self.bev_level_embeds]
+        for e in self.bev_pos_encoder_mlvl_embed:
+            tensors += list(e.parameters()) + list(e.buffers())
+
+        def make():
+            rows = [self.bev_pos_encoder_mlvl_embed[idx](self._bev_pos(idx, like)).permute(0, 2, 1)[0] + self.bev_level_embeds[idx].view(1, -1)
+                    for idx in range(self.lidar_feat_lvls)]
+            return torch.cat(rows).contiguous()
+        return derived.get(self, "lidar_pos", tensors, make)
+
+    def _lidar_ref(self, like, bs, shapes):
+        """(bs sum H*W, lvls, 2) float32 reference points, x / H and y / W as the reference normalises them; a constant per batch size."""
+        key = ("ref", like.device, bs, tuple(shapes))
+        t = self._bev_consts.get(key)
+        if t is None:
+            norm = []
+            for idx, (H, W) in enumerate(shapes):
+                n = self._bev_pos(idx, like).float().clone()
+                n[..., 0] /= H
+                n[..., 1] /= W
+                norm.append(n)
+            t = torch.cat(norm, dim=1).unsqueeze(2).repeat(bs, 1, len(shapes), 1)
+            t = self._bev_consts[key] = t.reshape(-1, len(shapes), 2).contiguous()
+        return t
+
+    def _encode_lidar_rows(self, lidar_feats, shapes):
+        """The encoder on channels-last rows: the pyramid flattened to (bs sum H*W, C), batch-major, levels one after the other -- the
+        `value` layout of `srf_msda_fwd` -- through `DetrTransformerEncoder.forward_rows`; no NCHW round trip between the layers."""
+        bs, C = lidar_feats[0].shape[:2]
+        x = torch.cat([f.permute(0, 2, 3, 1).reshape(bs, H * W, C) for f, (H, W) in zip(_channels_last(lidar_feats), shapes)], dim=1)
+        S = x.shape[1]
+        y = self.encoder_lidar.forward_rows(x.view(bs * S, C), self._lidar_pos(x), self._lidar_ref(x, bs, shapes), shapes).view(bs, S, C)
+        out, start = [], 0
+        for H, W in shapes:
+            out.append(y[:, start:start + H * W].reshape(bs, H, W, C).permute(0, 3, 1, 2))   # a view for bs == 1, channels-last
+            start += H * W
+        return out
 
     # ---- proposals ------------------------------------------------------------------------------------------
     @staticmethod
@@ -662,10 +797,12 @@ class SRFDetHead(BaseModule):
         return lambda i, x: nhwc.conv3x3(x, self.img_convs[i])
 
     # ---- forward --------------------------------------------------------------------------------------------
-    def forward(self, img_feats, point_feats, img_metas, precomputed_dpg_lidar=None):
+    def forward(self, img_feats, point_feats, img_metas, precomputed_dpg_lidar=None, lidar_encoded=False):
         """-> logits (#stage, bs, n_p, #cls), boxes (#stage, bs, n_p, D) with centres in metres, log sizes.
-        precomputed_dpg_lidar: `dpg_lidar_logits(point_feats)` computed earlier by the caller (graphs.GraphedFrame: in the BEV half)."""
-        logits_all, boxes_all = self._stages(img_feats, point_feats, img_metas, precomputed_dpg_lidar)
+        precomputed_dpg_lidar: `dpg_lidar_logits(point_feats)` computed earlier by the caller (graphs.GraphedFrame: in the BEV half).
+        lidar_encoded: with `with_lidar_encoder`, the caller has already run `encode_lidar` on point_feats (graphs.GraphedFrame: right
+        after the neck, so that the precomputed logits read encoded maps); otherwise `_stages` encodes on entry, exactly once."""
+        logits_all, boxes_all = self._stages(img_feats, point_feats, img_metas, precomputed_dpg_lidar, lidar_encoded=lidar_encoded)
         r = self.pc_range
         lo = _const(r[:3], point_feats[0])
         ext = _const([r[3] - r[0], r[4] - r[1], r[5] - r[2]], point_feats[0])
@@ -676,20 +813,25 @@ class SRFDetHead(BaseModule):
         boxes_all[..., :3] = boxes_all[..., :3] * ext + lo
         return logits_all, boxes_all
 
-    def forward_decode(self, img_feats, point_feats, img_metas, precomputed_dpg_lidar=None):
+    def forward_decode(self, img_feats, point_feats, img_metas, precomputed_dpg_lidar=None, lidar_encoded=False):
         """`decode(*forward(...))` for inference: (scores (bs, n_p, #cls), boxes (bs, n_p, 7|9)).  On the GPU without autograd only the
         last stage's outputs are kept -- each stage rewrites the centres of its input boxes in metres in place (srfdet_head.py:1646),
         so the per-stage copies `forward` makes for deep supervision are not needed -- and the end of `forward` + `decode` run as one
         launch (ops.decode_boxes) instead of 13."""
         if not (point_feats[0].is_cuda and not torch.is_grad_enabled()):
-            return self.decode(*self(img_feats, point_feats, img_metas, precomputed_dpg_lidar))
-        logits, pred = self._stages(img_feats, point_feats, img_metas, precomputed_dpg_lidar, last_only=True)
+            return self.decode(*self(img_feats, point_feats, img_metas, precomputed_dpg_lidar, lidar_encoded))
+        logits, pred = self._stages(img_feats, point_feats, img_metas, precomputed_dpg_lidar, last_only=True, lidar_encoded=lidar_encoded)
         return ops.decode_boxes(logits[-1], pred[-1], self.pc_range)
 
-    def _stages(self, img_feats, point_feats, img_metas, precomputed_dpg_lidar=None, last_only=False):
+    def _stages(self, img_feats, point_feats, img_metas, precomputed_dpg_lidar=None, last_only=False, lidar_encoded=False):
         """The decoder stages (srfdet_head.py:960-1000) -> per-stage lists of logits and boxes (centres normalised); with last_only
-        one entry each, and no copy of the boxes between stages."""
+        one entry each, and no copy of the boxes between stages.  With `with_lidar_encoder` the BEV pyramid goes through `encode_lidar`
+        first (srfdet_head.py:398-401), before the proposal generator, unless the caller says it has done so."""
         point_feats = list(point_feats)
+        if self.with_lidar_encoder and not lidar_encoded:
+            if precomputed_dpg_lidar is not None:
+                raise ValueError("precomputed_dpg_lidar must be computed from the encoded pyramid: pass lidar_encoded=True with it")
+            point_feats = self.encode_lidar(point_feats)
         if self.use_img and self.hidden_dim != self.feat_channels_img and not isinstance(img_feats, nhwc.ConsumedLevels):
             img_feats = self._img_convs_only(img_feats)
         boxes, prop_feats = self._stage_proposals(img_feats, point_feats, precomputed_dpg_lidar)

@@ -28,9 +28,11 @@ def model_cfg(name, **overrides):
     return wrapper.model
 
 
-def build(name, num_proposals=None, train=False):
+def build(name, num_proposals=None, train=False, **overrides):
+    """The model of reference config `name`; overrides: dotted keys as `model_cfg` takes them, e.g.
+    **{"bbox_head.with_lidar_encoder": True}."""
     from ..compat.registry import build_model
-    ov = {}
+    ov = dict(overrides)
     if num_proposals is not None:
         ov["bbox_head.num_proposals"] = num_proposals
     m = model_cfg(name, **ov)
