@@ -736,6 +736,35 @@ int srf_msda_fwd(const float *value, long long value_ld, int B, const int *shape
                  const float *offs, long long offs_ld, const float *logits, long long logits_ld, int Q, int heads, int head_dim, int P,
                  float *out, long long out_ld, srf_stream_t stream);
 
+/* srf_msda_bwd (csrc/msda_bwd.hip): the gradient of srf_msda_fwd, as that definition is written.  value, shapes, ref, offs, logits, Q,
+ * heads, head_dim, P: the forward's inputs, same layouts and pitches (offs and logits may share one row buffer).
+ *   grad_out:    (B Q, grad_out_ld) rows of heads * head_dim channels, the cotangent of `out`.
+ *   grad_value:  (B S, grad_value_ld), the layout of `value`.  The entry point ADDS into it: the caller zeroes it.
+ *   grad_offs:   (B Q, grad_offs_ld) rows of (heads, L, P, 2);  grad_logits: (B Q, grad_logits_ld) rows of (heads, L, P).  Both may point
+ *                into one row buffer, as the forward's inputs do.
+ * Each of the three outputs may be NULL: that gradient is skipped (its pitch is ignored) and the others do not change by a bit.
+ * With g = grad_out[q,h,:], a the softmax, px, py the forward's position, (x0, y0) = floor, lx = px - x0, ly = py - y0 and the
+ * corners v00 = value_l[y0][x0], v01 = [y0][x0+1], v10 = [y0+1][x0], v11 = [y0+1][x0+1] (0 outside the map):
+ *   t[l,p]              = <g, (1-ly)(1-lx) v00 + (1-ly) lx v01 + ly (1-lx) v10 + ly lx v11>
+ *   grad_logits[l,p]    = a[l,p] (t[l,p] - sum_j a[j] t[j])
+ *   grad_offs[l,p].x    = a[l,p] <g, (1-ly)(v01 - v00) + ly (v11 - v10)>
+ *   grad_offs[l,p].y    = a[l,p] <g, (1-lx)(v10 - v00) + lx (v11 - v01)>            (offsets are in pixels: no W or H factor)
+ *   grad_value[corner] += a[l,p] w_corner g                                         (corners inside the map only)
+ * A sample whose position is not inside (-1, H_l) x (-1, W_l) -- NaN and +-inf positions included -- has t = 0, a zero offset
+ * gradient and adds nothing.  A position on an integer takes its floor cell.  This is the rule of mmcv's CUDA operator and NOT the
+ * derivative grid_sample's backward takes at positions exactly on an integer or on the box edge; everywhere else the two agree.  There
+ * is no gradient for `ref`.  Non-finite logits propagate as float32 arithmetic propagates them (not pinned).
+ * Determinism: grad_offs and grad_logits are computed in a fixed order (the sum over a head's channels is a fixed cross-lane butterfly,
+ * the sum over j runs in sample order): two launches give the same bits.  grad_value is a data-dependent scatter of no-return float32
+ * atomic adds: its bits depend on the order in which the adds arrive, as for srf_roi_extract_bwd.
+ * Return codes and their order are srf_msda_fwd's, with grad_out and every non-NULL output held to the same rules (a pitch below the
+ * row's width: SRF_EINVAL; 2 GiB or more, a pitch % 4, a base that is not 16-byte aligned: SRF_EUNSUPPORTED); a NULL input with work to
+ * do: SRF_EINVAL.  B Q == 0, or all three outputs NULL, is nothing to do (SRF_OK, no launch).  All checks run before any HIP call. */
+int srf_msda_bwd(const float *value, long long value_ld, int B, const int *shapes /*host[L][2]*/, int L, const float *ref,
+                 const float *offs, long long offs_ld, const float *logits, long long logits_ld, int Q, int heads, int head_dim, int P,
+                 const float *grad_out, long long grad_out_ld, float *grad_value, long long grad_value_ld, float *grad_offs,
+                 long long grad_offs_ld, float *grad_logits, long long grad_logits_ld, srf_stream_t stream);
+
 /* ---- streaming layers of the channels-last camera branch (csrc/nhwc.hip); all take (N, H, W, ld) channel slices, C % 4 == 0,
  * 16-byte aligned pointers, ld % 4 == 0 ---------------------------------------------------------------------------------
  * Defined exactly by tests/nhwc_ref.py.  Checks, in this order: sizes (negative count, C <= 0, map extent < 1, ld < C: SRF_EINVAL);

@@ -161,6 +161,8 @@ SIGNATURES = {
                                c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_longlong, _P]),
     "srf_msda_fwd": (c_int, [_P, c_longlong, c_int, _HI, c_int, _P, _P, c_longlong, _P, c_longlong, c_int, c_int, c_int, c_int, _P, c_longlong,
                              _P]),
+    "srf_msda_bwd": (c_int, [_P, c_longlong, c_int, _HI, c_int, _P, _P, c_longlong, _P, c_longlong, c_int, c_int, c_int, c_int, _P, c_longlong,
+                             _P, c_longlong, _P, c_longlong, _P, c_longlong, _P]),
     "srf_nhwc_affine": (c_int, [_P, c_longlong, c_int, c_longlong, c_int, _P, c_int, _P, _P, c_longlong, c_int, _P, c_longlong, _P]),
     "srf_nhwc_colmean_workspace_bytes": (c_size_t, [c_int, c_int]),
     "srf_nhwc_colmean": (c_int, [_P, c_longlong, c_int, c_longlong, c_int, _P, _P, c_size_t, _P]),

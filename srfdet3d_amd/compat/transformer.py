@@ -5,10 +5,12 @@ mmcv's state_dict names (mmcv 1.7 semantics, from memory as everywhere in SURVEY
 configs use is built; anything else raises NotImplementedError naming it: pre-norm order, cross-attention, other attention types,
 `key_padding_mask`, 4-component reference points.
 
-The sampling core has two routes.  `multi_scale_deformable_attn_pytorch` is mmcv's pure-torch form (one grid_sample per level), in the
-tensors' own dtype, with autograd, no host synchronisation: training, CPU tensors, SRF_MSDA=0, unsupported shapes.  On the GPU in
+The sampling core has three routes.  `multi_scale_deformable_attn_pytorch` is mmcv's pure-torch form (one grid_sample per level), in the
+tensors' own dtype, with autograd, no host synchronisation: CPU tensors, SRF_MSDA=0, unsupported shapes, other dtypes.  On the GPU in
 inference `BaseTransformerLayer.forward_rows` runs a whole layer on channels-last rows: srf_linear GEMMs around `ops.msda`
-(csrc/msda.hip), six launches and one add per layer."""
+(csrc/msda.hip), six launches and one add per layer.  With gradients enabled on float32 GPU tensors the module's forward hands the
+core to `ops.msda_autograd` (forward csrc/msda.hip, backward csrc/msda_bwd.hip; SRF_MSDA_TRAIN=0 keeps the torch core); the Linears,
+the dropout and the LayerNorms around it stay torch modules under autograd."""
 import copy
 import math
 
@@ -137,6 +139,15 @@ class MultiScaleDeformableAttention(BaseModule):
         return derived.get(self, "msda_qproj", (so.weight, so.bias, aw.weight, aw.bias),
                            lambda: (torch.cat((so.weight, aw.weight)).contiguous(), torch.cat((so.bias, aw.bias)).contiguous()))
 
+    def _train_node_ok(self, value, query, reference_points, bs, S, Q):
+        """Gradients enabled, float32 GPU tensors, SRF_MSDA / SRF_MSDA_TRAIN on, no gradient wanted for the reference points (the node
+        has none), a shape `srf_msda_fwd` / `srf_msda_bwd` take: the sampling core runs as `ops._MsdaFn`."""
+        if not torch.is_grad_enabled() or not ops.msda_train_enabled() or reference_points.requires_grad:
+            return False
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in (value, query, reference_points)):
+            return False
+        return ops.msda_supported(bs, S, Q, self.num_heads, self.embed_dims // self.num_heads, self.num_levels, self.num_points)
+
     def forward(self, query, key=None, value=None, identity=None, query_pos=None, key_padding_mask=None, reference_points=None,
                 spatial_shapes=None, level_start_index=None, **kwargs):
         if key_padding_mask is not None:
@@ -158,12 +169,19 @@ class MultiScaleDeformableAttention(BaseModule):
             raise NotImplementedError(f"MultiScaleDeformableAttention: reference points with {reference_points.shape[-1]} components are "
                                       "not built, only (x, y) (DESIGN.md section 7)")
         heads, L, P = self.num_heads, self.num_levels, self.num_points
-        value = _lin(self.value_proj, value).view(bs, S, heads, -1)
-        offsets = _lin(self.sampling_offsets, query).view(bs, Q, heads, L, P, 2)
-        weights = _lin(self.attention_weights, query).view(bs, Q, heads, L * P).softmax(-1).view(bs, Q, heads, L, P)
-        normalizer = _shape_const(shapes, query)
-        locations = reference_points[:, :, None, :, None, :] + offsets / normalizer[None, None, None, :, None, :]
-        output = _lin(self.output_proj, multi_scale_deformable_attn_pytorch(value, shapes, locations, weights))
+        value = _lin(self.value_proj, value)
+        offsets = _lin(self.sampling_offsets, query)
+        logits = _lin(self.attention_weights, query)
+        if self._train_node_ok(value, query, reference_points, bs, S, Q):
+            # training on the GPU: the raw offsets (pixels) and raw logits go to the node, which does the softmax and the positions
+            core = ops.msda_autograd(value.reshape(bs * S, -1), shapes, reference_points.reshape(bs * Q, L, 2), offsets.reshape(bs * Q, -1),
+                                     logits.reshape(bs * Q, -1), heads, P).view(bs, Q, -1)
+        else:
+            weights = logits.view(bs, Q, heads, L * P).softmax(-1).view(bs, Q, heads, L, P)
+            normalizer = _shape_const(shapes, query)
+            locations = reference_points[:, :, None, :, None, :] + offsets.view(bs, Q, heads, L, P, 2) / normalizer[None, None, None, :, None, :]
+            core = multi_scale_deformable_attn_pytorch(value.view(bs, S, heads, -1), shapes, locations, weights)
+        output = _lin(self.output_proj, core)
         if not self.batch_first:
             output = output.permute(1, 0, 2)
         return self.dropout(output) + identity

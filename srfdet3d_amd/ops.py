@@ -2067,11 +2067,8 @@ def _rows(t, name, width):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), width)
 
 
-def msda(value, shapes, ref, offs, logits, heads, points, out=None):
-    """Multi-scale deformable attention forward (`srf_msda_fwd`, definition in include/srfdet3d.h).  value (B S, heads d) rows of the
-    flattened channels-last pyramid, shapes [(H_l, W_l)] host list, ref (B Q, L, 2) normalised (x, y), offs (B Q, heads L P 2) pixel
-    offsets, logits (B Q, heads L P) raw; value, offs, logits and out may be column slices of wider row buffers (offs and logits of one).
-    -> out (B Q, heads d).  B is B S / S.  No host synchronisation, no allocation outside torch's allocator: capturable."""
+def _msda_inputs(value, shapes, ref, offs, logits, heads, points):
+    """The checks `msda` and `msda_backward` share -> (shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld))."""
     shapes = [(int(h), int(w)) for h, w in shapes]
     L, P, heads = len(shapes), int(points), int(heads)
     S = sum(h * w for h, w in shapes)
@@ -2089,6 +2086,15 @@ def msda(value, shapes, ref, offs, logits, heads, points, out=None):
     if tuple(ref.shape) != (rows, L, 2) or logits.shape[0] != rows or (B and rows % B) or (B == 0 and rows):
         raise ValueError(f"msda: ref {tuple(ref.shape)} / logits {tuple(logits.shape)} do not match {rows} query rows, {L} levels, B = {B}")
     Q = rows // B if B else 0
+    return shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld)
+
+
+def msda(value, shapes, ref, offs, logits, heads, points, out=None):
+    """Multi-scale deformable attention forward (`srf_msda_fwd`, definition in include/srfdet3d.h).  value (B S, heads d) rows of the
+    flattened channels-last pyramid, shapes [(H_l, W_l)] host list, ref (B Q, L, 2) normalised (x, y), offs (B Q, heads L P 2) pixel
+    offsets, logits (B Q, heads L P) raw; value, offs, logits and out may be column slices of wider row buffers (offs and logits of one).
+    -> out (B Q, heads d).  B is B S / S.  No host synchronisation, no allocation outside torch's allocator: capturable."""
+    shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld) = _msda_inputs(value, shapes, ref, offs, logits, heads, points)
     if out is None:
         out = _empty((rows, C), torch.float32, value.device)
     out_ld = _rows(out, "out", C)
@@ -2101,6 +2107,75 @@ def msda(value, shapes, ref, offs, logits, heads, points, out=None):
     check(_lib.lib().srf_msda_fwd(_ptr(value), value_ld, B, hi(flat), L, _ptr(ref), _ptr(offs), offs_ld, _ptr(logits), logits_ld, Q, heads, d,
                                   P, _ptr(out), out_ld, _stream()), "msda_fwd")
     return out
+
+
+def msda_train_enabled():
+    """Whether `compat.transformer.MultiScaleDeformableAttention` trains through `_MsdaFn` (srf_msda_fwd / srf_msda_bwd) where it can.
+    SRF_MSDA_TRAIN=0 keeps training on the torch core; SRF_MSDA=0 does so as well.  Read at every call."""
+    return msda_enabled() and os.environ.get("SRF_MSDA_TRAIN", "1") != "0"
+
+
+def msda_backward(value, shapes, ref, offs, logits, heads, points, grad_out, need=(True, True, True), out=(None, None, None)):
+    """Gradient of `msda` (`srf_msda_bwd`, definition in include/srfdet3d.h): the forward's inputs and grad_out (B Q, heads d) ->
+    (d_value (B S, heads d), d_offs (B Q, heads L P 2), d_logits (B Q, heads L P)); an entry of `need` that is False skips that gradient
+    and returns None in its place.  There is no gradient for ref.  `out` may hold caller-owned row buffers (or column slices of wider
+    ones; d_offs and d_logits of one) for the three gradients: the kernel ADDS into d_value, so a caller who passes one zeroes it;
+    d_value allocated here is zeroed here.  d_offs and d_logits are bit-reproducible, d_value is summed by float atomics.  The same
+    domain as `msda` (ops.msda_supported).  No host synchronisation."""
+    shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld) = _msda_inputs(value, shapes, ref, offs, logits, heads, points)
+    if not isinstance(grad_out, torch.Tensor) or not grad_out.is_cuda:
+        raise RuntimeError("srfdet3d_amd: `grad_out` must be a GPU tensor (no CPU fallback exists)")
+    gout_ld = _rows(grad_out, "grad_out", C)
+    if grad_out.shape[0] != rows:
+        raise ValueError("msda_backward: grad_out has the wrong number of rows")
+    bufs, lds = [], []
+    for want, buf, name, nrows, width, zero in zip(need, out, ("d_value", "d_offs", "d_logits"), (B * S, rows, rows), (C, 2 * ns, ns),
+                                                   (True, False, False)):
+        if not want:
+            buf = None
+        elif buf is None:
+            buf = (torch.zeros if zero else torch.empty)((nrows, width), dtype=torch.float32, device=value.device)
+        elif buf.shape[0] != nrows:
+            raise ValueError(f"msda_backward: {name} has the wrong number of rows")
+        bufs.append(buf)
+        lds.append(width if buf is None else _rows(buf, name, width))
+    if not (msda_supported(B, S, Q, heads, d, L, P, value_ld, offs_ld, logits_ld, gout_ld)
+            and msda_supported(B, S, Q, heads, d, L, P, lds[0], lds[1], lds[2])):
+        raise RuntimeError(f"srfdet3d_amd: msda_backward does not take B {B}, S {S}, Q {Q}, heads {heads}, head_dim {d}, levels {L}, "
+                           f"points {P}, pitches {(value_ld, offs_ld, logits_ld, gout_ld, *lds)} (see ops.msda_supported)")
+    flat = [v for hw in shapes for v in hw]
+    check(_lib.lib().srf_msda_bwd(_ptr(value), value_ld, B, hi(flat), L, _ptr(ref), _ptr(offs), offs_ld, _ptr(logits), logits_ld, Q, heads, d,
+                                  P, _ptr(grad_out), gout_ld, _ptr(bufs[0]), lds[0], _ptr(bufs[1]), lds[1], _ptr(bufs[2]), lds[2],
+                                  _stream()), "msda_bwd")
+    return tuple(bufs)
+
+
+class _MsdaFn(torch.autograd.Function):
+    """`msda` with its gradient (`msda_backward`) for value, offs and logits; ref carries none.  Only the four inputs are saved: the
+    softmax and the sample positions are recomputed in the backward kernel."""
+
+    @staticmethod
+    def forward(ctx, value, ref, offs, logits, shapes, heads, points):
+        out = msda(value, shapes, ref, offs, logits, heads, points)
+        ctx.save_for_backward(value, ref, offs, logits)
+        ctx.cfg = (shapes, heads, points)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        value, ref, offs, logits = ctx.saved_tensors
+        shapes, heads, points = ctx.cfg
+        if grad_out.stride(-1) != 1 or (grad_out.shape[0] > 1 and grad_out.stride(0) % 4) or grad_out.data_ptr() % 16:
+            grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+        d_value, d_offs, d_logits = msda_backward(value, shapes, ref, offs, logits, heads, points, grad_out, need)
+        return d_value, None, d_offs, d_logits, None, None, None
+
+
+def msda_autograd(value, shapes, ref, offs, logits, heads, points):
+    """`msda` under torch.autograd: gradients for value, offs and logits through `srf_msda_bwd`."""
+    return _MsdaFn.apply(value, ref.detach(), offs, logits, [(int(h), int(w)) for h, w in shapes], int(heads), int(points))
 
 
 def stem_conv_nchw(x, weight, scale=None, shift=None, relu=False, out=None):
