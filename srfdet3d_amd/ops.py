@@ -2042,15 +2042,16 @@ def msda_enabled():
     return os.environ.get("SRF_MSDA", "1") != "0"
 
 
-def msda_supported(B, S, Q, heads, head_dim, levels, points, value_ld=None, offs_ld=None, logits_ld=None, out_ld=None):
+def msda_supported(B, S, Q, heads, head_dim, levels, points, value_ld=None, offs_ld=None, logits_ld=None, out_ld=None, more=()):
     """Shapes `srf_msda_fwd` takes, from the shapes alone: head_dim 16 or 32, 1 <= levels <= 4, 1 <= points <= 4, every pitch (floats per
     row; the row's width when None) at least the row's width and a multiple of 4, and each of value (B S rows), offs, logits, out and
-    ref (B Q rows) below 2 GiB.  The 16-byte alignment of the bases is checked at the call."""
+    ref (B Q rows) below 2 GiB.  `more`: (pitch, width, rows) of further tensors held to the same rule (the gradients of
+    `srf_msda_bwd`).  The 16-byte alignment of the bases is checked at the call."""
     if not (B >= 0 and S > 0 and Q >= 0 and heads > 0 and head_dim in (16, 32) and 1 <= levels <= 4 and 1 <= points <= 4):
         return False
     C, ns = heads * head_dim, heads * levels * points
     lds = ((C if value_ld is None else value_ld, C, B * S), (2 * ns if offs_ld is None else offs_ld, 2 * ns, B * Q),
-           (ns if logits_ld is None else logits_ld, ns, B * Q), (C if out_ld is None else out_ld, C, B * Q))
+           (ns if logits_ld is None else logits_ld, ns, B * Q), (C if out_ld is None else out_ld, C, B * Q), *more)
     if any(ld < width or ld % 4 for ld, width, _ in lds):
         return False
     lim = (1 << 31) // 4 - 1
@@ -2068,7 +2069,8 @@ def _rows(t, name, width):
 
 
 def _msda_inputs(value, shapes, ref, offs, logits, heads, points):
-    """The checks `msda` and `msda_backward` share -> (shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld))."""
+    """The checks `msda` and `msda_backward` share -> (shapes flattened for the ABI, ref, (B, S, Q, rows, C, d, L, P, ns),
+    (value_ld, offs_ld, logits_ld))."""
     shapes = [(int(h), int(w)) for h, w in shapes]
     L, P, heads = len(shapes), int(points), int(heads)
     S = sum(h * w for h, w in shapes)
@@ -2086,7 +2088,7 @@ def _msda_inputs(value, shapes, ref, offs, logits, heads, points):
     if tuple(ref.shape) != (rows, L, 2) or logits.shape[0] != rows or (B and rows % B) or (B == 0 and rows):
         raise ValueError(f"msda: ref {tuple(ref.shape)} / logits {tuple(logits.shape)} do not match {rows} query rows, {L} levels, B = {B}")
     Q = rows // B if B else 0
-    return shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld)
+    return [v for hw in shapes for v in hw], ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld)
 
 
 def msda(value, shapes, ref, offs, logits, heads, points, out=None):
@@ -2094,7 +2096,7 @@ def msda(value, shapes, ref, offs, logits, heads, points, out=None):
     flattened channels-last pyramid, shapes [(H_l, W_l)] host list, ref (B Q, L, 2) normalised (x, y), offs (B Q, heads L P 2) pixel
     offsets, logits (B Q, heads L P) raw; value, offs, logits and out may be column slices of wider row buffers (offs and logits of one).
     -> out (B Q, heads d).  B is B S / S.  No host synchronisation, no allocation outside torch's allocator: capturable."""
-    shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld) = _msda_inputs(value, shapes, ref, offs, logits, heads, points)
+    flat, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld) = _msda_inputs(value, shapes, ref, offs, logits, heads, points)
     if out is None:
         out = _empty((rows, C), torch.float32, value.device)
     out_ld = _rows(out, "out", C)
@@ -2103,7 +2105,6 @@ def msda(value, shapes, ref, offs, logits, heads, points, out=None):
     if not msda_supported(B, S, Q, heads, d, L, P, value_ld, offs_ld, logits_ld, out_ld):
         raise RuntimeError(f"srfdet3d_amd: msda does not take B {B}, S {S}, Q {Q}, heads {heads}, head_dim {d}, levels {L}, points {P}, "
                            f"pitches {(value_ld, offs_ld, logits_ld, out_ld)} (see ops.msda_supported)")
-    flat = [v for hw in shapes for v in hw]
     check(_lib.lib().srf_msda_fwd(_ptr(value), value_ld, B, hi(flat), L, _ptr(ref), _ptr(offs), offs_ld, _ptr(logits), logits_ld, Q, heads, d,
                                   P, _ptr(out), out_ld, _stream()), "msda_fwd")
     return out
@@ -2122,13 +2123,13 @@ def msda_backward(value, shapes, ref, offs, logits, heads, points, grad_out, nee
     ones; d_offs and d_logits of one) for the three gradients: the kernel ADDS into d_value, so a caller who passes one zeroes it;
     d_value allocated here is zeroed here.  d_offs and d_logits are bit-reproducible, d_value is summed by float atomics.  The same
     domain as `msda` (ops.msda_supported).  No host synchronisation."""
-    shapes, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld) = _msda_inputs(value, shapes, ref, offs, logits, heads, points)
+    flat, ref, (B, S, Q, rows, C, d, L, P, ns), (value_ld, offs_ld, logits_ld) = _msda_inputs(value, shapes, ref, offs, logits, heads, points)
     if not isinstance(grad_out, torch.Tensor) or not grad_out.is_cuda:
         raise RuntimeError("srfdet3d_amd: `grad_out` must be a GPU tensor (no CPU fallback exists)")
     gout_ld = _rows(grad_out, "grad_out", C)
     if grad_out.shape[0] != rows:
         raise ValueError("msda_backward: grad_out has the wrong number of rows")
-    bufs, lds = [], []
+    bufs, lds, given = [], [], []
     for want, buf, name, nrows, width, zero in zip(need, out, ("d_value", "d_offs", "d_logits"), (B * S, rows, rows), (C, 2 * ns, ns),
                                                    (True, False, False)):
         if not want:
@@ -2139,11 +2140,11 @@ def msda_backward(value, shapes, ref, offs, logits, heads, points, grad_out, nee
             raise ValueError(f"msda_backward: {name} has the wrong number of rows")
         bufs.append(buf)
         lds.append(width if buf is None else _rows(buf, name, width))
-    if not (msda_supported(B, S, Q, heads, d, L, P, value_ld, offs_ld, logits_ld, gout_ld)
-            and msda_supported(B, S, Q, heads, d, L, P, lds[0], lds[1], lds[2])):
+        if buf is not None:
+            given.append((lds[-1], width, nrows))
+    if not msda_supported(B, S, Q, heads, d, L, P, value_ld, offs_ld, logits_ld, gout_ld, more=given):
         raise RuntimeError(f"srfdet3d_amd: msda_backward does not take B {B}, S {S}, Q {Q}, heads {heads}, head_dim {d}, levels {L}, "
                            f"points {P}, pitches {(value_ld, offs_ld, logits_ld, gout_ld, *lds)} (see ops.msda_supported)")
-    flat = [v for hw in shapes for v in hw]
     check(_lib.lib().srf_msda_bwd(_ptr(value), value_ld, B, hi(flat), L, _ptr(ref), _ptr(offs), offs_ld, _ptr(logits), logits_ld, Q, heads, d,
                                   P, _ptr(grad_out), gout_ld, _ptr(bufs[0]), lds[0], _ptr(bufs[1]), lds[1], _ptr(bufs[2]), lds[2],
                                   _stream()), "msda_bwd")
