@@ -108,6 +108,28 @@ int srf_pillar_vfe(const float *voxels, const int *num, const int *coors4, const
 int srf_pillar_scatter_nhwc(const float *feats, const int *coors4, const int *rows_dev, int rows, int C, int B, int H, int W, float *out,
                             srf_stream_t stream);
 
+/* The encoder of the dynamic-voxelization configs (csrc/dvfe.hip, whose header holds the exact definition).
+ *
+ * srf_dvfe_fwd: DynamicVFECustom.forward in eval mode (voxel_encoder.py:162-240, utils.py:8-45) with with_cluster_center,
+ * with_centroid_aware_vox, mode="max", no distance feature and no fusion layer, in two launches behind srf_voxel_unique.
+ * points (n, nf); point2voxel, order, offsets, counts, num_voxels as srf_voxel_unique writes them; voxel_coors (>= rows, 4) (b, z, y, x) its
+ * sorted out_coors; voxel_size / offset: host[3] (x, y, z), offset = v / 2 + range_lo rounded to f32; voxel_center: append xyz - centre.
+ * Position encoder: W1 (d, 3), W2 (d, d) row-major, scale1 / shift1 / scale2 / shift2 (d) the folded eval BatchNorms.  Layers: Wa
+ * (C0, nf + d + 3 * voxel_center), scale_a / shift_a (C0); C1 > 0: Wb (C1, 2 * C0), scale_b / shift_b (C1); C1 == 0: one layer, Wb and
+ * its vectors unused (may be NULL).  out (rows, C1 > 0 ? C1 : C0); rows at or past min(*num_voxels, rows) are written as zeros; points with
+ * point2voxel < 0 (or past that count) touch nothing.  Nothing is read back; deterministic.
+ * workspace: srf_dvfe_workspace_bytes(n, C0) bytes (the per-point output of layer 0, the only per-point intermediate in memory).
+ * Checked before any HIP call, in this order: negative n / rows or non-positive nf, d, C0 (negative C1): SRF_EINVAL; n == 0 or rows == 0:
+ * SRF_OK, no launch; null pointers: SRF_EINVAL; limits (3 <= nf <= 8, d in {16, 32, 64}, C0 and C1 <= 16, points, the workspace and out below
+ * 2^31 bytes): SRF_EUNSUPPORTED; workspace too small: SRF_EWORKSPACE. */
+size_t srf_dvfe_workspace_bytes(int n, int C0);
+int srf_dvfe_fwd(const float *points, int n, int nf, const int *point2voxel, const int *order, const int *offsets, const int *counts,
+                 const int *num_voxels, const int *voxel_coors, int rows, const float *voxel_size /*host[3]*/,
+                 const float *offset /*host[3]*/, int voxel_center, const float *W1, const float *scale1, const float *shift1,
+                 const float *W2, const float *scale2, const float *shift2, int d, const float *Wa, const float *scale_a,
+                 const float *shift_a, int C0, const float *Wb, const float *scale_b, const float *shift_b, int C1, float *out,
+                 void *workspace, size_t workspace_bytes, srf_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * f-4  the step before the path: the CPU transforms of the reference's test pipeline between the decoded
  * sensor data and SRFDet.forward (configs/nus/srfdet_voxel_nusc_LC.py:253-283), on the device.

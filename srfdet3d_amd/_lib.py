@@ -92,6 +92,9 @@ SIGNATURES = {
     "srf_densify_bev": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "srf_pillar_vfe": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _HF, _HF, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
     "srf_pillar_scatter_nhwc": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "srf_dvfe_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "srf_dvfe_fwd": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _HF, _HF, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P,
+                             c_int, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),
     "srf_bitmap_build_padded": (c_int, [_P, c_int, _HI, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "srf_bitmap_rulebook_subm": (c_int, [_P, c_int, _HI, c_int, _HI, _P, _P, _P, _P, _P]),
     "srf_bitmap_strided_outputs": (c_int, [_P, c_int, _HI, c_int, _HI, _HI, _HI, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),

@@ -728,6 +728,59 @@ def pillar_scatter_nhwc(feats, coors4, batch, ny, nx, rows_dev=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- dynamic voxel encoder
+def dvfe_enabled():
+    """SRF_DVFE=0 keeps `plugin.voxel_encoders.DynamicVFECustom` on its torch route on the GPU as well: what the dynamic-voxelization
+    configs ran before csrc/dvfe.hip, the route the tests and tools/bench_dvfe.py alternate against.  Read at every call."""
+    return os.environ.get("SRF_DVFE", "1") != "0"
+
+
+def dvfe_ok(n, rows, nf, d, C0, C1=0):
+    """The shapes `srf_dvfe_fwd` takes (csrc/dvfe.hip, the SRF_EUNSUPPORTED line of the entry point): the raw features in 8 register
+    slots, a position encoder of 16, 32 or 64 channels, layers of at most 16 channels (C1 = 0: one layer), `points`, the per-point
+    workspace and `out` inside 32-bit byte ranges."""
+    return (3 <= nf <= 8 and d in (16, 32, 64) and 1 <= C0 <= 16 and 0 <= C1 <= 16 and below_2gb(n, nf) and below_2gb(n, C0)
+            and below_2gb(rows, C1 if C1 > 0 else C0))
+
+
+def dvfe(points, vm, voxel_size, offset, voxel_center, pos_enc, layers):
+    """DynamicVFECustom.forward in eval mode behind a `VoxelMap`, in two launches (`srf_dvfe_fwd`; definition in csrc/dvfe.hip and, as
+    numpy, in tests/dvfe_ref.py).  points (n, nf) f32; vm the map of their (n, 4) coordinates; voxel_size / offset three host floats
+    (x, y, z); pos_enc = (W1 (d, 3), scale1, shift1, W2 (d, d), scale2, shift2); layers = [(Wa (C0, nf + d + 3 * voxel_center), scale,
+    shift)] or that and (Wb (C1, 2 * C0), scale, shift); scales and shifts are folded eval BatchNorms.  -> (vm.M, C_last); in static mode
+    the rows past the device count are zeros."""
+    points = _dev(points, "points", torch.float32)
+    n, nf = points.shape
+    if n != vm.n:
+        raise ValueError("dvfe: the voxel map belongs to another point list")
+    W1, s1, h1, W2, s2, h2 = [_dev(t, "pos_enc", torch.float32) for t in pos_enc]
+    if not 1 <= len(layers) <= 2:
+        raise ValueError("dvfe: one or two layers")
+    Wa, sa, ha = [_dev(t, "layers[0]", torch.float32) for t in layers[0]]
+    Wb, sb, hb = [_dev(t, "layers[1]", torch.float32) for t in layers[1]] if len(layers) == 2 else (None, None, None)
+    d, C0 = W1.shape[0], Wa.shape[0]
+    C1 = Wb.shape[0] if Wb is not None else 0
+    centre = bool(voxel_center)
+    if tuple(W1.shape) != (d, 3) or tuple(W2.shape) != (d, d) or any(t.numel() != d for t in (s1, h1, s2, h2)):
+        raise ValueError("dvfe: pos_enc must be W1 (d, 3), W2 (d, d) and four vectors of d")
+    if tuple(Wa.shape) != (C0, nf + d + 3 * centre) or sa.numel() != C0 or ha.numel() != C0:
+        raise ValueError("dvfe: the first layer must be (C0, nf + d + 3 * voxel_center) with scale and shift (C0)")
+    if C1 and (tuple(Wb.shape) != (C1, 2 * C0) or sb.numel() != C1 or hb.numel() != C1):
+        raise ValueError("dvfe: the second layer must be (C1, 2 * C0) with scale and shift (C1)")
+    C = C1 or C0
+    out = _empty((vm.M, C), torch.float32, points.device)
+    if n == 0 or vm.M == 0:
+        return out
+    L = _lib.lib()
+    ws_bytes = L.srf_dvfe_workspace_bytes(n, C0)
+    ws = _empty((max(ws_bytes, 1),), torch.uint8, points.device)
+    check(L.srf_dvfe_fwd(_ptr(points), n, nf, _ptr(vm.point2voxel), _ptr(vm.order), _ptr(vm.offsets), _ptr(vm.counts), _ptr(vm.num_dev),
+                         _ptr(vm.coors), vm.M, hf(voxel_size), hf(offset), int(centre), _ptr(W1), _ptr(s1), _ptr(h1), _ptr(W2), _ptr(s2),
+                         _ptr(h2), d, _ptr(Wa), _ptr(sa), _ptr(ha), C0, _ptr(Wb), _ptr(sb), _ptr(hb), C1, _ptr(out), _ptr(ws), ws_bytes,
+                         _stream()), "dvfe_fwd")
+    return out
+
+
 def _densify(feats, indices, batch, spatial_shape):
     feats = _dev(feats, "feats", torch.float32)
     indices = _dev(indices, "indices", torch.int32)

@@ -6,13 +6,20 @@ utils.py:8-45 (same constructor arguments, same parameter names).  Differences t
 the sorted-unique voxel map is computed ONCE per call and shared by the cluster / VFE scatters, and
 "map voxel value back to its points" is an index with that map instead of a dense Z*Y*X*B int64 canvas
 (voxel_encoder.py:118-158 allocates 0.7 GB on the KITTI grid).
+
+In inference on f32 GPU tensors `DynamicVFECustom` in the configuration every config uses (cluster centre through the centroid-aware
+position encoder, mode="max", no distance feature) is TWO kernels behind the voxel map (`ops.dvfe`, csrc/dvfe.hip): one thread per point
+for the mean, the position encoder and the first VFE layer, one thread per voxel for the max and the second layer.  Everything else --
+training, CPU tensors, mode="avg", with_distance, return_point_feats, SRF_DVFE=0 -- runs the torch code below as written.
 """
 import torch
 from torch import nn
 from torch.nn import functional as F
 
+from .. import derived, ops
 from ..compat.cnn import build_norm_layer
 from ..compat.registry import VOXEL_ENCODERS
+from ..dense import fusable
 from ..voxel_layer import DynamicScatter
 
 
@@ -94,9 +101,36 @@ class DynamicVFECustom(nn.Module):
         vm = self.cluster_scatter.voxel_map(pts_coors)
         return self._to_points(voxel_mean, vm.point2voxel)
 
+    def hip_route(self, features):
+        """`ops.dvfe` computes this encoder: SRF_DVFE is on, the input is an f32 GPU tensor outside autograd and autocast, and the net is
+        the cluster centre through the bias-free position encoder, one or two bias-free VFE layers with eval BatchNorm1d and ReLU, a max
+        over the voxel and voxel features as the result (no distance feature, no fusion layer), in a shape the kernel takes."""
+        if not (ops.dvfe_enabled() and features.dim() == 2 and fusable(features)):
+            return False
+        if (not (self._with_cluster_center and self._with_centroid_aware_vox) or self._with_distance or self.return_point_feats
+                or self.fusion_layer is not None or self.vfe_scatter.average_points or not 1 <= self.num_vfe <= 2):
+            return False
+        enc = self.cen2point_pos_enc
+        linears, norms = [enc[0], enc[3]] + [v.linear for v in self.vfe_layers], [enc[1], enc[4]] + [v.norm for v in self.vfe_layers]
+        if any(l.bias is not None for l in linears) or not all(derived.foldable_bn(b, nn.BatchNorm1d) for b in norms):
+            return False
+        n, nf = features.shape
+        d, widths = enc[0].out_features, [v.linear.out_features for v in self.vfe_layers]
+        return (enc[0].in_features == 3 and enc[3].in_features == d and enc[3].out_features == d
+                and self.vfe_layers[0].linear.in_features == nf + d + 3 * bool(self._with_voxel_center)
+                and (self.num_vfe == 1 or self.vfe_layers[1].linear.in_features == 2 * widths[0])
+                and ops.dvfe_ok(n, n, nf, d, widths[0], widths[1] if self.num_vfe == 2 else 0))
+
     def forward(self, features, coors, points=None, img_feats=None, img_metas=None):
         """(N,C) points, (N,4) int (b,z,y,x) with -1 rows for dropped points -> ((M,C') voxel feats, (M,4) coors)."""
         vm = self.cluster_scatter.voxel_map(coors)
+        if self.hip_route(features):
+            enc = self.cen2point_pos_enc
+            pos_enc = (enc[0].weight, *derived.fold_bn(enc[1]), enc[3].weight, *derived.fold_bn(enc[4]))
+            layers = [(v.linear.weight, *derived.fold_bn(v.norm)) for v in self.vfe_layers]
+            voxel_feats = ops.dvfe(features, vm, (self.vx, self.vy, self.vz), (self.x_offset, self.y_offset, self.z_offset),
+                                   self._with_voxel_center, pos_enc, layers)
+            return voxel_feats, vm.coors
         parts = [features]
         if self._with_cluster_center:
             voxel_mean = vm.reduce(features, "mean")
