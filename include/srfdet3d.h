@@ -400,6 +400,25 @@ int srf_spconv_tiles_build(const int *nbr, int nbr_stride, int K, int A_out, con
 size_t srf_spconv_order_ints(int A_out, int K);
 int srf_spconv_order_build(const int *nbr, int nbr_stride, int K, int A_out, const int *rows_dev, int *plan, srf_stream_t stream);
 
+/* K5 with bf16 products (opt-in, inference; no reference counterpart beyond its fp16 option): f32 tensors, every input value and every
+ * weight rounded to bf16 once (round to nearest even), exact products on the bf16 MFMA, f32 accumulation in a fixed order, the epilogue
+ * of srf_spconv_fwd in f32 on the f32 accumulator (alpha, beta and the residual are not rounded), f32 stored.  Defined exactly by
+ * tests/spconv_bf16_ref.py.  The bits of an output row depend on its own pairs, the operands and the epilogue alone (not on A_out,
+ * *rows_dev, `tiles` or the rows beside it); two launches give the same bits.  Non-finite weights are outside the domain.
+ * The shapes (K, Cin, Cout) with this form are the ones srf_spconv_fwd_packed runs on its 64- / 128-channel kernel in the encoders:
+ *   (27, 32, 64)  (27, 64, 64)  (27, 64, 128)  (27, 128, 128)  (3, 128, 128)
+ * srf_spconv_bf16_packed_weight_bytes returns 0 for every other shape; there srf_spconv_bf16_pack_weights and srf_spconv_fwd_bf16
+ * return SRF_EUNSUPPORTED.  srf_spconv_bf16_pack_weights rounds W (K, Cin, Cout) and lays it out for the kernel.  srf_spconv_fwd_bf16
+ * takes the arguments of srf_spconv_fwd_packed with the same meanings and the same codes in the same order, all decided before any
+ * HIP call: bad arguments SRF_EINVAL; another shape SRF_EUNSUPPORTED; A_out == 0 SRF_OK with nothing launched; null pointers
+ * SRF_EINVAL; A_in == 0 or an input of 2 GiB or more SRF_EUNSUPPORTED.  `tiles` may be NULL; the kernel takes no row plan and ignores
+ * it.  Rows at or past *rows_dev are not written. */
+size_t srf_spconv_bf16_packed_weight_bytes(int K, int Cin, int Cout);
+int srf_spconv_bf16_pack_weights(const float *W, int K, int Cin, int Cout, void *packed, srf_stream_t stream);
+int srf_spconv_fwd_bf16(const float *in, int A_in, int Cin, const void *W_packed, int K, const int *nbr, int nbr_stride, int A_out,
+                        int Cout, const float *alpha, const float *beta, const float *residual, int relu, float *out,
+                        const int *rows_dev, const int *tiles, srf_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * K6  SparseConvTensor.dense() (+ the view to (B, C*D, H, W), which is a no-op on this layout).
  * Replaces sparse_encoder_custom.py:135-138.  out: (B, C, D, H, W) contiguous; zero_fill != 0 clears it first.

@@ -10,6 +10,7 @@ Everything held for a module lives in `mod.__dict__["_srf_derived"]`, a plain di
   cgemm, cgemm_split, cgemm_bf16        the same for the implicit-im2col GEMM                     (nhwc.packed)
   conv1x1_nchw                          the `srf_conv1x1` operand                                 (dense.conv1x1_cat_bn_act)
   spconv                                the packed sparse-conv weight                             (sparse._SparseConv)
+  spconv_bf16                           its bf16 operand images, inside `sparse.mfma_dtype`       (sparse._SparseConv)
   dcn, dcn_offset                       the two GEMM operands of a DCNv2 pack                     (compat/dcn.py)
   bn_fold                               (scale, shift) of an eval BatchNorm                       (fold_bn)
   linear_padded                         an nn.Linear weight zero-padded to K % 4 == 0             (dense.linear_graph_safe)

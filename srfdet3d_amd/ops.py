@@ -524,6 +524,39 @@ def pack_spconv_weights(weight):
     return packed
 
 
+def spconv_bf16_supported(K, Cin, Cout):
+    """True for the layer shapes `srf_spconv_fwd_bf16` takes (include/srfdet3d.h); a host call, no GPU work."""
+    return _lib.lib().srf_spconv_bf16_packed_weight_bytes(K, Cin, Cout) > 0
+
+
+# (K, Cin, Cout) whose bf16-product form was NOT faster than the f32 route by more than the spread of three repeats
+# (tools/bench_spconv_bf16.py, profiles/spconv_bf16_layer_bench.json): they keep the f32 route inside the mode
+SPCONV_BF16_NOT_FASTER = frozenset()
+
+
+def spconv_bf16_why_not(K, Cin, Cout):
+    """None when the bf16-product mode (`sparse.mfma_dtype`) takes a layer of this shape, else the reason it keeps its f32 route."""
+    if not spconv_bf16_supported(K, Cin, Cout):
+        return "no bf16-product form for this shape"
+    if (K, Cin, Cout) in SPCONV_BF16_NOT_FASTER:
+        return "not faster (profiles/spconv_bf16_layer_bench.json)"
+    return None
+
+
+def pack_spconv_bf16_weights(weight):
+    """(K,Cin,Cout) f32 -> the bf16 operand images `srf_spconv_fwd_bf16` stages (rounded once, here), or None for a shape without that
+    form."""
+    weight = _dev(weight, "weight", torch.float32)
+    K, Cin, Cout = weight.shape
+    L = _lib.lib()
+    nbytes = L.srf_spconv_bf16_packed_weight_bytes(K, Cin, Cout)
+    if nbytes == 0:
+        return None
+    packed = _empty((nbytes // 2,), torch.int16, weight.device)
+    check(L.srf_spconv_bf16_pack_weights(_ptr(weight), K, Cin, Cout, _ptr(packed), _stream()), "spconv_bf16_pack_weights")
+    return packed
+
+
 def spconv_tiles_wanted(Cin, Cout):
     """True for the layer shapes whose packed kernel takes a row plan (`tiles=` of spconv_fwd): work-balanced row ranges
     (`spconv_tiles`) for the 64- / 128-channel kernels, a mask-sorted row order (`spconv_order`) for the 32-channel one."""
@@ -615,6 +648,44 @@ def spconv_fwd(feats, weight, nbr, alpha=None, beta=None, residual=None, relu=Fa
                                         nbr.stride(0) if A_out > 0 else 0, A_out, Cout,
                                         _ptr(alpha), _ptr(beta), _ptr(residual), int(bool(relu)), _ptr(out), _ptr(rows_dev),
                                         _stream()), "spconv_fwd")
+    if timing is not None:
+        ev1.record()
+        timing["spconv"].append(_SpconvRecord(ev0, ev1, Cin, Cout, K, feats.shape[0], A_out, pair_counts, residual is not None))
+    return out
+
+
+def spconv_fwd_bf16(feats, weight, nbr, packed_bf16, alpha=None, beta=None, residual=None, relu=False, pair_counts=None,
+                    rows_dev=None, tiles=None):
+    """spconv_fwd on the bf16-product kernel (csrc/spconv_bf16.hip; OTHER values than spconv_fwd: inputs and weights rounded to bf16
+    once, exact products, f32 accumulation and epilogue -- tests/spconv_bf16_ref.py is the definition).  `packed_bf16` =
+    pack_spconv_bf16_weights(weight) -- `spconv_fwd(..., packed_bf16=)` as a function of its own, because the argument list of
+    spconv_fwd is part of the recorded call sequence tests/test_sparse_calls.py holds the f32 encoder to.  Routed like `packed=`: an
+    input of 2 GiB or more (or none) takes the f32 route srf_spconv_fwd.  `tiles` may be a plan of spconv_tiles(nbr); the kernel takes
+    none and its bits do not depend on it.  Inference only: a wanted gradient raises."""
+    if torch.is_grad_enabled() and (feats.requires_grad or weight.requires_grad or (residual is not None and residual.requires_grad)
+                                    or (alpha is not None and alpha.requires_grad) or (beta is not None and beta.requires_grad)):
+        raise RuntimeError("srfdet3d_amd: the bf16-product sparse convolution has no backward (inference under no_grad only)")
+    if packed_bf16 is None:
+        raise RuntimeError("srfdet3d_amd: spconv_fwd_bf16 needs pack_spconv_bf16_weights(weight); this shape has no bf16-product form")
+    feats = _dev(feats, "feats", torch.float32)
+    K, Cin, Cout = weight.shape
+    if not 0 < feats.shape[0] * Cin * 4 < 2 ** 31:   # 32-bit buffer offsets into the input
+        return spconv_fwd(feats, weight, nbr, alpha, beta, residual, relu, pair_counts=pair_counts, rows_dev=rows_dev)
+    if not nbr.is_cuda or nbr.dtype != torch.int32 or nbr.stride(1) != 1:
+        raise RuntimeError("srfdet3d_amd: `nbr` must be a GPU int32 tensor with unit inner stride")
+    A_out = nbr.shape[1]
+    out = _empty((A_out, Cout), torch.float32, feats.device)
+    if residual is not None:
+        residual = _dev(residual, "residual", torch.float32)
+    timing = KERNEL_TIMING
+    if timing is not None and torch.cuda.is_current_stream_capturing():
+        timing = None
+    if timing is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    check(_lib.lib().srf_spconv_fwd_bf16(_ptr(feats), feats.shape[0], Cin, _ptr(packed_bf16), K, _ptr(nbr),
+                                         nbr.stride(0) if A_out > 0 else 0, A_out, Cout, _ptr(alpha), _ptr(beta), _ptr(residual),
+                                         int(bool(relu)), _ptr(out), _ptr(rows_dev), _ptr(tiles), _stream()), "spconv_fwd_bf16")
     if timing is not None:
         ev1.record()
         timing["spconv"].append(_SpconvRecord(ev0, ev1, Cin, Cout, K, feats.shape[0], A_out, pair_counts, residual is not None))

@@ -82,6 +82,30 @@ class SRFDet(BaseModule):
             self._img_mfma_dtype = dtype
             self._drop_derived_state()
 
+    @property
+    def sparse_mfma_dtype(self):
+        """None (default: f32) or torch.bfloat16: the 64- and 128-output-channel layers of the sparse encoder (`pts_middle_encoder`) run
+        on the hand-written bf16-product kernel (`sparse.mfma_dtype`, csrc/spconv_bf16.hip): f32 tensors, operands rounded to bf16 once
+        per layer, f32 accumulation and epilogue.  Its other layers, the voxel encoder, SECOND, the BEV FPN, the decoder and the camera
+        branch stay as they are; independent of `img_mfma_dtype`.  Inference under no_grad in eval mode only: any other pass, and a
+        pass in which no layer took the bf16 route, raises.  Setting it drops the packed weights and the captured graphs
+        (`_drop_derived_state`); `enable_hip_graphs()` captures whichever mode is set."""
+        enc = getattr(self, "pts_middle_encoder", None)
+        return getattr(enc, "mfma_dtype", None)
+
+    @sparse_mfma_dtype.setter
+    def sparse_mfma_dtype(self, dtype):
+        if dtype is not None and dtype != torch.bfloat16:
+            raise ValueError(f"sparse_mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
+        enc = getattr(self, "pts_middle_encoder", None)
+        if not hasattr(enc, "mfma_dtype"):
+            if dtype is None:
+                return
+            raise NotImplementedError(f"sparse_mfma_dtype needs a sparse-convolution middle encoder, not {type(enc).__name__}")
+        if dtype != enc.mfma_dtype:
+            enc.mfma_dtype = dtype
+            self._drop_derived_state()
+
     def enable_hip_graphs(self, enabled=True, img_overlap=False, whole_frame=True):
         """Replay the static-shape tail (SECOND -> FPN -> decoder -> decode) as a captured hipGraph in `simple_test`
         (see srfdet3d_amd/graphs.py), and with images the VoVNet -> FPN branch as a second graph.  Results are identical

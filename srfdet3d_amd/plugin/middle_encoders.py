@@ -7,6 +7,7 @@ import torch
 
 from ..compat.cnn import BaseModule
 from ..compat.registry import MIDDLE_ENCODERS
+from .. import sparse
 from ..sparse import SparseBasicBlock, SparseConvTensor, SparseSequential, _SparseConv, make_sparse_convmodule
 
 
@@ -35,6 +36,11 @@ class SparseEncoderCustom(BaseModule):
         # reorder the active sites spatially before the first conv (results per site are unchanged: every output is
         # an fma chain ordered by kernel offset and channel, never by row); see ops.spatial_order
         self.spatial_sort = True
+        # None (f32, the default) or torch.bfloat16: `forward_levels` runs the layers inside `sparse.mfma_dtype(self.mfma_dtype)` -- the
+        # 64- / 128-output-channel layers on the bf16-product kernel (`SRFDet.sparse_mfma_dtype` sets it).  `mfma_routes`: a list that
+        # receives the per-layer route records of every pass, or None.
+        self.mfma_dtype = None
+        self.mfma_routes = None
 
         pre_act = order[0] != "conv"
         self.conv_input = make_sparse_convmodule(in_channels, base_channels, 3, norm_cfg=norm_cfg, padding=1,
@@ -81,13 +87,21 @@ class SparseEncoderCustom(BaseModule):
 
     def forward_levels(self, voxel_features, coors, batch_size, static_caps=None):
         """-> (BEV map, the input sparse.Level): its `chain()` holds the level every strided conv produced."""
+        if self.mfma_dtype is not None and (torch.is_grad_enabled() or self.training):
+            # training in the mode is not implemented: no quiet f32 pass instead
+            raise RuntimeError("the sparse encoder's mfma_dtype covers inference under no_grad in eval mode only")
         coors = coors.int()
         if static_caps is not None or (self.spatial_sort and coors.is_cuda and coors.shape[0] > 0):
             # rows into (b, y, x, z) order + the level's occupancy bitmap: all rulebooks below are built by bitmap rank
             x = SparseConvTensor.sorted_by_bitmap(voxel_features, coors, self.sparse_shape, int(batch_size), static_caps)
         else:
             x = SparseConvTensor(voxel_features, coors, self.sparse_shape, int(batch_size))
-        return self._layers(x).dense_bev(), x.level
+        with sparse.mfma_dtype(self.mfma_dtype, routes=self.mfma_routes) as mode:
+            bev = self._layers(x).dense_bev()
+        if self.mfma_dtype is not None and mode.launches == 0:
+            raise RuntimeError("the sparse encoder's mfma_dtype is set but none of its layers has a bf16-product form "
+                               "(the 64- and 128-output-channel shapes of srf_spconv_fwd_bf16): no quiet f32 pass")
+        return bev, x.level
 
     def _modules_in_order(self):
         return [self.conv_input] + list(self.encoder_layers._modules.values()) + [self.conv_out]

@@ -31,6 +31,41 @@ def _triple(v):
     return [int(v)] * 3
 
 
+# ---- the bf16-product mode of the sparse encoder (csrc/spconv_bf16.hip) --------------------------------------------------------
+_MFMA = None     # the innermost active `mfma_dtype` context, or None: every layer on its f32 route
+
+
+class mfma_dtype:
+    """Within `with sparse.mfma_dtype(torch.bfloat16):` a `_SparseConv` of one of the five 64- / 128-output-channel shapes of
+    `srf_spconv_fwd_bf16` (include/srfdet3d.h) runs on the bf16-product kernel: f32 tensors, inputs and weights rounded to bf16 once,
+    exact products, f32 accumulation and the f32 epilogue (BatchNorm fold, residual, ReLU) -- defined by tests/spconv_bf16_ref.py.
+    Every other layer keeps its f32 route: the 16- and 32-output-channel layers and any shape without that form, a shape that
+    `ops.SPCONV_BF16_NOT_FASTER` lists, a layer in training mode or with gradients enabled.  Off by default; `mfma_dtype(None)` inside
+    an active context switches it off again.
+
+    routes: a list that receives one dict(layer=, route="bf16" | "f32", why=) per executed layer.  `launches` counts the layers that
+    ran on the bf16 kernel.  Process-wide while the context is open, as `nhwc.mfma_dtype`; nothing outside the context sees it."""
+
+    def __init__(self, dtype, routes=None):
+        if dtype is not None and dtype != torch.bfloat16:
+            raise ValueError(f"sparse.mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
+        self.dtype, self.routes, self.launches = dtype, routes, 0
+
+    def __enter__(self):
+        global _MFMA
+        self._outer, _MFMA = _MFMA, (self if self.dtype is not None else None)
+        return self
+
+    def __exit__(self, *exc):
+        global _MFMA
+        _MFMA = self._outer
+        return False
+
+
+def mfma_active():
+    return _MFMA is not None
+
+
 class Rulebook:
     """The neighbour table `nbr` (K, A_out) of one kernel on one level, its pair counts, and the row plans its layers asked for."""
 
@@ -190,9 +225,17 @@ class _SparseConv(SparseModule):
     def index(self, level):
         """-> (Rulebook, row plan or None, output Level): what this layer needs of the coordinates alone, built on first use, kept on `level`."""
         rb, out = (level.subm(self.kernel_size), level) if self.subm else level.strided(self.indice_key, self.kernel_size, self.stride, self.padding)
-        plan = None if self.training or not self._packable else \
+        plan = None if self.training or not self._packable or self._bf16_why_not() is None else \
             rb.plan(self.in_channels, self.out_channels, rb.nbr.shape[0], self.subm, out.rows_dev)
         return rb, plan, out
+
+    def _bf16_why_not(self):
+        """None when the active bf16-product mode takes this layer, else why it keeps its f32 route ("" outside the mode)."""
+        if _MFMA is None:
+            return ""
+        if self.training or torch.is_grad_enabled():
+            return "training mode or gradients enabled"
+        return ops.spconv_bf16_why_not(math.prod(self.kernel_size), self.in_channels, self.out_channels)
 
     def forward(self, x, bn=None, relu=False, residual=None):
         """conv, optionally with an eval-mode BatchNorm1d, residual rows and ReLU fused into the same kernel."""
@@ -205,6 +248,18 @@ class _SparseConv(SparseModule):
                 beta = beta + self.bias * alpha
         elif self.bias is not None:
             alpha, beta = torch.ones_like(self.bias), self.bias
+        why = self._bf16_why_not()
+        if _MFMA is not None:
+            if _MFMA.routes is not None:
+                _MFMA.routes.append(dict(layer=f"{self.in_channels}->{self.out_channels} k{rb.nbr.shape[0]} "
+                                               f"{'subm' if self.subm else 'strided'} @{rb.nbr.shape[1]}",
+                                         route="f32" if why else "bf16", why=why))
+            _MFMA.launches += why is None
+        if why is None:   # (an input of 2 GiB or more falls back to srf_spconv_fwd inside ops.spconv_fwd_bf16)
+            packed_bf16 = derived.get(self, "spconv_bf16", (self.weight,), lambda: ops.pack_spconv_bf16_weights(w.detach()))
+            feats = ops.spconv_fwd_bf16(x.features, w, rb.nbr, packed_bf16, alpha, beta, residual, relu, pair_counts=rb.counts,
+                                        rows_dev=out.rows_dev)
+            return SparseConvTensor(feats, level=out)
         packed = None if self.training or not self._packable else \
             derived.get(self, "spconv", (self.weight,), lambda: ops.pack_spconv_weights(w.detach()))
         feats = ops.spconv_fwd(x.features, w, rb.nbr, alpha, beta, residual, relu, pair_counts=rb.counts, packed=packed,
