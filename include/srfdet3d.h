@@ -676,6 +676,18 @@ size_t srf_conv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, in
 int srf_conv_wgrad_nhwc(const float *g, long long g_ld, const float *x, long long x_ld, int N, int H, int W, int Cin, int Cout, int ksize,
                         void *workspace, size_t workspace_bytes, float *dW, srf_stream_t stream);
 
+/* srf_conv_wgrad_nhwc_bf16 (training, the opt-in bf16-product mode): the same weight gradient on ONE bf16 product per f32 product,
+ *   dW[co][ci][ky][kx] = sum over p of bf16(g[p][co]) * bf16(x[p + tap][ci]),
+ * each operand rounded once to nearest even, products exact in f32, f32 accumulation, pixels outside the image zero, the pixel ranges
+ * added in a fixed order: deterministic (csrc/wgrad_bf16.hip; reduced precision, the caller's explicit choice).  Arguments as
+ * srf_conv_wgrad_nhwc; workspace: srf_conv_wgrad_bf16_workspace_bytes bytes (partial sums and the bf16 planes of both operands; 0 for
+ * sizes the entry point refuses), 16-byte aligned.  Any map width.  Checked in this order, before any HIP call: non-positive sizes, a
+ * pitch below the channel count, null pointers: SRF_EINVAL; ksize other than 1 or 3, Cin % 4, Cout % 4, g_ld % 4, x_ld % 4, a base or
+ * workspace that is not 16-byte aligned, a tensor of 2 GB or more: SRF_EUNSUPPORTED; workspace too small: SRF_EWORKSPACE. */
+size_t srf_conv_wgrad_bf16_workspace_bytes(int N, int H, int W, int Cin, int Cout, int ksize);
+int srf_conv_wgrad_nhwc_bf16(const float *g, long long g_ld, const float *x, long long x_ld, int N, int H, int W, int Cin, int Cout,
+                             int ksize, void *workspace, size_t workspace_bytes, float *dW, srf_stream_t stream);
+
 /* srf_conv1x1_nhwc_topdown: an FPN lateral convolution with the top-down step in its epilogue (mmdet FPN.forward:
  * `laterals[i - 1] += F.interpolate(laterals[i], size=..., mode="nearest")`, necks of configs/nus/srfdet_voxel_nusc_LC.py:55-64
  * and :67-76): y[n][py][px][co] = act(conv) + top[n][floor(py Ht / H)][floor(px Wt / W)][co].  x rows are the pixels of an

@@ -2066,6 +2066,35 @@ def conv_wgrad_nhwc(g, x, ksize):
     return dW
 
 
+def conv_wgrad_bf16_supported(g, x, ksize):
+    """Shapes `conv_wgrad_nhwc_bf16` takes: as `conv_wgrad_supported`, at any map width."""
+    try:
+        g_ld, x_ld = nhwc_ld(g), nhwc_ld(x)
+    except RuntimeError:
+        return False
+    N, H, W, Cin = x.shape
+    Cout = g.shape[3]
+    return (ksize in (1, 3) and tuple(g.shape[:3]) == (N, H, W) and N * H * W > 0 and Cin > 0 and Cout > 0 and Cin % 4 == 0 and Cout % 4 == 0
+            and g_ld % 4 == 0 and x_ld % 4 == 0 and g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and below_2gb(N * H * W, max(g_ld, x_ld)))
+
+
+def conv_wgrad_nhwc_bf16(g, x, ksize):
+    """Weight gradient of a stride-1 Conv2d as `conv_wgrad_nhwc`, on one bf16 product per f32 product: `srf_conv_wgrad_nhwc_bf16` (both
+    operands rounded to bf16 once, exact products, f32 accumulation, fixed summation order: deterministic; csrc/wgrad_bf16.hip).  Reduced
+    precision, the caller's explicit choice."""
+    if not conv_wgrad_bf16_supported(g, x, ksize):
+        raise ValueError("conv_wgrad_nhwc_bf16: unsupported shapes / layout")
+    N, H, W, Cin = x.shape
+    Cout = g.shape[3]
+    L = _lib.lib()
+    nbytes = L.srf_conv_wgrad_bf16_workspace_bytes(N, H, W, Cin, Cout, ksize)
+    ws = _empty((max(nbytes, 4) // 4,), torch.float32, x.device)
+    dW = _empty((Cout, Cin, ksize, ksize), torch.float32, x.device)
+    check(L.srf_conv_wgrad_nhwc_bf16(_ptr(g), nhwc_ld(g), _ptr(x), nhwc_ld(x), N, H, W, Cin, Cout, ksize, _ptr(ws), nbytes, _ptr(dW), _stream()),
+          "conv_wgrad_nhwc_bf16")
+    return dW
+
+
 def conv_gemm_nhwc_supported(x):
     """Layout / size limits of srf_conv_gemm_nhwc as `conv_gemm_nhwc` drives it (batches are split, one image must fit)."""
     try:

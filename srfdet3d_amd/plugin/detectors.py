@@ -1,10 +1,12 @@
 """`SRFDet` / `SRFDetWaymo` detectors (mmdet3d_plugin/models/detectors/srfdet.py:13-343, srfdetwaymo.py:6-41):
 voxelize -> voxel encoder -> sparse middle encoder -> SECOND -> FPN -> SRFDetHead.  Same registry names,
 constructor arguments, sub-module attribute names and forward signatures as the reference."""
+import contextlib
+
 import torch
 import torch.nn.functional as F
 
-from .. import nhwc
+from .. import nhwc, train_conv
 from ..compat.boxes import bbox3d2result
 from ..compat.cnn import BaseModule
 from ..compat.registry import (DETECTORS, build_backbone, build_head, build_middle_encoder, build_neck,
@@ -57,6 +59,26 @@ class SRFDet(BaseModule):
         # (srfdet.py:141); opt-in, never the default.
         self.img_autocast_dtype = None
         self._img_mfma_dtype = None
+        self._train_mfma_dtype = None
+        self.train_mfma_routes = None     # a list here receives `train_conv.mfma_dtype`'s per-direction report of every recording pass
+
+    @property
+    def train_mfma_dtype(self):
+        """None (default: f32) or torch.bfloat16: while autograd is recording, the image backbone + neck run inside
+        `train_conv.mfma_dtype` -- the convolutions of their training nodes on one bf16 product per f32 product in all three directions
+        (csrc/gemm_bf16.hip, csrc/wgrad_bf16.hip): f32 tensors, operands rounded to bf16 once, f32 accumulation.  The head's `img_convs`
+        and everything LiDAR stay f32.  Independent of `img_mfma_dtype` (inference only); no-grad passes ignore it; together with
+        `img_autocast_dtype` it raises; a recording pass in which no direction took a bf16 route raises (never a quiet f32 pass)."""
+        return self._train_mfma_dtype
+
+    @train_mfma_dtype.setter
+    def train_mfma_dtype(self, dtype):
+        if dtype is not None:
+            if dtype != torch.bfloat16:
+                raise ValueError(f"train_mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
+            if self.img_autocast_dtype is not None:
+                raise ValueError("train_mfma_dtype and img_autocast_dtype exclude each other: set img_autocast_dtype = None first")
+        self._train_mfma_dtype = dtype
 
     @property
     def img_mfma_dtype(self):
@@ -261,8 +283,12 @@ class SRFDet(BaseModule):
             if torch.is_grad_enabled() or self.training:
                 # training in the mode is not implemented: no quiet f32 pass through the modules instead
                 raise RuntimeError("img_mfma_dtype covers inference under no_grad in eval mode only (the channels-last executor)")
+        train_mode = self._train_mfma_dtype if torch.is_grad_enabled() else None     # no-grad passes ignore the switch
+        if train_mode is not None and self.img_autocast_dtype is not None:
+            raise ValueError("train_mfma_dtype and img_autocast_dtype exclude each other")
         with torch.autocast(img.device.type, dtype=self.img_autocast_dtype, enabled=self.img_autocast_dtype is not None), \
-                nhwc.mfma_dtype(self._img_mfma_dtype) as mode:
+                nhwc.mfma_dtype(self._img_mfma_dtype) as mode, \
+                (train_conv.mfma_dtype(train_mode, routes=self.train_mfma_routes) if train_mode is not None else contextlib.nullcontext()) as tmode:
             feats = self.img_backbone(img)
             if isinstance(feats, dict):
                 feats = list(feats.values())
@@ -272,6 +298,9 @@ class SRFDet(BaseModule):
             # a missing kernel route is an error, never a quiet f32 pass (training, autograd or a CPU tensor leave the executor)
             raise RuntimeError("img_mfma_dtype is set but the image branch did not run on the channels-last executor "
                                "(it covers fp32 GPU inference under no_grad with BatchNorm in eval mode)")
+        if train_mode is not None and tmode.launches == 0:
+            raise RuntimeError("train_mfma_dtype is set but no layer of the image backbone + neck took a bf16 route under autograd "
+                               "(it covers the training nodes of train_conv.py on fp32 channels-last GPU tensors)")
         out = [f.float().view(B, f.shape[0] // B, *f.shape[1:]) for f in feats]
         return nhwc.ConsumedLevels(out) if isinstance(feats, nhwc.ConsumedLevels) else out
 

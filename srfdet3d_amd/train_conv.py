@@ -109,15 +109,112 @@ def fused_layer_ok(k, N, H, W, Cin, Cout):
     return k == 1 and gemm_layer_ok(N, H, W, Cin, Cout)
 
 
+# ---- the bf16-product mode (csrc/gemm_bf16.hip forward and data gradient, csrc/wgrad_bf16.hip weight gradient) ---------------------
+_MFMA = None     # the innermost active `mfma_dtype` context, or None: every node on its f32 routes
+
+
+class mfma_dtype:
+    """Within `with train_conv.mfma_dtype(torch.bfloat16):` the convolutions of `_Wino43Conv`, `_ConvAffineRelu`, `_OSAChain` and `_Conv1x1`
+    run on ONE bf16 product per f32 product in all three directions: f32 tensors, both operands rounded to bf16 once, exact products, f32
+    accumulation -- forward on `srf_conv_gemm_nhwc_bf16` (3x3; no Winograd in this mode) / `srf_conv1x1_nhwc_bf16`, the data gradient on
+    the same kernels with the rotated / transposed weight, the weight gradient on `srf_conv_wgrad_nhwc_bf16`.  All three see the same
+    bf16(W).  Everything else is unchanged and f32: the folded-BatchNorm / ReLU epilogue, `srf_nhwc_affine_relu_bwd`, `bn_eval_grads`,
+    `_ESEApply`, the depthwise node and the gate.  A node records the mode in its forward pass and its backward pass follows that record
+    (`loss.backward()` runs after the context has closed).  Off by default; `mfma_dtype(None)` switches an outer context off.
+
+    A layer whose forward or data gradient the bf16 kernels cannot take (`bf16_layer_ok`, operand alignment) keeps today's route for
+    both; a weight gradient the new kernel refuses goes through `_weight_grad`.
+    routes: a list that receives one dict(layer=, direction="fwd" | "dgrad" | "wgrad", route="bf16" | "f32", why=) per executed
+    direction; `launches` counts the directions that ran on the bf16 kernels.  Process-wide while open, as `nhwc.mfma_dtype`."""
+
+    def __init__(self, dtype, routes=None):
+        if dtype is not None and dtype != torch.bfloat16:
+            raise ValueError(f"train_conv.mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
+        self.dtype, self.routes, self.launches = dtype, routes, 0
+
+    def __enter__(self):
+        global _MFMA
+        self._outer, _MFMA = _MFMA, (self if self.dtype is not None else None)
+        return self
+
+    def __exit__(self, *exc):
+        global _MFMA
+        _MFMA = self._outer
+        return False
+
+
+def bf16_layer_ok(k, N, H, W, Cin, Cout):
+    """A k x k layer on the bf16-product GEMMs forward (K = Cin) and backward (K = Cout), as dense tensors: both channel counts in chunks
+    of 32, a 128-row tile of either tensor and (3x3: one image of either) inside the kernels' 32-bit ranges."""
+    C = max(Cin, Cout)
+    return (k in (1, 3) and N > 0 and ops.gemm_k_ok(Cin) and ops.gemm_k_ok(Cout) and ops.gemm_rows_ok(C) and (k == 1 or ops.below_2gb(H * W, C)))
+
+
+class _LayerMode:
+    """What a node keeps of the mode that was active in its forward pass: the context (its report outlives it) and why the layer's
+    forward and data gradient stay f32 (None: they run on the bf16 kernels)."""
+    __slots__ = ("mode", "layer", "why")
+
+    def __init__(self, mode, layer, why):
+        self.mode, self.layer, self.why = mode, layer, why
+
+    @property
+    def bf16(self):
+        return self.why is None
+
+    def report(self, direction, why=False):
+        why = self.why if why is False else why
+        route = "f32" if why else "bf16"
+        if self.mode.routes is not None:
+            self.mode.routes.append(dict(layer=self.layer, direction=direction, route=route, why=why))
+        self.mode.launches += route == "bf16"
+
+
+def _layer_mode(k, xn, Cout, out=None):
+    """At a layer's forward pass: None outside the mode, else its record (and the report's "fwd" row)."""
+    m = _MFMA
+    if m is None:
+        return None
+    N, H, W, Cin = xn.shape
+    x_ld, y_ld = ops.nhwc_ld(xn), (ops.nhwc_ld(out) if out is not None else Cout)
+    why = None
+    if not (ops.gemm_k_ok(Cin) and ops.gemm_k_ok(Cout)):
+        why = "input or output channels are no multiple of 32"
+    elif not (ops.operand_ok(x_ld, xn.data_ptr()) and (out is None or ops.operand_ok(y_ld, out.data_ptr()))):
+        why = "operand alignment"
+    elif not (bf16_layer_ok(k, N, H, W, Cin, Cout) and ops.gemm_rows_ok(max(x_ld, y_ld)) and (k == 1 or ops.below_2gb(H * W, x_ld))):
+        why = "beyond the 32-bit ranges"
+    lm = _LayerMode(m, f"{Cin}->{Cout} {k}x{k} @{N}x{H}x{W}", why)
+    lm.report("fwd")
+    return lm
+
+
+def _weight_grad_in(lm, gn, xn, weight, k):
+    """The weight gradient of a node whose forward pass recorded lm: outside the mode `_weight_grad` as ever; in it `srf_conv_wgrad_nhwc_bf16`
+    (whatever route the layer's other two directions took), unless the kernel refuses the operands."""
+    if lm is None:
+        return _weight_grad(gn, xn, weight, k)
+    if ops.conv_wgrad_bf16_supported(gn, xn, k):
+        lm.report("wgrad", None)
+        return ops.conv_wgrad_nhwc_bf16(gn, xn, k)
+    lm.report("wgrad", "channel counts or pitches that are no multiple of 4, alignment, or a tensor of 2 GB")
+    return _weight_grad(gn, xn, weight, k)
+
+
 # ---- one layer in its three directions ---------------------------------------------------------------------------------
 def _nhwc(t):
     """logical NCHW tensor -> its (N, H, W, C) view over channels-last storage (a copy only if it was not channels-last)."""
     return t.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
 
 
-def _layer_fwd(xn, w, scale=None, shift=None, relu=False, out=None):
-    """A layer on the channels-last slice xn: w (Cout, Cin, 3, 3) on `srf_wino43`, (Cout, Cin[, 1, 1]) on the 1x1 GEMM; packed once per call."""
+def _layer_fwd(xn, w, scale=None, shift=None, relu=False, out=None, bf16=False):
+    """A layer on the channels-last slice xn: w (Cout, Cin, 3, 3) on `srf_wino43`, (Cout, Cin[, 1, 1]) on the 1x1 GEMM; packed once per call.
+    bf16 (the `mfma_dtype` mode): on `srf_conv_gemm_nhwc_bf16` / `srf_conv1x1_nhwc_bf16` instead, the weight rounded to bf16 as it is packed."""
     Cout = w.shape[0]
+    if bf16:
+        if w.dim() == 4 and w.shape[2] == 3:
+            return ops.conv_gemm_nhwc(xn, None, Cout, (3, 3), 1, 1, scale, shift, relu, out=out, packed_bf16=ops.pack_conv_gemm_bf16_weights(w))
+        return ops.conv1x1_nhwc(xn, None, Cout, scale, shift, relu, out=out, packed_bf16=ops.pack_conv1x1_nhwc_bf16_weights(w.reshape(Cout, -1)))
     if w.dim() == 4 and w.shape[2] == 3:
         return ops.wino43(xn, ops.pack_wino43_weights(w), Cout, scale, shift, relu, out=out)
     w2 = w.reshape(Cout, -1)
@@ -125,11 +222,19 @@ def _layer_fwd(xn, w, scale=None, shift=None, relu=False, out=None):
                             packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w2))
 
 
-def _layer_dgrad(gn, w):
-    """Its data gradient: the same kernels on the weight rotated by 180 degrees with the channel axes swapped (3x3), transposed (1x1)."""
+def _layer_dgrad(gn, w, lm=None):
+    """Its data gradient: the same kernels on the weight rotated by 180 degrees with the channel axes swapped (3x3), transposed (1x1).
+    lm: what the node recorded of the mode in its forward pass (rounding commutes with the rotation and the transposition: bf16(W) again)."""
     if w.shape[2] == 3:
-        return _layer_fwd(gn, w.flip(2, 3).transpose(0, 1).contiguous())      # (Cin, Cout, 3, 3)
-    return _layer_fwd(gn, w.reshape(w.shape[0], w.shape[1]).t().contiguous())  # (Cin, Cout)
+        wt = w.flip(2, 3).transpose(0, 1).contiguous()      # (Cin, Cout, 3, 3)
+    else:
+        wt = w.reshape(w.shape[0], w.shape[1]).t().contiguous()  # (Cin, Cout)
+    if lm is None:
+        return _layer_fwd(gn, wt)
+    lm.report("dgrad")
+    if lm.bf16 and not ops.operand_ok(ops.nhwc_ld(gn), gn.data_ptr()):
+        gn = gn.contiguous()
+    return _layer_fwd(gn, wt, bf16=lm.bf16)
 
 
 def _weight_grad(gn, xn, weight, k):
@@ -178,7 +283,12 @@ def eligible(conv, x):
 class _Wino43Conv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
-        y = _layer_fwd(_nhwc(x), weight.detach(), None, None if bias is None else bias.detach(), False)
+        xn = _nhwc(x)
+        ctx.lm = lm = _layer_mode(3, xn, weight.shape[0])
+        if lm is None:
+            y = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False)
+        else:
+            y = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False, bf16=lm.bf16)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.keep_cl = x.stride(1) == 1
@@ -197,11 +307,11 @@ class _Wino43Conv(torch.autograd.Function):
         gy_cl = gyn.permute(0, 3, 1, 2)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = _layer_dgrad(gyn, weight.detach()).permute(0, 3, 1, 2)
+            gx = _layer_dgrad(gyn, weight.detach(), ctx.lm).permute(0, 3, 1, 2)
             if not ctx.keep_cl:
                 gx = gx.contiguous()
         if ctx.needs_input_grad[1]:
-            gw = _weight_grad(gyn, _nhwc(x), weight, 3)
+            gw = _weight_grad_in(ctx.lm, gyn, _nhwc(x), weight, 3)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gy_cl.sum(dim=(0, 2, 3))
         return gx, gw, gb
@@ -223,7 +333,8 @@ class _ConvAffineRelu(torch.autograd.Function):
         fold = ops.bn_eval_fold(gamma.detach(), beta.detach(), mean, var, eps)     # s, t0, inv in one launch
         s, t0 = fold[0], fold[1]
         t = t0 if bias is None else t0 + bias.detach() * s
-        yn = _layer_fwd(xn, weight.detach(), s, t, relu)
+        ctx.lm = lm = _layer_mode(weight.shape[2], xn, weight.shape[0])
+        yn = _layer_fwd(xn, weight.detach(), s, t, relu) if lm is None else _layer_fwd(xn, weight.detach(), s, t, relu, bf16=lm.bf16)
         ctx.save_for_backward(x, weight, yn, fold, mean)
         ctx.relu, ctx.has_bias = bool(relu), bias is not None
         return yn.permute(0, 3, 1, 2)          # logical NCHW, channels-last strides
@@ -237,9 +348,9 @@ class _ConvAffineRelu(torch.autograd.Function):
         if ctx.has_bias and need[2]:
             gb = sums[0] * fold[0]
         if need[0]:
-            gx = _layer_dgrad(gz, weight.detach()).permute(0, 3, 1, 2)
+            gx = _layer_dgrad(gz, weight.detach(), ctx.lm).permute(0, 3, 1, 2)
         if need[1]:
-            gw = _weight_grad(gz, _nhwc(x), weight, weight.shape[2])
+            gw = _weight_grad_in(ctx.lm, gz, _nhwc(x), weight, weight.shape[2])
         return gx, gw, gb, ggamma, gbeta, None, None, None, None
 
 
@@ -332,14 +443,24 @@ class _OSAChain(torch.autograd.Function):
         cat = torch.empty((N, H, W, Ctot), dtype=torch.float32, device=x.device)
         cat[..., :Cin].copy_(xn)
         saved = []
+        ctx.lms = lms = []         # per layer: what it recorded of the `mfma_dtype` mode (None outside it)
         lo, hi = 0, Cin            # the input slice of the next layer
         for i, p in enumerate(layers):
             fold = ops.bn_eval_fold(p.gamma.detach(), p.beta.detach(), p.mean, p.var, eps[i])
             if i < L:
-                _layer_fwd(cat[..., lo:hi], p.weight.detach(), fold[0], fold[1], True, out=cat[..., hi:hi + widths[i]])
+                xs, ys = cat[..., lo:hi], cat[..., hi:hi + widths[i]]
+                lms.append(_layer_mode(3, xs, widths[i], ys))
+                if lms[i] is None:
+                    _layer_fwd(cat[..., lo:hi], p.weight.detach(), fold[0], fold[1], True, out=cat[..., hi:hi + widths[i]])
+                else:
+                    _layer_fwd(xs, p.weight.detach(), fold[0], fold[1], True, out=ys, bf16=lms[i].bf16)
                 lo, hi = hi, hi + widths[i]
             else:
-                yc = _layer_fwd(cat, p.weight.detach(), fold[0], fold[1], True)
+                lms.append(_layer_mode(1, cat, int(p.weight.shape[0])))
+                if lms[i] is None:
+                    yc = _layer_fwd(cat, p.weight.detach(), fold[0], fold[1], True)
+                else:
+                    yc = _layer_fwd(cat, p.weight.detach(), fold[0], fold[1], True, bf16=lms[i].bf16)
             saved += [p.weight, p.mean, fold]
         ctx.save_for_backward(cat, yc, *saved)
         ctx.Cin, ctx.widths = Cin, widths
@@ -359,9 +480,9 @@ class _OSAChain(torch.autograd.Function):
         Ctot = cat.shape[3]
         p = layers[L]
         gz, _, grads[L][1], grads[L][2] = _bn_relu_bwd(_nhwc(gy), yc, p.fold, p.mean, True, need[L].gamma, need[L].beta)
-        g_cat = _layer_dgrad(gz, p.weight.detach())
+        g_cat = _layer_dgrad(gz, p.weight.detach(), ctx.lms[L])
         if need[L].weight:
-            grads[L][0] = _weight_grad(gz, cat, p.weight, 1)
+            grads[L][0] = _weight_grad_in(ctx.lms[L], gz, cat, p.weight, 1)
         del gz
         # the chain, last layer first
         carry = None
@@ -373,8 +494,8 @@ class _OSAChain(torch.autograd.Function):
             gz, _, grads[i][1], grads[i][2] = _bn_relu_bwd(g_cat[..., out_lo:out_hi], cat[..., out_lo:out_hi], p.fold, p.mean, True,
                                                            need[i].gamma, need[i].beta, gy2=carry)
             if need[i].weight:
-                grads[i][0] = _weight_grad(gz, cat[..., in_lo:in_hi], p.weight, 3)
-            carry = _layer_dgrad(gz, p.weight.detach()) if (i > 0 or need_x) else None
+                grads[i][0] = _weight_grad_in(ctx.lms[i], gz, cat[..., in_lo:in_hi], p.weight, 3)
+            carry = _layer_dgrad(gz, p.weight.detach(), ctx.lms[i]) if (i > 0 or need_x) else None
             out_hi = out_lo
         gx = carry.add_(g_cat[..., :Cin]).permute(0, 3, 1, 2) if need_x else None
         return (gx, None, *[g for rec in grads for g in rec])
@@ -525,7 +646,12 @@ class _Conv1x1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        yn = _layer_fwd(_nhwc(x), weight.detach(), None, None if bias is None else bias.detach(), False)
+        xn = _nhwc(x)
+        ctx.lm = lm = _layer_mode(1, xn, weight.shape[0])
+        if lm is None:
+            yn = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False)
+        else:
+            yn = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False, bf16=lm.bf16)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return yn.permute(0, 3, 1, 2)
@@ -536,9 +662,9 @@ class _Conv1x1(torch.autograd.Function):
         gn = _nhwc(gy)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = _layer_dgrad(gn, weight.detach()).permute(0, 3, 1, 2)
+            gx = _layer_dgrad(gn, weight.detach(), ctx.lm).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
-            gw = _weight_grad(gn, _nhwc(x), weight, 1)
+            gw = _weight_grad_in(ctx.lm, gn, _nhwc(x), weight, 1)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gn.sum(dim=(0, 1, 2))
         return gx, gw, gb

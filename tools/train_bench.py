@@ -42,6 +42,8 @@ def main():
     ap.add_argument("--kernel-table", default=None, metavar="FILE",
                     help="after the timed iterations, trace 2 more with torch.profiler and write the per-kernel table of the steady "
                          "state to FILE (markdown); rank 0 only")
+    ap.add_argument("--train-mfma-dtype", default=None, choices=["bf16"],
+                    help="SRFDet.train_mfma_dtype: the image backbone + neck train on one bf16 product per f32 product (default: f32)")
     a = ap.parse_args()
     rank, local, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(local)
@@ -54,6 +56,8 @@ def main():
     model = workloads.build("srfdet_voxel_nusc_LC", a.np, train=True)
     training.freeze_lidar_components(model)
     model = model.to(dev).train()
+    if a.train_mfma_dtype:
+        model.train_mfma_dtype = torch.bfloat16
     net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local], find_unused_parameters=True) if world > 1 else model
     # gradient all-reduce time (collective C1): a DDP communication hook that brackets every bucket's all-reduce with
     # events on the stream it runs on; the buckets overlap with the rest of backward, so this is time ON the communication stream, not
@@ -139,7 +143,7 @@ def main():
         comm_bytes = sum(n for _, _, n in comm_events) / a.iters if comm_events else 0
         print(json.dumps(dict(metric="training iterations/s, srfdet_voxel_nusc_LC", value=round(a.iters / dt, 3), n_gpus=world,
                               frames_per_s=round(a.iters * a.bs * world / dt, 3), bs_per_gpu=a.bs, num_proposals=a.np,
-                              image=f"{h}x{w}", trainable_params=ntrain, grad_bytes_per_step=4 * ntrain, last_loss=round(loss, 4),
+                              image=f"{h}x{w}", train_mfma_dtype=a.train_mfma_dtype, trainable_params=ntrain, grad_bytes_per_step=4 * ntrain, last_loss=round(loss, 4),
                               ms_per_step=round(step_ms, 2),
                               phases_ms=dict(forward_and_loss=round(fwd, 2), backward_incl_overlapped_allreduce=round(bwd, 2),
                                              clip_and_optimizer=round(optm, 2)),
