@@ -36,7 +36,7 @@ from collections import OrderedDict, namedtuple
 import torch
 from torch import nn
 
-from . import derived, ops
+from . import derived, mfma_mode, ops
 from .dense import _foldable, fusable
 
 _SWITCHES = {"IMG_NHWC": "1", "WINO43": "1", "FPN_FORK": "2"}   # this file's switches, SRF_<name> in the environment, read at every call: name -> default
@@ -91,10 +91,7 @@ def invalidate_caches(model):
 
 
 # ---- the bf16-product mode of the image branch (csrc/gemm_bf16.hip) ------------------------------------------------------------
-_MFMA = None     # the innermost active `mfma_dtype` context, or None: every layer on its f32 route
-
-
-class mfma_dtype:
+class mfma_dtype(mfma_mode.MfmaMode):
     """Within `with nhwc.mfma_dtype(torch.bfloat16):` the layers executed by `conv3x3`, `conv1x1` (plain, pool=, top=) and
     `conv_strided` -- so `vovnet_forward` and `fpn_forward` -- run on the bf16-product kernels: f32 tensors, both operands rounded to
     bf16 once, exact products, f32 accumulation and epilogue (`srf_conv1x1_nhwc_bf16*`; `srf_conv_gemm_nhwc_bf16` for every 3x3 layer,
@@ -110,44 +107,19 @@ class mfma_dtype:
     process-wide while the context is open (the executor is single-threaded); it is not an environment variable and nothing outside
     the context sees it."""
 
-    def __init__(self, dtype, routes=None):
-        if dtype is not None and dtype != torch.bfloat16:
-            raise ValueError(f"nhwc.mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
-        self.dtype, self.routes, self.launches = dtype, routes, 0
-
-    def __enter__(self):
-        global _MFMA
-        self._outer, _MFMA = _MFMA, (self if self.dtype is not None else None)
-        return self
-
-    def __exit__(self, *exc):
-        global _MFMA
-        _MFMA = self._outer
-        return False
-
 
 def mfma_active():
-    return _MFMA is not None
+    return mfma_dtype.active() is not None
 
 
 def _bf16_route(x, conv, out, form):
     """True when the active mode takes this layer; records the route.  form: "1x1" or "conv"."""
-    m = _MFMA
+    m = mfma_dtype.active()
     if m is None:
         return False
     N, H, W, cin = x.shape
-    try:
-        x_ld, y_ld = ops.nhwc_ld(x), (ops.nhwc_ld(out) if out is not None else conv.out_channels)
-        why = ("input channels are no multiple of 32" if not ops.gemm_k_ok(cin) else "operand alignment" if not ops.operand_ok(x_ld, x.data_ptr())
-               else "beyond the 32-bit ranges" if not ops.gemm_rows_ok(max(x_ld, y_ld)) or (form == "conv" and not ops.below_2gb(H * W, x_ld))
-               else None)
-    except RuntimeError:
-        why = "not a channel slice of a pixel-major buffer"
-    if m.routes is not None:
-        k, st = conv.kernel_size[0], conv.stride[0]
-        m.routes.append(dict(layer=f"{cin}->{conv.out_channels} {k}x{k}/s{st} @{N}x{H}x{W}", route="f32" if why else "bf16", why=why))
-    m.launches += why is None
-    return why is None
+    k, st = conv.kernel_size[0], conv.stride[0]
+    return m.report(f"{cin}->{conv.out_channels} {k}x{k}/s{st} @{N}x{H}x{W}", ops.gemm_bf16_why_not(x, conv.out_channels, out, im2col=form == "conv"))
 
 
 def _is_conv(conv, k, stride=1):

@@ -1594,6 +1594,25 @@ def below_2gb(pixels, ld):
     return 4 * pixels * ld < (1 << 31)
 
 
+def gemm_bf16_why_not(x, Cout, out=None, im2col=False, dgrad=False):
+    """None when the bf16 family takes the layer x (N, H, W, Cin) -> Cout channels [written into the channel slice `out`], else the
+    reason it keeps its f32 route.  im2col: `srf_conv_gemm_nhwc_bf16`, which also holds one image of x to 2 GB, not the 1x1 GEMM.
+    dgrad (the training nodes): the layer's data gradient is asked too -- the same kernel with K = Cout over a dense tensor of Cout
+    channels -- and `out`'s alignment, for a layer that keeps both directions on one route."""
+    N, H, W, Cin = x.shape
+    try:
+        x_ld, y_ld = nhwc_ld(x), (nhwc_ld(out) if out is not None else Cout)
+    except RuntimeError:
+        return "not a channel slice of a pixel-major buffer"
+    if not (gemm_k_ok(Cin) and (not dgrad or gemm_k_ok(Cout))):
+        return "input or output channels are no multiple of 32" if dgrad else "input channels are no multiple of 32"
+    if not (operand_ok(x_ld, x.data_ptr()) and (not dgrad or out is None or operand_ok(y_ld, out.data_ptr()))):
+        return "operand alignment"
+    if not gemm_rows_ok(max(x_ld, y_ld)) or (im2col and not below_2gb(H * W, max(x_ld, Cout) if dgrad else x_ld)) or (dgrad and N == 0):
+        return "beyond the 32-bit ranges"
+    return None
+
+
 def _pack_gemm(kind, weight):
     k = _GEMM_KINDS[kind]
     weight = _dev(weight.reshape(weight.shape[0], -1), "weight", torch.float32)

@@ -1,8 +1,6 @@
 """`SRFDet` / `SRFDetWaymo` detectors (mmdet3d_plugin/models/detectors/srfdet.py:13-343, srfdetwaymo.py:6-41):
 voxelize -> voxel encoder -> sparse middle encoder -> SECOND -> FPN -> SRFDetHead.  Same registry names,
 constructor arguments, sub-module attribute names and forward signatures as the reference."""
-import contextlib
-
 import torch
 import torch.nn.functional as F
 
@@ -62,6 +60,25 @@ class SRFDet(BaseModule):
         self._train_mfma_dtype = None
         self.train_mfma_routes = None     # a list here receives `train_conv.mfma_dtype`'s per-direction report of every recording pass
 
+    # ---- the three bf16-product switches: what they share is in the two helpers, what differs stands at the property --------------
+    def _not_with_autocast(self, name, how=""):
+        if self.img_autocast_dtype is not None:
+            raise ValueError(f"{name} and img_autocast_dtype exclude each other{how}")
+
+    def _mfma_arg(self, name, dtype, autocast=True):
+        """A value for the switch `name`: torch.bfloat16 or None, and (autocast) not next to `img_autocast_dtype`."""
+        if dtype is not None:
+            if dtype != torch.bfloat16:
+                raise ValueError(f"{name}: only torch.bfloat16 (or None) is implemented, not {dtype}")
+            if autocast:
+                self._not_with_autocast(name, ": set img_autocast_dtype = None first")
+
+    def _mfma_store(self, owner, attr, dtype):
+        """Changed, so `_drop_derived_state()`: the packed weights and the graphs belong to the route they were built on."""
+        if dtype != getattr(owner, attr):
+            setattr(owner, attr, dtype)
+            self._drop_derived_state()
+
     @property
     def train_mfma_dtype(self):
         """None (default: f32) or torch.bfloat16: while autograd is recording, the image backbone + neck run inside
@@ -73,12 +90,8 @@ class SRFDet(BaseModule):
 
     @train_mfma_dtype.setter
     def train_mfma_dtype(self, dtype):
-        if dtype is not None:
-            if dtype != torch.bfloat16:
-                raise ValueError(f"train_mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
-            if self.img_autocast_dtype is not None:
-                raise ValueError("train_mfma_dtype and img_autocast_dtype exclude each other: set img_autocast_dtype = None first")
-        self._train_mfma_dtype = dtype
+        self._mfma_arg("train_mfma_dtype", dtype)
+        self._train_mfma_dtype = dtype      # nothing derived depends on it: the training nodes pack their weights at every call
 
     @property
     def img_mfma_dtype(self):
@@ -91,18 +104,13 @@ class SRFDet(BaseModule):
 
     @img_mfma_dtype.setter
     def img_mfma_dtype(self, dtype):
+        self._mfma_arg("img_mfma_dtype", dtype)
         if dtype is not None:
-            if dtype != torch.bfloat16:
-                raise ValueError(f"img_mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
-            if self.img_autocast_dtype is not None:
-                raise ValueError("img_mfma_dtype and img_autocast_dtype exclude each other: set img_autocast_dtype = None first")
             from .vovnet import VoVNet
             if not isinstance(getattr(self, "img_backbone", None), VoVNet):
                 raise NotImplementedError("img_mfma_dtype needs an image backbone on the channels-last executor (VoVNet); "
                                           f"{type(getattr(self, 'img_backbone', None)).__name__} runs through torch")
-        if dtype != self._img_mfma_dtype:
-            self._img_mfma_dtype = dtype
-            self._drop_derived_state()
+        self._mfma_store(self, "_img_mfma_dtype", dtype)
 
     @property
     def sparse_mfma_dtype(self):
@@ -117,16 +125,13 @@ class SRFDet(BaseModule):
 
     @sparse_mfma_dtype.setter
     def sparse_mfma_dtype(self, dtype):
-        if dtype is not None and dtype != torch.bfloat16:
-            raise ValueError(f"sparse_mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
+        self._mfma_arg("sparse_mfma_dtype", dtype, autocast=False)     # (autocast covers the image branch alone)
         enc = getattr(self, "pts_middle_encoder", None)
         if not hasattr(enc, "mfma_dtype"):
             if dtype is None:
                 return
             raise NotImplementedError(f"sparse_mfma_dtype needs a sparse-convolution middle encoder, not {type(enc).__name__}")
-        if dtype != enc.mfma_dtype:
-            enc.mfma_dtype = dtype
-            self._drop_derived_state()
+        self._mfma_store(enc, "mfma_dtype", dtype)
 
     def enable_hip_graphs(self, enabled=True, img_overlap=False, whole_frame=True):
         """Replay the static-shape tail (SECOND -> FPN -> decoder -> decode) as a captured hipGraph in `simple_test`
@@ -277,29 +282,26 @@ class SRFDet(BaseModule):
             img = img.reshape(-1, *img.shape[2:])
         if self.use_grid_mask and self.training:
             img = self.grid_mask(img)
+        train_mode = self._train_mfma_dtype if torch.is_grad_enabled() else None     # no-grad passes ignore the switch
+        # `img_autocast_dtype` is a plain attribute and can be set after either switch: asked again here, where it would take effect
         if self._img_mfma_dtype is not None:
-            if self.img_autocast_dtype is not None:
-                raise ValueError("img_mfma_dtype and img_autocast_dtype exclude each other")
+            self._not_with_autocast("img_mfma_dtype")
             if torch.is_grad_enabled() or self.training:
                 # training in the mode is not implemented: no quiet f32 pass through the modules instead
                 raise RuntimeError("img_mfma_dtype covers inference under no_grad in eval mode only (the channels-last executor)")
-        train_mode = self._train_mfma_dtype if torch.is_grad_enabled() else None     # no-grad passes ignore the switch
-        if train_mode is not None and self.img_autocast_dtype is not None:
-            raise ValueError("train_mfma_dtype and img_autocast_dtype exclude each other")
+        if train_mode is not None:
+            self._not_with_autocast("train_mfma_dtype")
         with torch.autocast(img.device.type, dtype=self.img_autocast_dtype, enabled=self.img_autocast_dtype is not None), \
-                nhwc.mfma_dtype(self._img_mfma_dtype) as mode, \
-                (train_conv.mfma_dtype(train_mode, routes=self.train_mfma_routes) if train_mode is not None else contextlib.nullcontext()) as tmode:
+                nhwc.mfma_dtype(self._img_mfma_dtype) as mode, train_conv.mfma_dtype(train_mode, routes=self.train_mfma_routes) as tmode:
             feats = self.img_backbone(img)
             if isinstance(feats, dict):
                 feats = list(feats.values())
             if self.img_neck is not None:
                 feats = self.img_neck(feats)
-        if self._img_mfma_dtype is not None and mode.launches == 0:
-            # a missing kernel route is an error, never a quiet f32 pass (training, autograd or a CPU tensor leave the executor)
-            raise RuntimeError("img_mfma_dtype is set but the image branch did not run on the channels-last executor "
-                               "(it covers fp32 GPU inference under no_grad with BatchNorm in eval mode)")
-        if train_mode is not None and tmode.launches == 0:
-            raise RuntimeError("train_mfma_dtype is set but no layer of the image backbone + neck took a bf16 route under autograd "
+        # a missing kernel route is an error, never a quiet f32 pass (training, autograd or a CPU tensor leave the executor)
+        mode.require_launches("img_mfma_dtype is set but the image branch did not run on the channels-last executor "
+                              "(it covers fp32 GPU inference under no_grad with BatchNorm in eval mode)")
+        tmode.require_launches("train_mfma_dtype is set but no layer of the image backbone + neck took a bf16 route under autograd "
                                "(it covers the training nodes of train_conv.py on fp32 channels-last GPU tensors)")
         out = [f.float().view(B, f.shape[0] // B, *f.shape[1:]) for f in feats]
         return nhwc.ConsumedLevels(out) if isinstance(feats, nhwc.ConsumedLevels) else out
@@ -384,15 +386,6 @@ class SRFDet(BaseModule):
 @DETECTORS.register_module()
 class SRFDetWaymo(SRFDet):
     """Same model; results are returned without the `pts_bbox` wrapper (srfdetwaymo.py:13-41)."""
-
-    def _finish(self, scores, boxes, sel, img_metas):
-        """Detections from a graph replay: the NMS ran inside the graph with fixed shapes (`select_static`); one copy brings
-        the survivors to the host.  Falls back to the eager selection if a sample overflowed the static capacity."""
-        if sel is not None:
-            res = self.bbox_head.results_from_static(sel[0].cpu(), sel[1].cpu(), img_metas)
-            if res is not None:
-                return res
-        return self.bbox_head.get_bboxes(None, None, img_metas, decoded=(scores, boxes))
 
     def simple_test(self, img, points, img_metas, rescale=False):
         return [bbox3d2result(b, s, l) for b, s, l in self._test_bboxes(img, points, img_metas)]

@@ -98,9 +98,8 @@ class SparseEncoderCustom(BaseModule):
             x = SparseConvTensor(voxel_features, coors, self.sparse_shape, int(batch_size))
         with sparse.mfma_dtype(self.mfma_dtype, routes=self.mfma_routes) as mode:
             bev = self._layers(x).dense_bev()
-        if self.mfma_dtype is not None and mode.launches == 0:
-            raise RuntimeError("the sparse encoder's mfma_dtype is set but none of its layers has a bf16-product form "
-                               "(the 64- and 128-output-channel shapes of srf_spconv_fwd_bf16): no quiet f32 pass")
+        mode.require_launches("the sparse encoder's mfma_dtype is set but none of its layers has a bf16-product form "
+                              "(the 64- and 128-output-channel shapes of srf_spconv_fwd_bf16): no quiet f32 pass")
         return bev, x.level
 
     def _modules_in_order(self):

@@ -19,7 +19,7 @@ import math
 import torch
 from torch import nn
 
-from . import derived, ops
+from . import derived, mfma_mode, ops
 from .compat.cnn import build_norm_layer
 from .compat.registry import CONV_LAYERS
 
@@ -32,10 +32,7 @@ def _triple(v):
 
 
 # ---- the bf16-product mode of the sparse encoder (csrc/spconv_bf16.hip) --------------------------------------------------------
-_MFMA = None     # the innermost active `mfma_dtype` context, or None: every layer on its f32 route
-
-
-class mfma_dtype:
+class mfma_dtype(mfma_mode.MfmaMode):
     """Within `with sparse.mfma_dtype(torch.bfloat16):` a `_SparseConv` of one of the five 64- / 128-output-channel shapes of
     `srf_spconv_fwd_bf16` (include/srfdet3d.h) runs on the bf16-product kernel: f32 tensors, inputs and weights rounded to bf16 once,
     exact products, f32 accumulation and the f32 epilogue (BatchNorm fold, residual, ReLU) -- defined by tests/spconv_bf16_ref.py.
@@ -46,24 +43,9 @@ class mfma_dtype:
     routes: a list that receives one dict(layer=, route="bf16" | "f32", why=) per executed layer.  `launches` counts the layers that
     ran on the bf16 kernel.  Process-wide while the context is open, as `nhwc.mfma_dtype`; nothing outside the context sees it."""
 
-    def __init__(self, dtype, routes=None):
-        if dtype is not None and dtype != torch.bfloat16:
-            raise ValueError(f"sparse.mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
-        self.dtype, self.routes, self.launches = dtype, routes, 0
-
-    def __enter__(self):
-        global _MFMA
-        self._outer, _MFMA = _MFMA, (self if self.dtype is not None else None)
-        return self
-
-    def __exit__(self, *exc):
-        global _MFMA
-        _MFMA = self._outer
-        return False
-
 
 def mfma_active():
-    return _MFMA is not None
+    return mfma_dtype.active() is not None
 
 
 class Rulebook:
@@ -231,7 +213,7 @@ class _SparseConv(SparseModule):
 
     def _bf16_why_not(self):
         """None when the active bf16-product mode takes this layer, else why it keeps its f32 route ("" outside the mode)."""
-        if _MFMA is None:
+        if mfma_dtype.active() is None:
             return ""
         if self.training or torch.is_grad_enabled():
             return "training mode or gradients enabled"
@@ -248,13 +230,9 @@ class _SparseConv(SparseModule):
                 beta = beta + self.bias * alpha
         elif self.bias is not None:
             alpha, beta = torch.ones_like(self.bias), self.bias
-        why = self._bf16_why_not()
-        if _MFMA is not None:
-            if _MFMA.routes is not None:
-                _MFMA.routes.append(dict(layer=f"{self.in_channels}->{self.out_channels} k{rb.nbr.shape[0]} "
-                                               f"{'subm' if self.subm else 'strided'} @{rb.nbr.shape[1]}",
-                                         route="f32" if why else "bf16", why=why))
-            _MFMA.launches += why is None
+        why, mode = self._bf16_why_not(), mfma_dtype.active()
+        if mode is not None:
+            mode.report(f"{self.in_channels}->{self.out_channels} k{rb.nbr.shape[0]} {'subm' if self.subm else 'strided'} @{rb.nbr.shape[1]}", why)
         if why is None:   # (an input of 2 GiB or more falls back to srf_spconv_fwd inside ops.spconv_fwd_bf16)
             packed_bf16 = derived.get(self, "spconv_bf16", (self.weight,), lambda: ops.pack_spconv_bf16_weights(w.detach()))
             feats = ops.spconv_fwd_bf16(x.features, w, rb.nbr, packed_bf16, alpha, beta, residual, relu, pair_counts=rb.counts,

@@ -23,7 +23,7 @@ from collections import namedtuple
 import torch
 from torch import nn
 
-from . import derived, ops
+from . import derived, mfma_mode, ops
 
 # The SRF_TRAIN_* switches: A/B switches for tests and benchmarks, "1" when unset, read on every call (tests flip them mid-process).
 _SWITCHES = {
@@ -110,10 +110,7 @@ def fused_layer_ok(k, N, H, W, Cin, Cout):
 
 
 # ---- the bf16-product mode (csrc/gemm_bf16.hip forward and data gradient, csrc/wgrad_bf16.hip weight gradient) ---------------------
-_MFMA = None     # the innermost active `mfma_dtype` context, or None: every node on its f32 routes
-
-
-class mfma_dtype:
+class mfma_dtype(mfma_mode.MfmaMode):
     """Within `with train_conv.mfma_dtype(torch.bfloat16):` the convolutions of `_Wino43Conv`, `_ConvAffineRelu`, `_OSAChain` and `_Conv1x1`
     run on ONE bf16 product per f32 product in all three directions: f32 tensors, both operands rounded to bf16 once, exact products, f32
     accumulation -- forward on `srf_conv_gemm_nhwc_bf16` (3x3; no Winograd in this mode) / `srf_conv1x1_nhwc_bf16`, the data gradient on
@@ -126,21 +123,6 @@ class mfma_dtype:
     both; a weight gradient the new kernel refuses goes through `_weight_grad`.
     routes: a list that receives one dict(layer=, direction="fwd" | "dgrad" | "wgrad", route="bf16" | "f32", why=) per executed
     direction; `launches` counts the directions that ran on the bf16 kernels.  Process-wide while open, as `nhwc.mfma_dtype`."""
-
-    def __init__(self, dtype, routes=None):
-        if dtype is not None and dtype != torch.bfloat16:
-            raise ValueError(f"train_conv.mfma_dtype: only torch.bfloat16 (or None) is implemented, not {dtype}")
-        self.dtype, self.routes, self.launches = dtype, routes, 0
-
-    def __enter__(self):
-        global _MFMA
-        self._outer, _MFMA = _MFMA, (self if self.dtype is not None else None)
-        return self
-
-    def __exit__(self, *exc):
-        global _MFMA
-        _MFMA = self._outer
-        return False
 
 
 def bf16_layer_ok(k, N, H, W, Cin, Cout):
@@ -163,28 +145,27 @@ class _LayerMode:
         return self.why is None
 
     def report(self, direction, why=False):
-        why = self.why if why is False else why
-        route = "f32" if why else "bf16"
-        if self.mode.routes is not None:
-            self.mode.routes.append(dict(layer=self.layer, direction=direction, route=route, why=why))
-        self.mode.launches += route == "bf16"
+        self.mode.report(self.layer, self.why if why is False else why, direction=direction)
+
+
+class _NoMode:
+    """What it keeps of a forward pass outside the mode: every direction on its f32 route, nothing to report."""
+    bf16 = False
+
+    def report(self, direction, why=False):
+        pass
+
+
+_F32 = _NoMode()
 
 
 def _layer_mode(k, xn, Cout, out=None):
-    """At a layer's forward pass: None outside the mode, else its record (and the report's "fwd" row)."""
-    m = _MFMA
+    """At a layer's forward pass: `_F32` outside the mode, else its record (and the report's "fwd" row)."""
+    m = mfma_dtype.active()
     if m is None:
-        return None
+        return _F32
     N, H, W, Cin = xn.shape
-    x_ld, y_ld = ops.nhwc_ld(xn), (ops.nhwc_ld(out) if out is not None else Cout)
-    why = None
-    if not (ops.gemm_k_ok(Cin) and ops.gemm_k_ok(Cout)):
-        why = "input or output channels are no multiple of 32"
-    elif not (ops.operand_ok(x_ld, xn.data_ptr()) and (out is None or ops.operand_ok(y_ld, out.data_ptr()))):
-        why = "operand alignment"
-    elif not (bf16_layer_ok(k, N, H, W, Cin, Cout) and ops.gemm_rows_ok(max(x_ld, y_ld)) and (k == 1 or ops.below_2gb(H * W, x_ld))):
-        why = "beyond the 32-bit ranges"
-    lm = _LayerMode(m, f"{Cin}->{Cout} {k}x{k} @{N}x{H}x{W}", why)
+    lm = _LayerMode(m, f"{Cin}->{Cout} {k}x{k} @{N}x{H}x{W}", ops.gemm_bf16_why_not(xn, Cout, out, im2col=k == 3, dgrad=True))
     lm.report("fwd")
     return lm
 
@@ -192,12 +173,11 @@ def _layer_mode(k, xn, Cout, out=None):
 def _weight_grad_in(lm, gn, xn, weight, k):
     """The weight gradient of a node whose forward pass recorded lm: outside the mode `_weight_grad` as ever; in it `srf_conv_wgrad_nhwc_bf16`
     (whatever route the layer's other two directions took), unless the kernel refuses the operands."""
-    if lm is None:
-        return _weight_grad(gn, xn, weight, k)
-    if ops.conv_wgrad_bf16_supported(gn, xn, k):
-        lm.report("wgrad", None)
-        return ops.conv_wgrad_nhwc_bf16(gn, xn, k)
-    lm.report("wgrad", "channel counts or pitches that are no multiple of 4, alignment, or a tensor of 2 GB")
+    if lm is not _F32:
+        if ops.conv_wgrad_bf16_supported(gn, xn, k):
+            lm.report("wgrad", None)
+            return ops.conv_wgrad_nhwc_bf16(gn, xn, k)
+        lm.report("wgrad", "channel counts or pitches that are no multiple of 4, alignment, or a tensor of 2 GB")
     return _weight_grad(gn, xn, weight, k)
 
 
@@ -222,15 +202,13 @@ def _layer_fwd(xn, w, scale=None, shift=None, relu=False, out=None, bf16=False):
                             packed_split=lambda: ops.pack_conv1x1_nhwc_split_weights(w2))
 
 
-def _layer_dgrad(gn, w, lm=None):
+def _layer_dgrad(gn, w, lm=_F32):
     """Its data gradient: the same kernels on the weight rotated by 180 degrees with the channel axes swapped (3x3), transposed (1x1).
     lm: what the node recorded of the mode in its forward pass (rounding commutes with the rotation and the transposition: bf16(W) again)."""
     if w.shape[2] == 3:
         wt = w.flip(2, 3).transpose(0, 1).contiguous()      # (Cin, Cout, 3, 3)
     else:
         wt = w.reshape(w.shape[0], w.shape[1]).t().contiguous()  # (Cin, Cout)
-    if lm is None:
-        return _layer_fwd(gn, wt)
     lm.report("dgrad")
     if lm.bf16 and not ops.operand_ok(ops.nhwc_ld(gn), gn.data_ptr()):
         gn = gn.contiguous()
@@ -285,10 +263,7 @@ class _Wino43Conv(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         xn = _nhwc(x)
         ctx.lm = lm = _layer_mode(3, xn, weight.shape[0])
-        if lm is None:
-            y = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False)
-        else:
-            y = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False, bf16=lm.bf16)
+        y = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False, bf16=lm.bf16)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.keep_cl = x.stride(1) == 1
@@ -334,7 +309,7 @@ class _ConvAffineRelu(torch.autograd.Function):
         s, t0 = fold[0], fold[1]
         t = t0 if bias is None else t0 + bias.detach() * s
         ctx.lm = lm = _layer_mode(weight.shape[2], xn, weight.shape[0])
-        yn = _layer_fwd(xn, weight.detach(), s, t, relu) if lm is None else _layer_fwd(xn, weight.detach(), s, t, relu, bf16=lm.bf16)
+        yn = _layer_fwd(xn, weight.detach(), s, t, relu, bf16=lm.bf16)
         ctx.save_for_backward(x, weight, yn, fold, mean)
         ctx.relu, ctx.has_bias = bool(relu), bias is not None
         return yn.permute(0, 3, 1, 2)          # logical NCHW, channels-last strides
@@ -443,24 +418,18 @@ class _OSAChain(torch.autograd.Function):
         cat = torch.empty((N, H, W, Ctot), dtype=torch.float32, device=x.device)
         cat[..., :Cin].copy_(xn)
         saved = []
-        ctx.lms = lms = []         # per layer: what it recorded of the `mfma_dtype` mode (None outside it)
+        ctx.lms = lms = []         # per layer: what it recorded of the `mfma_dtype` mode
         lo, hi = 0, Cin            # the input slice of the next layer
         for i, p in enumerate(layers):
             fold = ops.bn_eval_fold(p.gamma.detach(), p.beta.detach(), p.mean, p.var, eps[i])
             if i < L:
                 xs, ys = cat[..., lo:hi], cat[..., hi:hi + widths[i]]
                 lms.append(_layer_mode(3, xs, widths[i], ys))
-                if lms[i] is None:
-                    _layer_fwd(cat[..., lo:hi], p.weight.detach(), fold[0], fold[1], True, out=cat[..., hi:hi + widths[i]])
-                else:
-                    _layer_fwd(xs, p.weight.detach(), fold[0], fold[1], True, out=ys, bf16=lms[i].bf16)
+                _layer_fwd(xs, p.weight.detach(), fold[0], fold[1], True, out=ys, bf16=lms[i].bf16)
                 lo, hi = hi, hi + widths[i]
             else:
                 lms.append(_layer_mode(1, cat, int(p.weight.shape[0])))
-                if lms[i] is None:
-                    yc = _layer_fwd(cat, p.weight.detach(), fold[0], fold[1], True)
-                else:
-                    yc = _layer_fwd(cat, p.weight.detach(), fold[0], fold[1], True, bf16=lms[i].bf16)
+                yc = _layer_fwd(cat, p.weight.detach(), fold[0], fold[1], True, bf16=lms[i].bf16)
             saved += [p.weight, p.mean, fold]
         ctx.save_for_backward(cat, yc, *saved)
         ctx.Cin, ctx.widths = Cin, widths
@@ -648,10 +617,7 @@ class _Conv1x1(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         xn = _nhwc(x)
         ctx.lm = lm = _layer_mode(1, xn, weight.shape[0])
-        if lm is None:
-            yn = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False)
-        else:
-            yn = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False, bf16=lm.bf16)
+        yn = _layer_fwd(xn, weight.detach(), None, None if bias is None else bias.detach(), False, bf16=lm.bf16)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return yn.permute(0, 3, 1, 2)

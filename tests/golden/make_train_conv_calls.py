@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Generate tests/golden/train_conv_calls.json: the sequence of `ops` calls each autograd node of srfdet3d_amd/train_conv.py makes,
-forward and backward, at one tiny shape (N = 1, H = 4, W = 32, 32 channels) on CPU tensors.  The `ops` functions the nodes use are
+forward and backward, at one tiny shape (N = 1, H = 4, W = 32, 32 channels) on CPU tensors -- each convolution node a second time as
+`<case>/bf16`: forward inside `train_conv.mfma_dtype(torch.bfloat16, routes=[...])`, backward after the context has closed, the route
+list as a last `-- routes --` record.  The `ops` functions the nodes use are
 replaced by stand-ins that record their arguments and return tensors of the right shape: per call the op's name and, for every
 parameter of the real function's signature (defaults filled in, so positional and keyword spellings are one), a tensor's shape and
-strides, a scalar's value, "callable" for a lazily packed weight, null for None.  tests/test_train_conv_calls.py runs the same
+strides, a scalar's value, "callable" for a lazily packed weight, null for None.  `ops.nhwc_ld` tests `is_cuda`; it is stood in for,
+unrecorded, by `make_nhwc_calls._ld`.  tests/test_train_conv_calls.py runs the same
 recorder on the tree under test and compares: same kernels, same order, same arguments -- with unchanged kernels, unchanged bits.
 
-The committed file was written from the commit BEFORE the nodes were rewritten over one layer primitive, from a checkout of it made by
+The committed file was written from the commit BEFORE the nodes were rewritten over one layer primitive, its `/bf16` cases from the
+commit BEFORE the three bf16-product modes were put on one context class, each from a checkout of it made by
 hand (this script runs no git command):
 
 usage:  python tests/golden/make_train_conv_calls.py [--tree CHECKOUT]      (default: the tree this file lies in)
@@ -19,6 +23,8 @@ import os
 import sys
 
 import torch
+
+from make_nhwc_calls import _conv_gemm_nhwc, _ld
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -58,6 +64,11 @@ def _conv1x1_nhwc(x, packed_weight, Cout, scale=None, shift=None, relu=False, ou
 STANDINS = {
     "wino43": lambda x, packed_weight, Cout, scale=None, shift=None, relu=False, out=None: _conv_out(x, Cout, out),
     "conv1x1_nhwc": _conv1x1_nhwc,
+    "conv_gemm_nhwc": _conv_gemm_nhwc,
+    "pack_conv_gemm_bf16_weights": lambda weight: _zeros(1),
+    "pack_conv1x1_nhwc_bf16_weights": lambda weight: _zeros(1),
+    "conv_wgrad_nhwc_bf16": lambda g, x, ksize: _zeros(g.shape[3], x.shape[3], ksize, ksize),
+    "conv_wgrad_bf16_supported": lambda g, x, ksize: True,
     "pack_wino43_weights": lambda weight: _zeros(1),
     "pack_conv1x1_nhwc_weights": lambda weight: _zeros(1),
     "pack_conv1x1_nhwc_split_weights": lambda weight: _zeros(1),
@@ -75,7 +86,7 @@ STANDINS = {
 
 @contextlib.contextmanager
 def recording(ops, calls):
-    real = {name: getattr(ops, name) for name in STANDINS}
+    real = {name: getattr(ops, name) for name in (*STANDINS, "nhwc_ld")}
 
     def standin(name):
         sig = inspect.signature(real[name])
@@ -89,6 +100,7 @@ def recording(ops, calls):
     try:
         for name in STANDINS:
             setattr(ops, name, standin(name))
+        ops.nhwc_ld = _ld            # silent: not an `ops` call of the record
         yield
     finally:
         for name, fn in real.items():
@@ -124,16 +136,23 @@ def _cases(tc):
     }
 
 
+BF16 = "/bf16"   # the suffix of a case run inside the bf16-product mode: every case but `_ESEApply`, which has no convolution
+
+
 def record(tc, ops):
     """{case: [call records]} of srfdet3d_amd.train_conv module `tc` over the `ops` module it uses."""
     out = {}
-    for name, run in _cases(tc).items():
+    cases = _cases(tc)
+    for name, run in [*cases.items(), *((n + BF16, r) for n, r in cases.items() if n != "_ESEApply")]:
         torch.manual_seed(0)
-        calls = []
+        calls, routes = [], ([] if name.endswith(BF16) else None)
         with recording(ops, calls):
-            y = run()
+            with tc.mfma_dtype(None if routes is None else torch.bfloat16, routes=routes):
+                y = run()
             calls.append(dict(op="-- backward --", args={}))
             y.backward(torch.randn_like(y))
+        if routes is not None:
+            calls.append(dict(op="-- routes --", args=routes))
         out[name] = calls
     return out
 

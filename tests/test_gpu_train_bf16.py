@@ -239,7 +239,7 @@ def test_backward_follows_the_mode_of_its_forward_and_a_closed_context_leaves_no
     after = _step(*layer)
     for a, b in zip(after, never):
         assert torch.equal(a, b)                                            # bit for bit the run that never opened it
-    assert train_conv._MFMA is None
+    assert train_conv.mfma_dtype.active() is None
 
 
 def test_routes_of_a_layer_the_bf16_gemms_refuse(dev):

@@ -1,4 +1,5 @@
-"""Argument checks of srf_conv_wgrad_nhwc_bf16 (csrc/wgrad_bf16.hip) and the mode's layer limits (train_conv.bf16_layer_ok); no GPU.
+"""Argument checks of srf_conv_wgrad_nhwc_bf16 (csrc/wgrad_bf16.hip), the mode's layer limits (train_conv.bf16_layer_ok,
+ops.gemm_bf16_why_not) and the context class the three bf16-product modes share (srfdet3d_amd/mfma_mode.py); no GPU.
 
 Every pointer is a fake address and every row of the return-code table is REFUSED, so no row ever launches a kernel: the codes are all
 decided before any HIP call, in the order of the other entry points (SRF_EINVAL, then SRF_EUNSUPPORTED, then SRF_EWORKSPACE)."""
@@ -84,13 +85,82 @@ def test_bf16_layer_ok(i):
 
 def test_the_context_takes_bf16_or_none_only():
     with train_conv.mfma_dtype(None) as m:
-        assert m.launches == 0 and train_conv._MFMA is None
+        assert m.launches == 0 and train_conv.mfma_dtype.active() is None
     with train_conv.mfma_dtype(torch.bfloat16) as m:
-        assert train_conv._MFMA is m
+        assert train_conv.mfma_dtype.active() is m
         with train_conv.mfma_dtype(None):
-            assert train_conv._MFMA is None
-        assert train_conv._MFMA is m
-    assert train_conv._MFMA is None
+            assert train_conv.mfma_dtype.active() is None
+        assert train_conv.mfma_dtype.active() is m
+    assert train_conv.mfma_dtype.active() is None
     for bad in (torch.float16, torch.float32, "bf16"):
         with pytest.raises(ValueError):
             train_conv.mfma_dtype(bad)
+
+
+def test_the_three_modes_share_one_base_and_stay_independent():
+    from srfdet3d_amd import mfma_mode, nhwc, sparse
+    kinds = (nhwc.mfma_dtype, sparse.mfma_dtype, train_conv.mfma_dtype)
+    assert all(issubclass(k, mfma_mode.MfmaMode) and k.active() is None for k in kinds)
+    for kind, name in zip(kinds, ("nhwc", "sparse", "train_conv")):
+        with pytest.raises(ValueError, match=f"^{name}.mfma_dtype: only torch.bfloat16"):
+            kind(torch.float16)
+    ri, rt = [], []
+    with nhwc.mfma_dtype(torch.bfloat16, routes=ri) as a:
+        assert (nhwc.mfma_dtype.active(), sparse.mfma_dtype.active(), train_conv.mfma_dtype.active()) == (a, None, None)
+        with sparse.mfma_dtype(torch.bfloat16) as b, train_conv.mfma_dtype(torch.bfloat16, routes=rt) as c:
+            assert (nhwc.mfma_dtype.active(), sparse.mfma_dtype.active(), train_conv.mfma_dtype.active()) == (a, b, c)
+            assert nhwc.mfma_active() and sparse.mfma_active()
+            with sparse.mfma_dtype(None) as off:                     # hides its own kind only
+                assert (nhwc.mfma_dtype.active(), sparse.mfma_dtype.active(), train_conv.mfma_dtype.active()) == (a, None, c)
+                assert not sparse.mfma_active()
+            assert sparse.mfma_dtype.active() is b
+            # the report: a falsy reason is the bf16 route and counts, any other is the f32 route with that reason
+            assert a.report("L0", None) is True and a.report("L1", "") is True and a.report("L2", "operand alignment") is False
+            assert c.report("L3", None, direction="fwd") is True and c.report("L3", "no", direction="dgrad") is False
+            b.report("L4", None)                                     # no list given: counted all the same
+            with pytest.raises(KeyError):
+                with train_conv.mfma_dtype(None):
+                    assert train_conv.mfma_dtype.active() is None
+                    raise KeyError("inside")
+            assert train_conv.mfma_dtype.active() is c               # ... the exit under an exception restored the outer one
+        assert (sparse.mfma_dtype.active(), train_conv.mfma_dtype.active()) == (None, None)
+    assert all(k.active() is None for k in kinds)
+    assert (a.launches, b.launches, c.launches, off.launches) == (2, 1, 1, 0)
+    assert ri == [dict(layer="L0", route="bf16", why=None), dict(layer="L1", route="bf16", why=""), dict(layer="L2", route="f32", why="operand alignment")]
+    assert rt == [dict(layer="L3", direction="fwd", route="bf16", why=None), dict(layer="L3", direction="dgrad", route="f32", why="no")]
+    assert [list(r) for r in ri + rt] == [["layer", "route", "why"]] * 3 + [["layer", "direction", "route", "why"]] * 2     # the key order
+    a.require_launches("unused")
+    for asked, what in ((nhwc.mfma_dtype(torch.bfloat16), RuntimeError), (nhwc.mfma_dtype(None), None)):
+        with asked:
+            pass
+        if what is None:
+            asked.require_launches("a mode that was not asked for requires nothing")
+        else:
+            with pytest.raises(what, match="nothing ran"):
+                asked.require_launches("nothing ran")
+
+
+class _Dense:
+    """What `ops.gemm_bf16_why_not` reads of a dense channels-last (N, H, W, C) f32 tensor at an aligned address, without its storage."""
+    dtype = torch.float32
+
+    def __init__(self, N, H, W, C):
+        self.shape = (N, H, W, C)
+
+    dim = lambda self: 4
+    data_ptr = lambda self: P
+
+    def stride(self, i):
+        N, H, W, C = self.shape
+        return (H * W * C, W * C, C, 1)[i]
+
+
+@pytest.mark.parametrize("i", [i for i, (args, _, _) in enumerate(LAYERS) if args[0] in (1, 3)])
+def test_gemm_bf16_why_not_agrees_with_bf16_layer_ok_on_dense_tensors(i, monkeypatch):
+    import make_nhwc_calls
+    from srfdet3d_amd import ops
+    (k, N, H, W, Cin, Cout), want, why = LAYERS[i]
+    monkeypatch.setattr(ops, "nhwc_ld", make_nhwc_calls._ld)        # (`ops.nhwc_ld` without its device test)
+    got = ops.gemm_bf16_why_not(_Dense(N, H, W, Cin), Cout, None, im2col=k == 3, dgrad=True)
+    assert (got is None) is want, (why, got)
+    assert got in (None, "input or output channels are no multiple of 32", "beyond the 32-bit ranges")
