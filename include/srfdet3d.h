@@ -940,6 +940,39 @@ int srf_decode_boxes(const float *logits, const float *pred, int R, int ncls, in
  * live row counts of the sparse levels c (nc ints) -> out (na + nb + nc floats; the integers are < 2^24, exact).  One launch. */
 int srf_host_pack(const float *a, int na, const int *b, int nb, const int *c, int nc, float *out, srf_stream_t stream);
 int srf_box_iou_rotated(const float *boxes_a, int n, const float *boxes_b, int m, float *iou, srf_stream_t stream);
+
+/* The dynamic-k OTA label assignment of training (OTAssignerSRFDet, ota_srfdet.py:18-327) for all S decoder stages and B samples of a step
+ * (csrc/ota.hip, whose header holds the exact definition; tests/ota_ref.py is the same text in numpy).
+ *
+ * srf_ota_assign: pred_boxes (S, B, P, D) normalised boxes, columns 0..7 are read; pred_logits (S, B, P, C); gt_boxes (B, Gpad, 7) gravity
+ * centre [x, y, z, dx, dy, dz, yaw], padded; gt_labels (B, Gpad) int32 (clamped into [0, C)); n_gt (B) int32 live boxes per sample (clamped
+ * into [0, Gpad]; the padding is never read); head_idx (S) int32; the weights of FocalLossCost / BBox3DL1Cost / IoU3DCost, the focal
+ * alpha / gamma / eps, center_radius, candidate_topk and num_heads of the assigner.  Fixed-shape outputs, nothing is read back: count (S, B)
+ * matched predictions; pred_idx (S, B, P) their indices ascending in the first count slots; gt_idx (S, B, P) the matched ground truth of each
+ * (the first matched column); the other slots hold -1; status (S, B) 0, or 1 when the repair loop reached its cap of 32 iterations.
+ * Two launches (cost, match), no float atomics: two calls give the same bytes.  workspace: srf_ota_workspace_bytes(S, B, P, Gpad).
+ *
+ * srf_ota_cost / srf_ota_match are the two stages on the caller's own matrices, g-major: cost and iou (S, B, Gpad, P) f32, columns
+ * g >= n_gt[b] untouched.  srf_ota_match adds 100000 to rows of `cost` in place when it has to repair; its workspace holds the match bytes:
+ * srf_ota_match_workspace_bytes(S, B, P, Gpad).
+ *
+ * Checked before any HIP call, in this order: non-positive S, B, P, Gpad, D, C or candidate_topk: SRF_EINVAL; null pointers: SRF_EINVAL;
+ * limits (P <= 4096: a byte of LDS per row; Gpad <= 512: an int of LDS per column; S * B <= 65535; D in {8, 10}; C <= 64; S * B * P * Gpad
+ * and S * B * P * C floats below 2^31 bytes): SRF_EUNSUPPORTED; workspace too small: SRF_EWORKSPACE.  The workspace sizes are 0 outside
+ * the limits. */
+size_t srf_ota_workspace_bytes(int S, int B, int P, int Gpad);
+size_t srf_ota_match_workspace_bytes(int S, int B, int P, int Gpad);
+int srf_ota_cost(const float *pred_boxes, const float *pred_logits, const float *gt_boxes, const int *gt_labels, const int *n_gt, int S, int B,
+                 int P, int D, int C, int Gpad, float w_cls, float w_reg, float w_iou, float alpha, float gamma, float eps, float center_radius,
+                 float *cost, float *iou, srf_stream_t stream);
+int srf_ota_match(float *cost, const float *iou, const int *n_gt, const int *head_idx, int S, int B, int P, int Gpad, int candidate_topk,
+                  int num_heads, int *count, int *pred_idx, int *gt_idx, int *status, void *workspace, size_t workspace_bytes,
+                  srf_stream_t stream);
+int srf_ota_assign(const float *pred_boxes, const float *pred_logits, const float *gt_boxes, const int *gt_labels, const int *n_gt,
+                   const int *head_idx, int S, int B, int P, int D, int C, int Gpad, float w_cls, float w_reg, float w_iou, float alpha,
+                   float gamma, float eps, float center_radius, int candidate_topk, int num_heads, int *count, int *pred_idx, int *gt_idx,
+                   int *status, void *workspace, size_t workspace_bytes, srf_stream_t stream);
+
 size_t srf_nms_rotated_workspace_bytes(int n);
 int srf_nms_rotated(const float *boxes, int n, float iou_threshold, int *keep, void *workspace, size_t workspace_bytes,
                     srf_stream_t stream);

@@ -205,6 +205,13 @@ SIGNATURES = {
     "srf_roi_extract_bwd": (c_int, [POINTER(FeatMap), POINTER(c_void_p), c_int, c_int, _P, c_int, c_int, c_int, c_float, _P,
                                     c_int64, c_int64, c_int64, _P]),
     "srf_box_iou_rotated": (c_int, [_P, c_int, _P, c_int, _P, _P]),
+    "srf_ota_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "srf_ota_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "srf_ota_cost": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
+                             c_float, _P, _P, _P]),
+    "srf_ota_match": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "srf_ota_assign": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
+                               c_float, c_float, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "srf_box_rois": (c_int, [_P, c_int, c_int, c_int, _HF, _HF, c_int, _P, _P, c_int, _P, _P]),
 }
 

@@ -2467,3 +2467,99 @@ def box_iou_rotated(a, b):
     out = _empty((a.shape[0], b.shape[0]), torch.float32, a.device)
     check(_lib.lib().srf_box_iou_rotated(_ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(out), _stream()), "box_iou_rotated")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------- OTA label assignment
+OTA_MAX_P, OTA_MAX_G, OTA_MAX_C, OTA_MAX_PAIRS = 4096, 512, 64, 65535
+
+
+def ota_enabled():
+    """SRF_OTA=0 keeps `plugin.training.OTAssignerSRFDet` on its torch route on the GPU as well: what training ran before csrc/ota.hip, the
+    route the tests and tools/bench_ota.py alternate against.  Read at every call."""
+    return os.environ.get("SRF_OTA", "1") != "0"
+
+
+def ota_assign_ok(S, B, P, D, C, Gpad, candidate_topk=1):
+    """The shapes `srf_ota_assign` takes (csrc/ota.hip, the SRF_EINVAL and SRF_EUNSUPPORTED lines of the entry point): at most 4096
+    predictions (a byte of LDS per row) and 512 padded ground-truth boxes (an int of LDS per column), at most 65535 (stage, sample) pairs,
+    boxes of 8 or 10 columns, at most 64 classes, the cost matrix and the logits inside 32-bit byte ranges."""
+    return (S >= 1 and B >= 1 and 1 <= P <= OTA_MAX_P and 1 <= Gpad <= OTA_MAX_G and S * B <= OTA_MAX_PAIRS and D in (8, 10)
+            and 1 <= C <= OTA_MAX_C and candidate_topk >= 1 and below_2gb(S * B * P, Gpad) and below_2gb(S * B * P, C))
+
+
+def _ota_inputs(pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt):
+    pred_boxes = _dev(pred_boxes, "pred_boxes", torch.float32)
+    pred_logits = _dev(pred_logits, "pred_logits", torch.float32)
+    gt_boxes = _dev(gt_boxes, "gt_boxes", torch.float32)
+    gt_labels = _dev(gt_labels, "gt_labels", torch.int32)
+    n_gt = _dev(n_gt, "n_gt", torch.int32)
+    if pred_boxes.dim() != 4 or pred_logits.dim() != 4 or pred_logits.shape[:3] != pred_boxes.shape[:3]:
+        raise ValueError("ota: pred_boxes (S, B, P, D) and pred_logits (S, B, P, C)")
+    S, B, P, D = pred_boxes.shape
+    if gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 7 or tuple(gt_labels.shape) != tuple(gt_boxes.shape[:2]) or \
+            tuple(n_gt.shape) != (B,):
+        raise ValueError("ota: gt_boxes (B, Gpad, 7), gt_labels (B, Gpad) and n_gt (B)")
+    C, G = pred_logits.shape[3], gt_boxes.shape[1]
+    if not ota_assign_ok(S, B, P, D, C, G):
+        raise ValueError(f"ota: shape S {S} B {B} P {P} D {D} C {C} Gpad {G} is outside the limits of srf_ota_assign (ops.ota_assign_ok)")
+    return pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt, (S, B, P, D, C, G)
+
+
+def ota_assign(pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt, head_idx, cost_weights, alpha, gamma, eps, center_radius, candidate_topk,
+               num_heads):
+    """The dynamic-k OTA assignment of S decoder stages x B samples in one call (`srf_ota_assign`; definition in csrc/ota.hip and, as numpy, in
+    tests/ota_ref.py).  pred_boxes (S, B, P, 8 | 10) normalised boxes; pred_logits (S, B, P, C); gt_boxes (B, Gpad, 7) gravity-centre
+    [x, y, z, dx, dy, dz, yaw], padded; gt_labels (B, Gpad) int32; n_gt (B) int32; head_idx (S) int32; cost_weights the three weights of
+    (FocalLossCost, BBox3DL1Cost, IoU3DCost).  -> count (S, B), pred_idx (S, B, P), gt_idx (S, B, P), status (S, B), all int32: the matched
+    predictions ascending in the first count slots with the ground truth of each, -1 behind them; status 1 where the repair loop hit its
+    cap.  count and status are the two halves of one tensor (`count._base`), so that one copy brings both to the host.  Nothing is read
+    back here."""
+    pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt, (S, B, P, D, C, G) = _ota_inputs(pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt)
+    head_idx = _dev(head_idx, "head_idx", torch.int32)
+    if tuple(head_idx.shape) != (S,) or candidate_topk < 1:
+        raise ValueError("ota: head_idx (S) and candidate_topk >= 1")
+    dev = pred_boxes.device
+    both = _empty((2, S, B), torch.int32, dev)
+    count, status = both[0], both[1]
+    pred_idx, gt_idx = _empty((S, B, P), torch.int32, dev), _empty((S, B, P), torch.int32, dev)
+    L = _lib.lib()
+    ws_bytes = L.srf_ota_workspace_bytes(S, B, P, G)
+    ws = _empty((max(ws_bytes, 1),), torch.uint8, dev)
+    w_cls, w_reg, w_iou = cost_weights
+    check(L.srf_ota_assign(_ptr(pred_boxes), _ptr(pred_logits), _ptr(gt_boxes), _ptr(gt_labels), _ptr(n_gt), _ptr(head_idx), S, B, P, D, C, G,
+                           w_cls, w_reg, w_iou, alpha, gamma, eps, center_radius, candidate_topk, num_heads, _ptr(count), _ptr(pred_idx),
+                           _ptr(gt_idx), _ptr(status), _ptr(ws), ws_bytes, _stream()), "ota_assign")
+    return count, pred_idx, gt_idx, status
+
+
+def ota_cost(pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt, cost_weights, alpha, gamma, eps, center_radius):
+    """The first stage of `ota_assign` alone (`srf_ota_cost`): -> cost, iou (S, B, Gpad, P) f32, g-major as the matching reads them; the
+    columns g >= n_gt[b] are not written."""
+    pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt, (S, B, P, D, C, G) = _ota_inputs(pred_boxes, pred_logits, gt_boxes, gt_labels, n_gt)
+    cost, iou = _empty((S, B, G, P), torch.float32, pred_boxes.device), _empty((S, B, G, P), torch.float32, pred_boxes.device)
+    w_cls, w_reg, w_iou = cost_weights
+    check(_lib.lib().srf_ota_cost(_ptr(pred_boxes), _ptr(pred_logits), _ptr(gt_boxes), _ptr(gt_labels), _ptr(n_gt), S, B, P, D, C, G, w_cls, w_reg,
+                                  w_iou, alpha, gamma, eps, center_radius, _ptr(cost), _ptr(iou), _stream()), "ota_cost")
+    return cost, iou
+
+
+def ota_match(cost, iou, n_gt, head_idx, candidate_topk, num_heads):
+    """The second stage of `ota_assign` alone (`srf_ota_match`) on g-major matrices cost, iou (S, B, Gpad, P) f32.  `cost` is left as it was:
+    the kernel works on a copy (it adds to the rows it repairs).  -> count, pred_idx, gt_idx, status as `ota_assign`."""
+    cost = _dev(cost, "cost", torch.float32).clone()
+    iou = _dev(iou, "iou", torch.float32)
+    n_gt, head_idx = _dev(n_gt, "n_gt", torch.int32), _dev(head_idx, "head_idx", torch.int32)
+    if cost.dim() != 4 or cost.shape != iou.shape or tuple(n_gt.shape) != (cost.shape[1],) or tuple(head_idx.shape) != (cost.shape[0],):
+        raise ValueError("ota_match: cost and iou (S, B, Gpad, P), n_gt (B), head_idx (S)")
+    S, B, G, P = cost.shape
+    if not ota_assign_ok(S, B, P, 8, 1, G, candidate_topk):
+        raise ValueError("ota_match: shape outside the limits of srf_ota_match (ops.ota_assign_ok)")
+    dev = cost.device
+    both = _empty((2, S, B), torch.int32, dev)
+    pred_idx, gt_idx = _empty((S, B, P), torch.int32, dev), _empty((S, B, P), torch.int32, dev)
+    L = _lib.lib()
+    ws_bytes = L.srf_ota_match_workspace_bytes(S, B, P, G)
+    ws = _empty((max(ws_bytes, 1),), torch.uint8, dev)
+    check(L.srf_ota_match(_ptr(cost), _ptr(iou), _ptr(n_gt), _ptr(head_idx), S, B, P, G, candidate_topk, num_heads, _ptr(both[0]), _ptr(pred_idx), _ptr(gt_idx), _ptr(both[1]),
+                          _ptr(ws), ws_bytes, _stream()), "ota_match")
+    return both[0], pred_idx, gt_idx, both[1]

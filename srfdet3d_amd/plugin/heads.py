@@ -877,15 +877,25 @@ class SRFDetHead(BaseModule):
         """srfdet_head.py:1041-1201.  The reference calls `reduce_mean` twice per decoder layer (the matched-pair count of the
         classification and of the box loss: 10 blocking all-reduces + `.item()` per iteration, :1134, :1178).  Both counts of a layer are
         the same number and every one of them is known once the assignments are made, so here the layers are assigned first and
-        ALL counts travel in ONE all-reduce with ONE read-back (collective C4)."""
+        ALL counts travel in ONE all-reduce with ONE read-back (collective C4).
+        An assigner with `assign_layers` (OTAssignerSRFDet) assigns all layers in one call whose own read-back -- the matched counts --
+        is the only device-to-host copy of the step in one process: the counts are then host numbers, and the losses select their rows by
+        the index tensors that call returns.  Under torch.distributed the all-reduce of the counts brings a second one."""
+        import torch.distributed as dist
         from .training import reduce_mean
         dev = gt_labels_list[0].device
         gts = [torch.cat((g.gravity_center, g.tensor[:, 3:]), dim=1).to(dev) for g in gt_bboxes_list]
         losses = {}
         layers = [(outputs, self.num_heads, "")] + [(aux, i + 1, f"s.{i}.") for i, aux in enumerate(outputs.get("aux_outputs", []))]
-        assigned = [self.assigner(out, gts, gt_labels_list, head_idx) for out, head_idx, _ in layers]
-        local = [float(sum(int(j.numel()) for _, j in idx)) for idx in assigned]          # host-known: no synchronisation
-        reduced = reduce_mean(torch.tensor(local, dtype=torch.float32, device=dev)).tolist()   # one collective, one read-back
+        if hasattr(self.assigner, "assign_layers"):
+            assigned = self.assigner.assign_layers([(out, head_idx) for out, head_idx, _ in layers], gts, gt_labels_list)
+        else:
+            assigned = [self.assigner(out, gts, gt_labels_list, head_idx) for out, head_idx, _ in layers]
+        local = [float(sum(int(a[1].numel()) for a in idx)) for idx in assigned]          # host-known: no synchronisation
+        if dist.is_available() and dist.is_initialized():
+            reduced = reduce_mean(torch.tensor(local, dtype=torch.float32, device=dev)).tolist()   # one collective, one read-back
+        else:
+            reduced = local                                                               # reduce_mean of one process: the counts themselves
         for (out, _, prefix), idx, n_local, n_mean in zip(layers, assigned, local, reduced):
             n_cls = n_mean if self.sync_cls_avg_factor else n_local
             losses[prefix + "loss_cls"] = self.loss_classification(out, gt_labels_list, idx, num=max(n_cls, 1.0))
@@ -897,8 +907,10 @@ class SRFDetHead(BaseModule):
         logits = outputs["pred_logits"]
         target = torch.full(logits.shape[:2], self.num_classes, dtype=torch.int64, device=logits.device)
         n = 0
-        for b, (labels, (fg, j)) in enumerate(zip(gt_labels_list, indices)):
-            target[b, fg] = labels[j]
+        for b, (labels, idx) in enumerate(zip(gt_labels_list, indices)):
+            fg, j = idx
+            rows = getattr(idx, "rows", None)
+            target[b, fg if rows is None else rows] = labels[j]     # by index: the same rows without the mask's host synchronisation
             n += int(j.numel())
         if num is None:   # stand-alone call: the reference's own sequence (one all-reduce for this layer)
             t = logits.new_tensor([float(n)])
@@ -912,7 +924,8 @@ class SRFDetHead(BaseModule):
         from .bbox_util import normalize_bbox
         from .training import reduce_mean
         pred = outputs["pred_boxes"]
-        p = torch.cat([pred[b, fg] for b, (fg, _) in enumerate(indices)])
+        by_index = all(getattr(idx, "rows", None) is not None for idx in indices)
+        p = torch.cat([pred[b, idx.rows if by_index else idx[0]] for b, idx in enumerate(indices)])   # the same rows in the same order
         t = torch.cat([g[j] for g, (_, j) in zip(gt_bboxes_list, indices)])
         if len(p) == 0:
             return torch.nan_to_num(pred.sum() * 0)
@@ -922,6 +935,11 @@ class SRFDetHead(BaseModule):
         ok = torch.isfinite(tn).all(dim=-1)
         D = self.code_weights.numel()
         w = torch.ones_like(p) * self.code_weights
+        if by_index:
+            # no boolean mask (a host synchronisation): a row with a non-finite target meets its own prediction, |p - p| = 0 and no gradient.
+            # With every target finite -- any real step -- these are the operands of the masked form bit for bit.
+            pd = p[:, :D]
+            return torch.nan_to_num(self.loss_bbox(pd, torch.where(ok[:, None], tn[:, :D], pd.detach()), w[:, :D]) / num)
         return torch.nan_to_num(self.loss_bbox(p[ok, :D], tn[ok, :D], w[ok, :D]) / num)
 
     def simple_test_bboxes(self, img_feats, point_feats, img_metas):

@@ -1,6 +1,7 @@
 """Training-side pieces of the reference that sit next to the hot path: losses, match costs, 3-D IoU,
-the dynamic-k OTA label assignment and the frozen-LiDAR-branch helper.  Plain torch (label assignment is
-O(np * n_gt)), except the rotated BEV IoU, which is a HIP kernel.
+the dynamic-k OTA label assignment and the frozen-LiDAR-branch helper.  The losses and match costs are plain torch.  The label assignment
+on the GPU is HIP: all decoder stages and samples of a step in one call (`ops.ota_assign`, csrc/ota.hip; SRF_OTA=0 switches it off), with
+the torch restatement kept as the route of everything that call does not take; so is the rotated BEV IoU under `bbox_overlaps_3d`.
 
 Mirrors: OTAssignerSRFDet  mmdet3d_plugin/core/bbox/assigners/ota_srfdet.py:18-327
          BBox3DL1Cost / IoU3DCost  mmdet3d_plugin/core/bbox/match_costs/match_cost.py:5-36
@@ -179,9 +180,22 @@ class HungarianAssignerSRFDet:
         return AssignResult(n_gt, gt_inds, None, labels=labels)
 
 
+class Assigned(tuple):
+    """What OTAssignerSRFDet returns for one sample: the pair (fg, j) -- fg (n_p,) bool, the foreground predictions; j (fg.sum(),) long, the
+    ground-truth index of each in ascending prediction order -- and, on the kernel route, `rows` = the foreground indices themselves
+    (fg.nonzero() without its host synchronisation), so that the losses select rows by index.  `rows` is None on the torch route."""
+
+    def __new__(cls, fg, j, rows=None):
+        self = super().__new__(cls, (fg, j))
+        self.rows = rows
+        return self
+
+
 @BBOX_ASSIGNERS.register_module()
 class OTAssignerSRFDet(nn.Module):
-    """1-to-k dynamic matching of predictions to ground truth (ota_srfdet.py:18-327)."""
+    """1-to-k dynamic matching of predictions to ground truth (ota_srfdet.py:18-327).  On the GPU the whole assignment of a step -- every
+    decoder stage, every sample -- is one call of `ops.ota_assign` (csrc/ota.hip: a cost and a match kernel, no read-back inside); the torch
+    ops below are the same assignment for everything that call does not take (`kernel_route`)."""
 
     def __init__(self, cls_cost, reg_cost, iou_cost, center_radius=1.5, candidate_topk=5, pc_range=None, iou_calculator=None,
                  num_heads=6):
@@ -190,21 +204,109 @@ class OTAssignerSRFDet(nn.Module):
         self.cls_cost, self.reg_cost, self.iou_cost = MATCH_COST.build(cls_cost), MATCH_COST.build(reg_cost), MATCH_COST.build(iou_cost)
 
     def forward(self, outputs, gt_boxes_list, gt_labels_list, head_idx):
-        return [self.single_assigner(outputs["pred_boxes"][i], outputs["pred_logits"][i], gt_boxes_list[i], gt_labels_list[i],
-                                     head_idx) for i in range(len(gt_boxes_list))]
+        return self.assign_layers([(outputs, head_idx)], gt_boxes_list, gt_labels_list)[0]
+
+    def single_assigner(self, pred_boxes, pred_logits, gt_boxes, gt_labels, head_idx):
+        out = dict(pred_boxes=pred_boxes[None], pred_logits=pred_logits[None])
+        return self.assign_layers([(out, head_idx)], [gt_boxes], [gt_labels])[0][0]
+
+    def kernel_params(self):
+        """The scalar arguments of `ops.ota_assign`, or None when a match cost is not one of the three classes csrc/ota.hip restates."""
+        if type(self.cls_cost) is not FocalLossCost or type(self.reg_cost) is not BBox3DL1Cost or type(self.iou_cost) is not IoU3DCost:
+            return None
+        c = self.cls_cost
+        return dict(cost_weights=(float(c.weight), float(self.reg_cost.weight), float(self.iou_cost.weight)), alpha=float(c.alpha),
+                    gamma=float(c.gamma), eps=float(c.eps), center_radius=float(self.center_radius), candidate_topk=int(self.candidate_topk),
+                    num_heads=int(self.num_heads))
+
+    def kernel_route(self, layers, gts, labels):
+        """Whether `assign_layers` makes the one call of `ops.ota_assign`: SRF_OTA is not 0, the three match costs are the configs', every
+        tensor is a float32 (labels: integer) GPU tensor and the stacked shape is inside `ops.ota_assign_ok`."""
+        if not ops.ota_enabled() or self.kernel_params() is None or not layers or not gts:
+            return False
+        boxes, logits = layers[0][0]["pred_boxes"], layers[0][0]["pred_logits"]
+        for out, head_idx in layers:
+            b, l = out["pred_boxes"], out["pred_logits"]
+            if not (b.is_cuda and l.is_cuda and b.dtype == l.dtype == torch.float32 and b.dim() == 3 and b.shape == boxes.shape
+                    and l.shape == logits.shape and l.shape[:2] == b.shape[:2]) or not isinstance(head_idx, int):
+                return False
+        if len(gts) != boxes.shape[0] or len(labels) != len(gts):
+            return False
+        for g, l in zip(gts, labels):
+            if not (g.is_cuda and l.is_cuda and g.dtype == torch.float32 and g.dim() == 2 and g.shape[1] >= 7 and l.dim() == 1
+                    and l.shape[0] == g.shape[0] and not l.dtype.is_floating_point and l.dtype != torch.bool):
+                return False
+        gpad = self._gpad(gts)
+        return ops.ota_assign_ok(len(layers), boxes.shape[0], boxes.shape[1], boxes.shape[2], logits.shape[2], gpad, self.candidate_topk)
+
+    @staticmethod
+    def _gpad(gts):
+        return (max(max(int(g.shape[0]) for g in gts), 1) + 7) // 8 * 8
 
     @torch.no_grad()
-    def single_assigner(self, pred_boxes, pred_logits, gt_boxes, gt_labels, head_idx):
+    def assign_layers(self, layers, gts, labels):
+        """All decoder stages of a step at once.  layers: [(outputs of a stage, its head_idx)], every stage with pred_boxes (B, P, D) and
+        pred_logits (B, P, C); gts / labels: the B samples' (n, >= 7) gravity-centre boxes and (n,) classes.  -> per stage, per sample an
+        `Assigned`: (fg, j) as `single_assigner` has always returned them, with `.rows` = the foreground indices ascending.
+        On the kernel route (`kernel_route`) this is ONE call of `ops.ota_assign` and ONE device-to-host copy (the matched counts and the
+        status words); a (stage, sample) pair whose repair loop hit the kernel's cap is assigned again by the torch route."""
+        if not self.kernel_route(layers, gts, labels):
+            return [[self._single_torch(out["pred_boxes"][i], out["pred_logits"][i], gts[i], labels[i], head_idx) for i in range(len(gts))]
+                    for out, head_idx in layers]
+        dev = gts[0].device
+        S, B, P, G = len(layers), len(gts), layers[0][0]["pred_boxes"].shape[1], self._gpad(gts)
+        boxes = torch.stack([out["pred_boxes"].detach() for out, _ in layers])
+        logits = torch.stack([out["pred_logits"].detach() for out, _ in layers])
+        ns = [int(g.shape[0]) for g in gts]                                  # host-known: no synchronisation
+        gt_pad, lab_pad = torch.zeros((B, G, 7), dtype=torch.float32, device=dev), torch.zeros((B, G), dtype=torch.int32, device=dev)
+        for b, (g, l) in enumerate(zip(gts, labels)):
+            if ns[b]:
+                gt_pad[b, :ns[b]] = g[:, :7]
+                lab_pad[b, :ns[b]] = l
+        # the box counts and head indices go up in one copy from pinned memory: a copy from pageable memory waits for the stream
+        meta = torch.tensor(ns + [h for _, h in layers], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        n_gt, heads = meta[:B], meta[B:]
+        count, pred_idx, gt_idx, status = ops.ota_assign(boxes, logits, gt_pad, lab_pad, n_gt, heads, **self.kernel_params())
+        host = count._base.cpu().tolist()                                    # the one read-back: [counts, status words]
+        # fg of every pair in one go: slot t of pair q is foreground row pred_idx[q, t] when t < count[q]; the other slots go to a spare cell
+        slot = torch.arange(P, device=dev)
+        live = slot[None, None, :] < count[:, :, None]
+        flat = (torch.arange(S * B, device=dev).view(S, B, 1) * P + pred_idx).masked_fill_(~live, S * B * P)
+        fg_all = torch.zeros(S * B * P + 1, dtype=torch.bool, device=dev)
+        fg_all.index_fill_(0, flat.view(-1), True)
+        fg_all = fg_all[:S * B * P].view(S, B, P)
+        rows_all, j_all = pred_idx.long(), gt_idx.long()
+        res = []
+        for s, (out, head_idx) in enumerate(layers):
+            stage = []
+            for b in range(B):
+                n = host[0][s][b]
+                if host[1][s][b] != 0:
+                    stage.append(self._single_torch(out["pred_boxes"][b], out["pred_logits"][b], gts[b], labels[b], head_idx))
+                else:
+                    stage.append(Assigned(fg_all[s, b], j_all[s, b, :n], rows_all[s, b, :n]))
+            res.append(stage)
+        return res
+
+    @torch.no_grad()
+    def _single_torch(self, pred_boxes, pred_logits, gt_boxes, gt_labels, head_idx):
+        """One stage of one sample in torch ops: the route of CPU tensors, other dtypes, shapes past the kernel's limits, other match costs,
+        SRF_OTA=0 and of a pair the kernel gave up on."""
         n_gt = gt_boxes.size(0)
         if n_gt == 0:
-            return pred_boxes.new_zeros((pred_boxes.shape[0],), dtype=torch.bool), pred_boxes.new_zeros((0,), dtype=torch.long)
+            return Assigned(pred_boxes.new_zeros((pred_boxes.shape[0],), dtype=torch.bool), pred_boxes.new_zeros((0,), dtype=torch.long))
+        cost, ious = self.cost_matrices(pred_boxes, pred_logits, gt_boxes, gt_labels)
+        return Assigned(*self._dynamic_k(cost, ious, n_gt, head_idx))
+
+    def cost_matrices(self, pred_boxes, pred_logits, gt_boxes, gt_labels):
+        """cost and 3-D IoU (n_p, n_gt) of one sample, n_gt > 0, in torch ops."""
         valid, in_both = self._in_gt_and_center(pred_boxes, gt_boxes)
         cls = self.cls_cost(pred_logits, gt_labels)
         reg = self.reg_cost(pred_boxes[:, :8], normalize_bbox(gt_boxes[:, :7], self.pc_range))
         ious = bbox_overlaps_3d(denormalize_bbox(pred_boxes, self.pc_range), gt_boxes)
         cost = cls + reg + self.iou_cost(ious) + (~in_both) * 100.0
         cost[~valid] = cost[~valid] + 10000.0
-        return self._dynamic_k(cost, ious, n_gt, head_idx)
+        return cost, ious
 
     def _in_gt_and_center(self, pred, gt):
         c = pred[:, None, :3]                                                  # (n_p, 1, 3)
@@ -221,6 +323,8 @@ class OTAssignerSRFDet(nn.Module):
         # the reference walks the ground-truth boxes: `topk(cost[:, g], k = ks[g].item(), largest=False)` per box (ota_srfdet.py:296-300) --
         # one read-back of ks and, per box, a top-k and an index_put launch (200 + 200 launches per step at 20 boxes x 10 assignments).
         # The same set in one pass: a prediction matches box g when its rank in the ascending order of cost[:, g] is below ks[g].
+        # Ties go to the lower index (the stable sort here, the first minimum of argmin below): tests/ota_ref.py states the rule,
+        # tests/test_ota_ref.py holds this function to it, and csrc/ota.hip follows it on the GPU.
         order = torch.argsort(cost, dim=0, stable=True)
         rank = torch.empty_like(order)
         rank.scatter_(0, order, torch.arange(cost.shape[0], device=cost.device)[:, None].expand_as(order))

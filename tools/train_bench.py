@@ -44,6 +44,9 @@ def main():
                          "state to FILE (markdown); rank 0 only")
     ap.add_argument("--train-mfma-dtype", default=None, choices=["bf16"],
                     help="SRFDet.train_mfma_dtype: the image backbone + neck train on one bf16 product per f32 product (default: f32)")
+    ap.add_argument("--ota-ab", type=int, default=0, metavar="R",
+                    help="after the timed iterations, R more alternated pairs of --iters iterations with the label assignment on its HIP "
+                         "route and on the torch route (SRF_OTA unset / 0, read at every call): iterations/s of each, one model, one process")
     a = ap.parse_args()
     rank, local, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(local)
@@ -156,6 +159,38 @@ def main():
                                                        "(they include queueing behind earlier buckets and overlap one another: an UPPER bound, as is the "
                                                        "first-start-to-last-end span); the buckets overlap with backward (world == 1: no collective)"),
                               loss_scalar_allreduces_per_step=1 if world > 1 else 0)))
+    if a.ota_ab:
+        keep = os.environ.get("SRF_OTA")
+        its = {"hip": [], "torch": []}
+        fwd_ms = {"hip": [], "torch": []}
+        for _ in range(a.ota_ab):
+            for name in ("hip", "torch"):
+                if name == "hip":
+                    os.environ.pop("SRF_OTA", None)
+                else:
+                    os.environ["SRF_OTA"] = "0"
+                step()
+                del phases[:]
+                torch.cuda.synchronize()
+                if world > 1:
+                    dist.barrier()
+                t1 = time.perf_counter()
+                for _ in range(a.iters):
+                    step(record=True)
+                torch.cuda.synchronize()
+                if world > 1:
+                    dist.barrier()
+                its[name].append(round(a.iters / (time.perf_counter() - t1), 3))
+                fwd_ms[name].append(round(sum(e[0].elapsed_time(e[1]) for e in phases) / len(phases), 2))
+        if keep is None:
+            os.environ.pop("SRF_OTA", None)
+        else:
+            os.environ["SRF_OTA"] = keep
+        if rank == 0:
+            print(json.dumps(dict(metric="training iterations/s, label assignment on the HIP route against the torch route (SRF_OTA=0), alternated",
+                                  n_gpus=world, bs_per_gpu=a.bs, num_proposals=a.np, image=f"{h}x{w}", train_mfma_dtype=a.train_mfma_dtype,
+                                  iters_per_window=a.iters, it_per_s=its, forward_and_loss_ms=fwd_ms,
+                                  spread_it_per_s={k: round(max(v) - min(v), 3) for k, v in its.items()})))
     if rank == 0 and a.kernel_table:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
