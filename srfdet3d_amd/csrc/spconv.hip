@@ -675,25 +675,35 @@ __device__ __forceinline__ void srf_gsp_step(__amdgpu_buffer_rsrc_t rs, __amdgpu
         __builtin_amdgcn_sched_barrier(0);
     }
     // ---- LDS only again: accumulators of step i back into the tile, those of step i + 1 out of it (in-order LDS: shared rows are
-    // read after they were written); plain ds_read_b32 into the accumulator registers themselves (the compiler pairs them as
-    // ds_read2 and then shuffles registers behind a wait), awaited before the barrier together with the stores ----
+    // read after they were written); plain ds_read_b32 in assembly (the compiler pairs its own as ds_read2 and then shuffles
+    // registers behind a wait).  The compiler counts none of these reads: nothing touches t[][] until the wait statement in front
+    // of the barrier, which names every one of them, has retired the reads together with the stores; acc is assigned behind it ----
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
         for (int cb = 0; cb < NT; ++cb) *reinterpret_cast<srf_lds_float *>(G.oaddr[jj] + cb * 64) = acc[cb][jj];
     __builtin_amdgcn_sched_barrier(0);
+    float t[NT][4];
 #pragma unroll
     for (int cb = 0; cb < NT; ++cb)
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-            float t;
-            if (cb == 0) asm volatile("ds_read_b32 %0, %1" : "=v"(t) : "v"(oaddr_n[jj]) : "memory");
-            else asm volatile("ds_read_b32 %0, %1 offset:64" : "=v"(t) : "v"(oaddr_n[jj]) : "memory");
-            acc[cb][jj] = t;
+            if (cb == 0) asm volatile("ds_read_b32 %0, %1" : "=v"(t[cb][jj]) : "v"(oaddr_n[jj]) : "memory");
+            else asm volatile("ds_read_b32 %0, %1 offset:64" : "=v"(t[cb][jj]) : "v"(oaddr_n[jj]) : "memory");
         }
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) G.oaddr[jj] = oaddr_n[jj];   // (a renaming: the copies, if any, land in the next MFMA block)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if constexpr (NT == 1)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[0][2]), "+v"(t[0][3]) : : "memory");
+    else
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[0][2]), "+v"(t[0][3]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[1][2]), "+v"(t[1][3])
+                     :
+                     : "memory");
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) acc[cb][jj] = t[cb][jj];
     __syncthreads();
 }
 

@@ -206,27 +206,33 @@ __global__ __launch_bounds__(256, 2) void srf_wgrad_split_k(WgArgs a)
     wg_bf8 fa[3][2], fb[3][2];
     // k step KS: rows + 16 = + 4096 bytes (the swizzle term (row >> 2) & 3 is unchanged by + 16 rows); plane PL: + WG_PLANE -- both as
     // the instruction's immediate offset: 8 address registers serve the 48 transposed reads of a chunk
-#define WG_FRAG(DST, O, T, PL, KS)                                                                                         \
+    // the two transposed reads (halves 0 and 1) of operand O, tile T, plane PL: rd[8 PL + 4 O + 2 T + h]
+#define WG_TR2(O, T, PL, KS)                                                                                               \
     do {                                                                                                                   \
-        wg_u2 r0_, r1_;                                                                                                    \
-        WG_TR(r0_, fad[O][T][0], (KS) * 4096 + (PL) * WG_PLANE);                                                           \
-        WG_TR(r1_, fad[O][T][1], (KS) * 4096 + (PL) * WG_PLANE);                                                           \
-        DST##_raw = wg_u4{r0_[0], r0_[1], r1_[0], r1_[1]};                                                                 \
+        WG_TR(rd[8 * (PL) + 4 * (O) + 2 * (T)], fad[O][T][0], (KS) * 4096 + (PL) * WG_PLANE);                              \
+        WG_TR(rd[8 * (PL) + 4 * (O) + 2 * (T) + 1], fad[O][T][1], (KS) * 4096 + (PL) * WG_PLANE);                          \
     } while (0)
-    wg_u4 fa00_raw, fa01_raw, fa10_raw, fa11_raw, fa20_raw, fa21_raw, fb00_raw, fb01_raw, fb10_raw, fb11_raw, fb20_raw, fb21_raw;
+    // ... -> the fragment: its two halves side by side
+#define WG_FRAG(O, T, PL) __builtin_bit_cast(wg_bf8, (wg_u4{rd[8 * (PL) + 4 * (O) + 2 * (T)][0], rd[8 * (PL) + 4 * (O) + 2 * (T)][1], \
+                                                            rd[8 * (PL) + 4 * (O) + 2 * (T) + 1][0], rd[8 * (PL) + 4 * (O) + 2 * (T) + 1][1]}))
+    // The 24 reads of a k step are statements of their own (the compiler places them among the MFMAs of the step before); the
+    // compiler counts none of them, and nothing reads rd[] until the wait statement, which names all 24 destinations, has run:
+    // the fragments, and through them the MFMAs, depend on that statement's outputs.
+    wg_u2 rd[24];
 #define WG_READ(KS)                                                                                                        \
     do {                                                                                                                   \
-        WG_FRAG(fa00, 0, 0, 0, KS); WG_FRAG(fa01, 0, 1, 0, KS); WG_FRAG(fb00, 1, 0, 0, KS); WG_FRAG(fb01, 1, 1, 0, KS);    \
-        WG_FRAG(fa10, 0, 0, 1, KS); WG_FRAG(fa11, 0, 1, 1, KS); WG_FRAG(fb10, 1, 0, 1, KS); WG_FRAG(fb11, 1, 1, 1, KS);    \
-        WG_FRAG(fa20, 0, 0, 2, KS); WG_FRAG(fa21, 0, 1, 2, KS); WG_FRAG(fb20, 1, 0, 2, KS); WG_FRAG(fb21, 1, 1, 2, KS);    \
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa00_raw), "+v"(fa01_raw), "+v"(fa10_raw), "+v"(fa11_raw), "+v"(fa20_raw), "+v"(fa21_raw)); \
-        asm volatile("" : "+v"(fb00_raw), "+v"(fb01_raw), "+v"(fb10_raw), "+v"(fb11_raw), "+v"(fb20_raw), "+v"(fb21_raw)); \
-        fa[0][0] = *reinterpret_cast<const wg_bf8 *>(&fa00_raw); fa[0][1] = *reinterpret_cast<const wg_bf8 *>(&fa01_raw);   \
-        fa[1][0] = *reinterpret_cast<const wg_bf8 *>(&fa10_raw); fa[1][1] = *reinterpret_cast<const wg_bf8 *>(&fa11_raw);   \
-        fa[2][0] = *reinterpret_cast<const wg_bf8 *>(&fa20_raw); fa[2][1] = *reinterpret_cast<const wg_bf8 *>(&fa21_raw);   \
-        fb[0][0] = *reinterpret_cast<const wg_bf8 *>(&fb00_raw); fb[0][1] = *reinterpret_cast<const wg_bf8 *>(&fb01_raw);   \
-        fb[1][0] = *reinterpret_cast<const wg_bf8 *>(&fb10_raw); fb[1][1] = *reinterpret_cast<const wg_bf8 *>(&fb11_raw);   \
-        fb[2][0] = *reinterpret_cast<const wg_bf8 *>(&fb20_raw); fb[2][1] = *reinterpret_cast<const wg_bf8 *>(&fb21_raw);   \
+        WG_TR2(0, 0, 0, KS); WG_TR2(0, 1, 0, KS); WG_TR2(1, 0, 0, KS); WG_TR2(1, 1, 0, KS);                                \
+        WG_TR2(0, 0, 1, KS); WG_TR2(0, 1, 1, KS); WG_TR2(1, 0, 1, KS); WG_TR2(1, 1, 1, KS);                                \
+        WG_TR2(0, 0, 2, KS); WG_TR2(0, 1, 2, KS); WG_TR2(1, 0, 2, KS); WG_TR2(1, 1, 2, KS);                                \
+        asm volatile("s_waitcnt lgkmcnt(0)"                                                                                \
+                     : "+v"(rd[0]), "+v"(rd[1]), "+v"(rd[2]), "+v"(rd[3]), "+v"(rd[4]), "+v"(rd[5]), "+v"(rd[6]), "+v"(rd[7]),           \
+                       "+v"(rd[8]), "+v"(rd[9]), "+v"(rd[10]), "+v"(rd[11]), "+v"(rd[12]), "+v"(rd[13]), "+v"(rd[14]), "+v"(rd[15]),     \
+                       "+v"(rd[16]), "+v"(rd[17]), "+v"(rd[18]), "+v"(rd[19]), "+v"(rd[20]), "+v"(rd[21]), "+v"(rd[22]), "+v"(rd[23]));  \
+        _Pragma("unroll") for (int pl_ = 0; pl_ < 3; ++pl_)                                                                \
+            _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_) {                                                             \
+                fa[pl_][t_] = WG_FRAG(0, t_, pl_);                                                                         \
+                fb[pl_][t_] = WG_FRAG(1, t_, pl_);                                                                         \
+            }                                                                                                              \
     } while (0)
 #define WG_MM(PA, PB)                                                                                                      \
     _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                                       \
@@ -258,6 +264,7 @@ __global__ __launch_bounds__(256, 2) void srf_wgrad_split_k(WgArgs a)
 #undef WG_STORE
 #undef WG_READ
 #undef WG_FRAG
+#undef WG_TR2
 #undef WG_MM
 #undef WG_MFMA6
 
