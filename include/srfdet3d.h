@@ -484,7 +484,8 @@ int srf_box_rois(float *boxes, int B, int P, int box_dim, const float *pc_range 
  *   [LayerNorm(ln1, eps1)] -> [ReLU if relu1] -> [+ residual (M x N, ldr)] -> [LayerNorm(ln2, eps2)] -> [ReLU if relu2];
  *   null pointers skip a step.  Replaces nn.Linear + nn.LayerNorm + ReLU (+ the residual adds) call chains, e.g.
  *   out_layer -> norm3 -> ReLU -> (+prop) -> norm2 (srfdet_head.py:2689-2691, :1502-1503).  K % 4 == 0; K >= 2048 is
- *   split over K and needs the workspace (srf_linear_workspace_bytes); LayerNorm steps need N <= 1024.
+ *   split over K and needs the workspace (srf_linear_workspace_bytes), as does any row step with N > 128.  The row steps
+ *   (LayerNorm, residual, relu2) need N <= 1024, else SRF_EUNSUPPORTED; bias and relu1 alone take any N, split over K or not.
  * srf_self_attention: qkv (P x 3E) = [q | k | v] rows after in_proj -> out (P x E), heads H, head dim E/H in {16, 32};
  *   replaces the attention core of nn.MultiheadAttention(batch 1) at srfdet_head.py:1489.
  * srf_dynconv_mid: feats (R x S x C) bin-major RoI features, params (R x 2*C*D) from dynamic_layer ->

@@ -349,6 +349,24 @@ __global__ __launch_bounds__(256) void srf_rows_epilogue_k(const float *__restri
         if (lane + i * 64 < N) Y[(size_t)row * ldy + lane + i * 64] = v[i];
 }
 
+// split-K slabs of a product wider than the 1024 columns a wave of srf_rows_epilogue_k<16> spans.  Only the plain chain
+// (bias, relu1) gets here -- a row epilogue with N > 1024 is refused -- and that chain is column-local: one thread per
+// column, rows over blockIdx.y, slabs summed in slab order like the row reducer.
+__global__ __launch_bounds__(256) void srf_cols_epilogue_k(const float *__restrict__ partial, int nsplit, int M, int N,
+                                                         float *__restrict__ Y, int ldy, const float *__restrict__ bias, int relu)
+{
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= N) return;
+    const float b = bias ? bias[col] : 0.f;
+    for (int row = blockIdx.y; row < M; row += gridDim.y) {
+        float s = 0.f;
+        for (int p = 0; p < nsplit; ++p) s += partial[((size_t)p * M + row) * N + col];
+        s += b;
+        if (relu) s = s > 0.f ? s : 0.f;
+        Y[(size_t)row * ldy + col] = s;
+    }
+}
+
 static RowEpilogue srf_make_epilogue(const float *bias, const float *ln1_g, const float *ln1_b, float eps1, int relu1,
                                      const float *residual, int ldr, const float *ln2_g, const float *ln2_b, float eps2,
                                      int relu2)
@@ -464,6 +482,9 @@ extern "C" int srf_linear(const float *X, int M, int K, int ldx, const float *W,
         if (N <= 128)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_rows_epilogue_k<2>), dim3(srf_ceil_div(M, 4)), dim3(256), 0, st,
                                (const float *)workspace, nsplit, M, N, Y, ldy, ep);
+        else if (N > 1024)  // !rows (refused above otherwise): bias / relu1 per column, no whole-row wave
+            hipLaunchKernelGGL(srf_cols_epilogue_k, dim3(srf_ceil_div(N, 256), M < 65535 ? M : 65535), dim3(256), 0, st,
+                               (const float *)workspace, nsplit, M, N, Y, ldy, bias, relu1);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_rows_epilogue_k<16>), dim3(srf_ceil_div(M, 4)), dim3(256), 0, st,
                                (const float *)workspace, nsplit, M, N, Y, ldy, ep);

@@ -1432,7 +1432,7 @@ def stem7_range_ok(pixels, ld):
 
 
 def ese_channels_ok(C):
-    """Channels of an eSE block's output: quads for srf_ese_gate (csrc/decoder.hip:427) and srf_nhwc_affine (csrc/nhwc.hip:65); C <= 1024
+    """Channels of an eSE block's output: quads for srf_ese_gate (csrc/decoder.hip:445) and srf_nhwc_affine (csrc/nhwc.hip:65); C <= 1024
     as the gate held it (the bound of srf_nhwc_colmean, csrc/nhwc.hip:137, which took the eSE mean before the GEMM's epilogue did)."""
     return quads_ok(C) and C <= 1024
 

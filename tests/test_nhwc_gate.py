@@ -80,7 +80,7 @@ LIMITS = [
     (ops.stem_channels_ok, (3, 32), False, "Cout != 64 (csrc/conv.hip:1352)"),
     (ops.ese_channels_ok, (1024,), True, "as the gate held it: out_channels <= 1024"),
     (ops.ese_channels_ok, (1028,), False, "as the gate held it: out_channels > 1024 (the bound of srf_nhwc_colmean, csrc/nhwc.hip:137)"),
-    (ops.ese_channels_ok, (1022,), False, "C & 3: srf_ese_gate (csrc/decoder.hip:427), srf_nhwc_affine (csrc/nhwc.hip:65)"),
+    (ops.ese_channels_ok, (1022,), False, "C & 3: srf_ese_gate (csrc/decoder.hip:445), srf_nhwc_affine (csrc/nhwc.hip:65)"),
     (ops.gemm_k_ok, (768,), True, "the 768-wide buffer of a stage-2 block of V-99-eSE (srf_gemm_check_1x1: K & 31, csrc/gemm_host.hpp)"),
     (ops.gemm_k_ok, (720,), False, "the stage-5 buffer of V-19-slim-eSE: 720 & 31 (srf_gemm_check_1x1: K & 31, csrc/gemm_host.hpp)"),
     # the executor applies the range of srf_wino3x3 to every buffer a 3x3 layer reads, whichever Winograd kernel runs the layer
