@@ -339,7 +339,8 @@ int srf_rulebook_strided_pairs(int A, const int *ksize, const void *out_table, i
  * Replaces spconv SubMConv3d/SparseConv3d.forward (+ the BN1d and ReLU modules chained by mmdet3d's
  * make_sparse_convmodule / SparseBasicBlock) on the path sparse_encoder_custom.py:125-134.
  * out[o] = sum_k W[k]^T in[nbr[k][o]] accumulated as an f32 fma chain (k ascending, c ascending);
- * then y = fma(x, alpha, beta) if alpha, y += residual[o] if residual, y = max(y,0) if relu.
+ * then y = fma(x, alpha, beta) if alpha, y += residual[o] if residual, y = max(y,0) if relu (each step one rounded f32 operation:
+ * srf_spconv_epilogue, csrc/spconv_frame.hpp, shared by every entry point below).
  * W: (K, Cin, Cout) row-major.  Supported Cout: 16 (any Cin <= 512) and 32, 64, 128 (Cin a multiple of 4).
  * rows_dev (may be NULL): device int; output rows >= *rows_dev are padding of a static-shape level and are skipped
  * (their tiles return at once), so a hipGraph can launch the layer at its capacity without paying for it.
@@ -365,11 +366,8 @@ int srf_spconv_bwd_weight(const float *in, int A_in, int Cin, const float *grad_
 
 /* Fast path of K5 for constant weights: re-lay W once (srf_spconv_pack_weights -> packed, of
  * srf_spconv_packed_weight_bytes bytes) into the operand layout of the kernel, then call srf_spconv_fwd_packed with
- * the same remaining arguments.  Results are bit-identical to srf_spconv_fwd.  The shapes with a packed form:
- *   Cin -> Cout        K
- *   16 / 32 -> 32      27
- *   32 / 64 -> 64      any
- *   64 / 128 -> 128    any
+ * the same remaining arguments.  Results are bit-identical to srf_spconv_fwd.  The shapes (K, Cin, Cout) with a packed form, with the
+ * bf16 form below and with a row plan are ONE table: srf_spconv_shape, csrc/spconv_frame.hpp.
  * srf_spconv_packed_weight_bytes returns 0 for every other shape (no packed form: use srf_spconv_fwd); there
  * srf_spconv_pack_weights and srf_spconv_fwd_packed return SRF_EUNSUPPORTED.  srf_spconv_fwd_packed also returns
  * SRF_EUNSUPPORTED for an input of 2 GiB or more (A_in * Cin * 4 >= 2^31) or with no rows (A_in == 0). */
@@ -392,22 +390,24 @@ int srf_spconv_tiles_row_cost(void);
 size_t srf_spconv_tiles_workspace_bytes(int A_out);
 int srf_spconv_tiles_build(const int *nbr, int nbr_stride, int K, int A_out, const int *rows_dev, void *workspace,
                            int *tiles, srf_stream_t stream);
-/* Row order for the 32-output-channel layers of srf_spconv_fwd_packed (optional; passed as its `tiles` argument when Cout == 32,
- * Cin in {16, 32}, K == 27): rows with the same set of kernel offsets side by side, so that a wave, which multiplies every offset any of
+/* Row order for the 32-output-channel layers of srf_spconv_fwd_packed (optional; passed as its `tiles` argument for the shapes of
+ * plan kind 2): rows with the same set of kernel offsets side by side, so that a wave, which multiplies every offset any of
  * its 32 rows has, skips more of them.  plan: srf_spconv_order_ints(A_out, K) ints = [order: A_pad][sorted rulebook: K x A_pad], A_pad =
  * A_out rounded up to 1024; order[pos] = the row at position pos (-1: padding).  One launch, no workspace; rows_dev as for the
  * convolution.  Outputs are bit-identical with and without a plan (every row is its own fma chain).  No reference counterpart. */
 size_t srf_spconv_order_ints(int A_out, int K);
 int srf_spconv_order_build(const int *nbr, int nbr_stride, int K, int A_out, const int *rows_dev, int *plan, srf_stream_t stream);
+/* Which plan srf_spconv_fwd_packed takes as `tiles` for a layer shape (the table's third column; a host call): 0 none, 1 the row
+ * ranges of srf_spconv_tiles_build, 2 the row order of srf_spconv_order_build. */
+int srf_spconv_plan_kind(int K, int Cin, int Cout);
 
 /* K5 with bf16 products (opt-in, inference; no reference counterpart beyond its fp16 option): f32 tensors, every input value and every
  * weight rounded to bf16 once (round to nearest even), exact products on the bf16 MFMA, f32 accumulation in a fixed order, the epilogue
  * of srf_spconv_fwd in f32 on the f32 accumulator (alpha, beta and the residual are not rounded), f32 stored.  Defined exactly by
  * tests/spconv_bf16_ref.py.  The bits of an output row depend on its own pairs, the operands and the epilogue alone (not on A_out,
  * *rows_dev, `tiles` or the rows beside it); two launches give the same bits.  Non-finite weights are outside the domain.
- * The shapes (K, Cin, Cout) with this form are the ones srf_spconv_fwd_packed runs on its 64- / 128-channel kernel in the encoders:
- *   (27, 32, 64)  (27, 64, 64)  (27, 64, 128)  (27, 128, 128)  (3, 128, 128)
- * srf_spconv_bf16_packed_weight_bytes returns 0 for every other shape; there srf_spconv_bf16_pack_weights and srf_spconv_fwd_bf16
+ * The shapes (K, Cin, Cout) with this form are the ones srf_spconv_fwd_packed runs on its 64- / 128-channel kernel in the encoders
+ * (the table's bf16 column).  srf_spconv_bf16_packed_weight_bytes returns 0 for every other shape; there srf_spconv_bf16_pack_weights and srf_spconv_fwd_bf16
  * return SRF_EUNSUPPORTED.  srf_spconv_bf16_pack_weights rounds W (K, Cin, Cout) and lays it out for the kernel.  srf_spconv_fwd_bf16
  * takes the arguments of srf_spconv_fwd_packed with the same meanings and the same codes in the same order, all decided before any
  * HIP call: bad arguments SRF_EINVAL; another shape SRF_EUNSUPPORTED; A_out == 0 SRF_OK with nothing launched; null pointers

@@ -77,6 +77,7 @@ SIGNATURES = {
     "srf_spconv_tiles_build": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "srf_spconv_order_ints": (c_size_t, [c_int, c_int]),
     "srf_spconv_order_build": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
+    "srf_spconv_plan_kind": (c_int, [c_int, c_int, c_int]),
     "srf_spconv_bf16_packed_weight_bytes": (c_size_t, [c_int, c_int, c_int]),
     "srf_spconv_bf16_pack_weights": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "srf_spconv_fwd_bf16": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P]),

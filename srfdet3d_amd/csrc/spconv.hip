@@ -10,17 +10,16 @@
 // v_mfma_f32_32x32x2_f32 (v_mfma_f32_16x16x4_f32 for COUT = 16).  Missing neighbours contribute exact zeros.
 // The f32 MFMA is a k-ordered fma chain, so every output element is the chain over (k ascending, c ascending)
 // that oracle/srf_oracle.c:orc_spconv_fwd forms -- results compare exactly.  Each output row is written once,
-// with eval-BatchNorm (y = fma(x, alpha, beta)), residual add and ReLU applied in registers.
+// with the epilogue of spconv_frame.hpp (eval-BatchNorm, residual add, ReLU) applied in registers.
 //
 // LDS per workgroup (COUT = 128): nbr tile 27*64*4 = 6.9 KB, A chunk 64*33*4 = 8.4 KB, W chunk 32*128*4 = 16 KB
 // -> 5 workgroups per CU; latency is hidden by occupancy rather than by an explicit pipeline.
-#include "common.hpp"
+#include "spconv_frame.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define SRF_KC 32
-#define SRF_KMAX 27
 
 template <int TM, int COUT>
 __device__ __forceinline__ void srf_stage_tile(const float *__restrict__ in, int Cin, const float *__restrict__ Wk, int c0,
@@ -58,15 +57,6 @@ __device__ __forceinline__ void srf_stage_tile(const float *__restrict__ in, int
         if (c0 + c < Cin) v = *reinterpret_cast<const float4 *>(Wk + (size_t)(c0 + c) * COUT + j * 4);
         *reinterpret_cast<float4 *>(&s_w[c][j * 4]) = v;
     }
-}
-
-// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).  Give every XCD one contiguous
-// range of output tiles, so that the input rows its tiles gather (rows that are close in index are close in space)
-// stay in that XCD's 4 MB L2 instead of being re-fetched through the fabric.  Bijective for any grid size.
-__device__ __forceinline__ int srf_xcd_tile(int b, int n)
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
 
 template <int TM>
@@ -173,10 +163,7 @@ __global__ __launch_bounds__(256) void srf_spconv_mfma32_k(const float *__restri
     __shared__ float s_a[2][TM][SRF_KC + 1];
     __shared__ __attribute__((aligned(16))) float s_w[2][SRF_KC][COUT];
 
-    if (rows_dev) {  // static-shape levels: rows >= *rows_dev are padding; their tiles do nothing
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
+    A_out = srf_live_rows(A_out, rows_dev);
     // tiles of LIVE rows only, dealt XCD-contiguously over the first n_tiles workgroups (a capacity-sized launch must not
     // leave whole XCDs with nothing but padding)
     const int n_tiles = (A_out + TM - 1) / TM;
@@ -257,32 +244,19 @@ __global__ __launch_bounds__(256) void srf_spconv_mfma32_k(const float *__restri
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int row = row0 + wr * 32 + (j & 3) + 8 * (j >> 2) + 4 * kh;
-            if (row < A_out) {
-                float v = acc[ct][j];
-                if (alpha) v = __fmaf_rn(v, al, be);
-                if (residual) v = __fadd_rn(v, residual[(size_t)row * COUT + col]);
-                if (relu) v = v > 0.0f ? v : 0.0f;
-                out[(size_t)row * COUT + col] = v;
-            }
+            if (row < A_out)
+                out[(size_t)row * COUT + col] =
+                    srf_spconv_epilogue(acc[ct][j], alpha, al, be, residual, [&] { return residual[(size_t)row * COUT + col]; }, relu);
         }
     }
 }
 
 // =====================================================================================================================
 // Packed weights (inference: the weights are constants, so they are re-laid-out once per layer).  A layer shape has at most
-// one packed layout, and srf_spconv_fwd_packed runs one kernel on it:
-//   w32: K = 27, Cout = 32, Cin in {16, 32}                     -> srf_spconv_w32_k (srf_pack_weights_w32_k)
-//   gs:  Cout = 64, Cin in {32, 64}; Cout = 128, Cin in {64, 128}; any K -> srf_spconv_gsp_k (srf_pack_weights_gs_k)
-// Every other shape has none (srf_spconv_packed_weight_bytes = 0) and runs on srf_spconv_fwd, which gives the same bits.
+// one packed layout, and srf_spconv_fwd_packed runs one kernel on it (the shapes: srf_spconv_shape, spconv_frame.hpp):
+//   w32 -> srf_spconv_w32_k (srf_pack_weights_w32_k)         gs -> srf_spconv_gsp_k (srf_pack_weights_gs_k)
 // =====================================================================================================================
-enum SrfPackedLayout { SRF_PACKED_NONE, SRF_PACKED_W32, SRF_PACKED_GS };
-static SrfPackedLayout srf_packed_layout(int K, int Cin, int Cout)
-{
-    if (K <= 0 || K > SRF_KMAX) return SRF_PACKED_NONE;
-    if (K == SRF_KMAX && Cout == 32 && (Cin == 16 || Cin == 32)) return SRF_PACKED_W32;
-    if ((Cout == 64 && (Cin == 32 || Cin == 64)) || (Cout == 128 && (Cin == 64 || Cin == 128))) return SRF_PACKED_GS;
-    return SRF_PACKED_NONE;
-}
+extern "C" int srf_spconv_plan_kind(int K, int Cin, int Cout) { return srf_spconv_shape(K, Cin, Cout).plan; }
 
 __global__ void srf_pack_weights_gs_k(const float *__restrict__ W, int K, int Cin, int Cout, int nchunk, float *__restrict__ P);
 
@@ -303,14 +277,14 @@ __global__ __launch_bounds__(256) void srf_pack_weights_w32_k(const float *__res
 
 extern "C" size_t srf_spconv_packed_weight_bytes(int K, int Cin, int Cout)
 {
-    if (srf_packed_layout(K, Cin, Cout) == SRF_PACKED_NONE) return 0;
+    if (srf_spconv_shape(K, Cin, Cout).packed == SRF_PACKED_NONE) return 0;
     return (size_t)K * ((Cin + 31) / 32) * Cout * 32 * sizeof(float);
 }
 
 extern "C" int srf_spconv_pack_weights(const float *W, int K, int Cin, int Cout, float *packed, srf_stream_t stream)
 {
     if (!W || !packed || K <= 0 || K > SRF_KMAX || Cin <= 0 || Cout <= 0) return SRF_EINVAL;
-    const SrfPackedLayout layout = srf_packed_layout(K, Cin, Cout);
+    const SrfPackedLayout layout = srf_spconv_shape(K, Cin, Cout).packed;
     if (layout == SRF_PACKED_NONE) return SRF_EUNSUPPORTED;
     if (layout == SRF_PACKED_W32) {
         hipLaunchKernelGGL(srf_pack_weights_w32_k, dim3(srf_ceil_div((long long)K * Cin * 32, 256)), dim3(256), 0, (hipStream_t)stream, W, K,
@@ -408,10 +382,7 @@ __global__ __launch_bounds__(256) void srf_gs_rowpairs_k(const int *__restrict__
                                                        int *__restrict__ blocksum, int row_cost)
 {
     __shared__ int s_scan[4];
-    if (rows_dev) {
-        const int live = *rows_dev;
-        A = A < live ? A : live;
-    }
+    A = srf_live_rows(A, rows_dev);
     const int r0 = blockIdx.x * SRF_TB_ROWS;
     int carry = 0;
     for (int j = 0; j < SRF_TB_ROWS / 256; ++j) {  // block-uniform trip count: the barriers inside the scan are safe
@@ -456,10 +427,7 @@ __global__ __launch_bounds__(256) void srf_gs_blockscan_k(const int *__restrict_
 __global__ __launch_bounds__(256) void srf_gs_cut_k(const int *__restrict__ local, const int *__restrict__ blockoff, int nb, int A,
                                                   const int *__restrict__ rows_dev, int T, int *__restrict__ tiles)
 {
-    if (rows_dev) {
-        const int live = *rows_dev;
-        A = A < live ? A : live;
-    }
+    A = srf_live_rows(A, rows_dev);
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t > T) return;
     const int nbl = (A + SRF_TB_ROWS - 1) / SRF_TB_ROWS;  // live blocks (<= nb)
@@ -733,10 +701,7 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
     __shared__ __attribute__((aligned(16))) float s_a[2 * NCH * CHS];
 
     const int A_cap = A_out;
-    if (rows_dev) {
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
+    A_out = srf_live_rows(A_out, rows_dev);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int range0, range1;
     if (tiles) {
@@ -948,13 +913,7 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_gsp_k(const float *__restri
         f32x4 rsd = {0.f, 0.f, 0.f, 0.f};
         if (residual) rsd = *reinterpret_cast<const f32x4 *>(residual + (size_t)row * COUT + c4);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float x = v[j];
-            if (alpha) x = __fmaf_rn(x, al[j], be[j]);
-            if (residual) x = __fadd_rn(x, rsd[j]);
-            if (relu) x = x > 0.0f ? x : 0.0f;
-            v[j] = x;
-        }
+        for (int j = 0; j < 4; ++j) v[j] = srf_spconv_epilogue(v[j], alpha, al[j], be[j], residual, [&] { return rsd[j]; }, relu);
         *reinterpret_cast<f32x4 *>(out + (size_t)row * COUT + c4) = v;
     }
     __syncthreads();
@@ -995,10 +954,7 @@ __global__ __launch_bounds__(256) void srf_spconv_order_k(const int *__restrict_
     __shared__ int s_hist[SRF_ORD_BINS];
     __shared__ int s_part[256];
     __shared__ int s_row[SRF_ORD_WIN];
-    if (rows_dev) {
-        const int live = *rows_dev;
-        A = A < live ? A : live;
-    }
+    A = srf_live_rows(A, rows_dev);
     const int tid = threadIdx.x, w0 = blockIdx.x * SRF_ORD_WIN;
     for (int b = tid; b < SRF_ORD_BINS; b += 256) s_hist[b] = 0;
     __syncthreads();
@@ -1085,10 +1041,7 @@ __global__ __launch_bounds__(512) void srf_spconv_w32_k(const float *__restrict_
     constexpr int K = SRF_KMAX, H = CIN / 2, NV = H / 4, NB = CIN / 8, TM = 256;
     extern __shared__ __attribute__((aligned(16))) f32x4 s_w32[];   // [K][NB][2][32]
     const int A_cap = A_out;
-    if (rows_dev) {
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
+    A_out = srf_live_rows(A_out, rows_dev);
     const int n_tiles = plan ? ((A_out + SRF_ORD_WIN - 1) / SRF_ORD_WIN) * 4 : (A_out + TM - 1) / TM;
     if ((int)blockIdx.x >= n_tiles) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1195,10 +1148,7 @@ __global__ __launch_bounds__(512) void srf_spconv_w32_k(const float *__restrict_
     }
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-        float v = acc[j];
-        if (alpha) v = __fmaf_rn(v, al, be);
-        if (residual) v = __fadd_rn(v, res[j]);
-        if (relu) v = v > 0.0f ? v : 0.0f;
+        const float v = srf_spconv_epilogue(acc[j], alpha, al, be, residual, [&] { return res[j]; }, relu);
         if (orow[j] >= 0) out[(size_t)orow[j] * 32 + r] = v;
     }
 }
@@ -1208,14 +1158,11 @@ extern "C" int srf_spconv_fwd_packed(const float *in, int A_in, int Cin, const f
                                      const float *residual, int relu, float *out, const int *rows_dev, const int *tiles,
                                      srf_stream_t stream)
 {
-    if (A_in < 0 || A_out < 0 || Cin <= 0 || Cin > 512 || K <= 0 || K > SRF_KMAX || nbr_stride < A_out) return SRF_EINVAL;
-    if ((alpha == nullptr) != (beta == nullptr)) return SRF_EINVAL;
-    const SrfPackedLayout layout = srf_packed_layout(K, Cin, Cout);
-    if (layout == SRF_PACKED_NONE) return SRF_EUNSUPPORTED;
-    if (A_out == 0) return SRF_OK;
-    if (!in || !W_packed || !nbr || !out) return SRF_EINVAL;
-    // both kernels gather through a buffer descriptor: 32-bit byte offsets into the input
-    if (A_in == 0 || (long long)A_in * Cin * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;
+    const SrfPackedLayout layout = srf_spconv_shape(K, Cin, Cout).packed;
+    // both kernels gather through a buffer descriptor (range32)
+    const int rc = srf_spconv_check({layout != SRF_PACKED_NONE, false, true}, in, A_in, Cin, W_packed, K, nbr, nbr_stride, A_out, Cout, alpha,
+                                    beta, out);
+    if (rc != SRF_OK || A_out == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (layout == SRF_PACKED_W32) {
         int dev = 0;
@@ -1270,10 +1217,7 @@ __global__ __launch_bounds__(256) void srf_spconv_mfma16_k(const float *__restri
     __shared__ float s_a[TM][SRF_KC + 1];
     __shared__ __attribute__((aligned(16))) float s_w[SRF_KC][COUT];
 
-    if (rows_dev) {  // static-shape levels: rows >= *rows_dev are padding; their tiles do nothing
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
+    A_out = srf_live_rows(A_out, rows_dev);
     const int row0 = blockIdx.x * TM;
     if (row0 >= A_out) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1304,13 +1248,8 @@ __global__ __launch_bounds__(256) void srf_spconv_mfma16_k(const float *__restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int row = row0 + wave * 16 + kq * 4 + j;
-        if (row < A_out) {
-            float v = acc[j];
-            if (alpha) v = __fmaf_rn(v, al, be);
-            if (residual) v = __fadd_rn(v, residual[(size_t)row * COUT + col]);
-            if (relu) v = v > 0.0f ? v : 0.0f;
-            out[(size_t)row * COUT + col] = v;
-        }
+        if (row < A_out)
+            out[(size_t)row * COUT + col] = srf_spconv_epilogue(acc[j], alpha, al, be, residual, [&] { return residual[(size_t)row * COUT + col]; }, relu);
     }
 }
 
@@ -1328,10 +1267,7 @@ __global__ __launch_bounds__(256) void srf_spconv_c16_k(const float *__restrict_
                                                       const int *__restrict__ rows_dev)
 {
     constexpr int COUT = 16, KM = SRF_KMAX, G = 9;
-    if (rows_dev) {  // static-shape levels: rows >= *rows_dev are padding; their tiles do nothing
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
+    A_out = srf_live_rows(A_out, rows_dev);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row0 = (blockIdx.x * 4 + wave) * 16;
     if (row0 >= A_out) return;  // no barriers in this kernel: waves are independent
@@ -1385,13 +1321,8 @@ __global__ __launch_bounds__(256) void srf_spconv_c16_k(const float *__restrict_
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int orow = row0 + q * 4 + i;
-        if (orow < A_out) {
-            float v = acc[i];
-            if (alpha) v = __fmaf_rn(v, al, be);
-            if (residual) v = __fadd_rn(v, residual[(size_t)orow * COUT + r]);
-            if (relu) v = v > 0.f ? v : 0.f;
-            out[(size_t)orow * COUT + r] = v;
-        }
+        if (orow < A_out)
+            out[(size_t)orow * COUT + r] = srf_spconv_epilogue(acc[i], alpha, al, be, residual, [&] { return residual[(size_t)orow * COUT + r]; }, relu);
     }
 }
 
@@ -1409,10 +1340,7 @@ __global__ __launch_bounds__(256) void srf_spconv_c16l_k(const float *__restrict
 {
     constexpr int COUT = 16, KM = SRF_KMAX, G = 3, NBATCH = KM / G, D = 3;
     __shared__ float s_w[KM * STEPS * 64];   // [k][j][lane]: lane (col r, q) holds W[k][4 j + q][r]
-    if (rows_dev) {
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
+    A_out = srf_live_rows(A_out, rows_dev);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
     for (int e = tid; e < KM * STEPS * 64; e += 256) {
@@ -1455,7 +1383,7 @@ __global__ __launch_bounds__(256) void srf_spconv_c16l_k(const float *__restrict
     }
 #undef C16L_LOAD
     const float al = alpha ? alpha[r] : 1.f, be = alpha ? beta[r] : 0.f;
-    float res[4];
+    float res[4] = {0.f, 0.f, 0.f, 0.f};
     if (residual) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1466,10 +1394,7 @@ __global__ __launch_bounds__(256) void srf_spconv_c16l_k(const float *__restrict
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int orow = row0 + q * 4 + i;
-        float v = acc[i];
-        if (alpha) v = __fmaf_rn(v, al, be);
-        if (residual) v = __fadd_rn(v, res[i]);
-        if (relu) v = v > 0.f ? v : 0.f;
+        const float v = srf_spconv_epilogue(acc[i], alpha, al, be, residual, [&] { return res[i]; }, relu);
         if (orow < A_out) out[(size_t)orow * COUT + r] = v;
     }
 }
@@ -1481,11 +1406,9 @@ extern "C" int srf_spconv_fwd(const float *in, int A_in, int Cin, const float *W
                               int A_out, int Cout, const float *alpha, const float *beta, const float *residual,
                               int relu, float *out, const int *rows_dev, srf_stream_t stream)
 {
-    if (A_in < 0 || A_out < 0 || Cin <= 0 || Cin > 512 || K <= 0 || K > SRF_KMAX || nbr_stride < A_out) return SRF_EINVAL;
-    if ((alpha == nullptr) != (beta == nullptr)) return SRF_EINVAL;
-    if (A_out == 0) return SRF_OK;
-    if (!in || !W || !nbr || !out) return SRF_EINVAL;
-    if (Cout != 16 && ((Cin & 3) || A_in == 0)) return SRF_EUNSUPPORTED;  // the wide kernels gather whole float4s
+    // the wide kernels gather whole float4s (quads); the output width is decided by the switch below
+    const int rc = srf_spconv_check({true, true, false}, in, A_in, Cin, W, K, nbr, nbr_stride, A_out, Cout, alpha, beta, out);
+    if (rc != SRF_OK || A_out == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
 #define SRF_ARGS in, Cin, W, K, nbr, nbr_stride, A_out, alpha, beta, residual, relu, out, rows_dev
     switch (Cout) {

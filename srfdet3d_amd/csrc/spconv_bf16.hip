@@ -7,8 +7,8 @@
 //     out[o, :] = epilogue( sum over offsets k with nbr[k][o] >= 0, over channels c of  bf16(x[nbr[k][o], c]) * bf16(W[k, c, :]) )
 // bf16() = round to nearest even (v_cvt_pk_bf16_f32 = torch.Tensor.bfloat16()); the weights are rounded once, when they are packed, a
 // gathered row in registers right behind its load.  Every product is exact in f32; the sum is an f32 accumulation in a fixed order
-// (offsets ascending; inside an offset 16 channels per v_mfma_f32_32x32x16_bf16, ascending).  The epilogue is the f32 route's, in f32
-// on the f32 accumulator: fma(acc, alpha, beta), + residual, ReLU.  alpha, beta and the residual are not rounded; f32 is stored.
+// (offsets ascending; inside an offset 16 channels per v_mfma_f32_32x32x16_bf16, ascending).  The epilogue is the f32 route's
+// (srf_spconv_epilogue, spconv_frame.hpp), in f32 on the f32 accumulator.  alpha, beta and the residual are not rounded; f32 is stored.
 // No float atomics: two launches give the same bits.
 //
 // The bits of an output row depend on that row's own pairs, the operands and the epilogue alone -- not on the capacity, the live row
@@ -24,7 +24,7 @@
 // arithmetic gives on the ROUNDED operands of the row's OWN pairs -- a non-finite input row reaches exactly the output rows whose
 // rulebook column holds it, because every other row multiplies zeros from the descriptor, not that row; bf16 subnormals are kept).
 // Non-finite WEIGHTS are outside the domain: a row without a pair at an offset multiplies 0 x W[k] there, which must be 0.
-// Limits: the five layer shapes of srf_spconv_gsp_k (below), inputs below 2 GiB (32-bit buffer offsets).
+// Limits: the layer shapes srf_spconv_shape (spconv_frame.hpp) gives the bf16 form, inputs below 2 GiB (32-bit buffer offsets).
 //
 // Structure: output-stationary.  A workgroup = 4 waves x 32 consecutive output rows; a wave keeps its 32 x COUT accumulators in
 // registers (COUT / 32 tiles of v_mfma_f32_32x32x16_bf16).  Lane (row r = lane & 31, half h = lane >> 5) of that MFMA holds the
@@ -34,11 +34,8 @@
 // waves through two LDS images: the image of the next used offset goes global -> registers before the MFMAs and registers -> LDS
 // behind them, one barrier per offset.  The tile's rulebook columns sit in LDS (27 x 128 ints); offsets no row of the workgroup has
 // are not staged at all.
-#include "common.hpp"
+#include "spconv_frame.hpp"
 
-#ifndef SRF_KMAX
-#define SRF_KMAX 27
-#endif
 #define SB_ROWS 128   // output rows of a workgroup: 4 waves x 32
 
 typedef __bf16 sb_bf2 __attribute__((ext_vector_type(2)));
@@ -48,24 +45,11 @@ typedef float sb_f4 __attribute__((ext_vector_type(4)));
 typedef float sb_f16 __attribute__((ext_vector_type(16)));
 typedef unsigned sb_u4 __attribute__((ext_vector_type(4)));
 
-static bool sb_shape_ok(int K, int Cin, int Cout)
-{
-    if (K == 27) return (Cout == 64 && (Cin == 32 || Cin == 64)) || (Cout == 128 && (Cin == 64 || Cin == 128));
-    return K == 3 && Cin == 128 && Cout == 128;
-}
-
 __device__ __forceinline__ unsigned sb_pk_bf16(float a, float b)
 {
     const sb_f2 v = {a, b};
     const sb_bf2 h = __builtin_convertvector(v, sb_bf2);   // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
     return *reinterpret_cast<const unsigned *>(&h);
-}
-
-// srf_xcd_tile of spconv.hip: every XCD gets one contiguous range of tiles (blocks b and b + 8 share an L2)
-__device__ __forceinline__ int sb_xcd_tile(int b, int n)
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
 
 // W (K, Cin, Cout) f32 -> P[k][s = Cin / 16][n = Cout / 32][lane 64][j 8] bf16 = W[k][16 s + 8 (lane >> 5) + j][32 n + (lane & 31)]
@@ -95,13 +79,10 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_bf16_k(const float *__restr
     __shared__ int s_nbr[SRF_KMAX * SB_ROWS];
     __shared__ unsigned s_mask;
 
-    if (rows_dev) {
-        const int live = *rows_dev;
-        A_out = A_out < live ? A_out : live;
-    }
+    A_out = srf_live_rows(A_out, rows_dev);
     const int n_tiles = (A_out + SB_ROWS - 1) / SB_ROWS;
     if ((int)blockIdx.x >= n_tiles) return;
-    const int row0 = sb_xcd_tile(blockIdx.x, n_tiles) * SB_ROWS;
+    const int row0 = srf_xcd_tile(blockIdx.x, n_tiles) * SB_ROWS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
 
     if (tid == 0) s_mask = 0u;
@@ -205,24 +186,20 @@ __global__ __launch_bounds__(256, 2) void srf_spconv_bf16_k(const float *__restr
         for (int j = 0; j < 16; ++j) {
             const int row = row0 + wave * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
             if (row >= A_out) continue;
-            float x = acc[n][j];
-            if (alpha) x = __fmaf_rn(x, al, be);
-            if (residual) x = __fadd_rn(x, residual[(size_t)row * COUT + col]);
-            if (relu) x = x > 0.0f ? x : 0.0f;
-            out[(size_t)row * COUT + col] = x;
+            out[(size_t)row * COUT + col] = srf_spconv_epilogue(acc[n][j], alpha, al, be, residual, [&] { return residual[(size_t)row * COUT + col]; }, relu);
         }
     }
 }
 
 extern "C" size_t srf_spconv_bf16_packed_weight_bytes(int K, int Cin, int Cout)
 {
-    return sb_shape_ok(K, Cin, Cout) ? (size_t)K * Cin * Cout * 2 : 0;
+    return srf_spconv_shape(K, Cin, Cout).bf16 ? (size_t)K * Cin * Cout * 2 : 0;
 }
 
 extern "C" int srf_spconv_bf16_pack_weights(const float *W, int K, int Cin, int Cout, void *packed, srf_stream_t stream)
 {
     if (!W || !packed || K <= 0 || K > SRF_KMAX || Cin <= 0 || Cout <= 0) return SRF_EINVAL;
-    if (!sb_shape_ok(K, Cin, Cout)) return SRF_EUNSUPPORTED;
+    if (!srf_spconv_shape(K, Cin, Cout).bf16) return SRF_EUNSUPPORTED;
     const int total = K * Cin * Cout;
     hipLaunchKernelGGL(srf_spconv_bf16_pack_k, dim3(srf_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, W, Cin, Cout,
                        (unsigned short *)packed, total);
@@ -235,12 +212,10 @@ extern "C" int srf_spconv_fwd_bf16(const float *in, int A_in, int Cin, const voi
                                    float *out, const int *rows_dev, const int *tiles, srf_stream_t stream)
 {
     (void)tiles;   // no row plan: equal-height tiles (every row's bits are its own, see the header)
-    if (A_in < 0 || A_out < 0 || Cin <= 0 || Cin > 512 || K <= 0 || K > SRF_KMAX || nbr_stride < A_out) return SRF_EINVAL;
-    if ((alpha == nullptr) != (beta == nullptr)) return SRF_EINVAL;
-    if (!sb_shape_ok(K, Cin, Cout)) return SRF_EUNSUPPORTED;
-    if (A_out == 0) return SRF_OK;
-    if (!in || !W_packed || !nbr || !out) return SRF_EINVAL;
-    if (A_in == 0 || (long long)A_in * Cin * 4 >= (1ll << 31)) return SRF_EUNSUPPORTED;   // 32-bit buffer offsets into the input
+    // 32-bit buffer offsets into the input (range32)
+    const int rc = srf_spconv_check({srf_spconv_shape(K, Cin, Cout).bf16, false, true}, in, A_in, Cin, W_packed, K, nbr, nbr_stride, A_out, Cout,
+                                    alpha, beta, out);
+    if (rc != SRF_OK || A_out == 0) return rc;
     const dim3 grid((unsigned)srf_ceil_div(A_out, SB_ROWS));
 #define SB_LAUNCH(CIN, COUT)                                                                                                              \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_spconv_bf16_k<CIN, COUT>), grid, dim3(256), 0, (hipStream_t)stream, in, A_in,                    \

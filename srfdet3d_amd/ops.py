@@ -505,9 +505,28 @@ def rulebook_strided_bitmap(indices, level, ksize, stride, pad, out_capacity=Non
 KERNEL_TIMING = None
 
 
+# Which (K, Cin, Cout) has a packed-weight kernel, a bf16-product form and a row plan is ONE table of the library (srf_spconv_shape,
+# csrc/spconv_frame.hpp); the four questions below are host calls into it, no GPU work.
 def spconv_packed_supported(K, Cin, Cout):
-    """True for the layer shapes with a packed-weight kernel (include/srfdet3d.h); a host call, no GPU work."""
+    """True for the layer shapes with a packed-weight kernel."""
     return _lib.lib().srf_spconv_packed_weight_bytes(K, Cin, Cout) > 0
+
+
+def spconv_plan_kind(K, Cin, Cout):
+    """The plan the packed kernel of this shape takes as `tiles=`: 0 none, 1 row ranges (`spconv_tiles`), 2 a row order (`spconv_order`)."""
+    return _lib.lib().srf_spconv_plan_kind(K, Cin, Cout)
+
+
+def spconv_input_ok(rows, Cin):
+    """An input the packed and the bf16-product kernels can address -- 32-bit byte offsets through a buffer descriptor: it has rows and
+    lies below 2 GiB (`range32` of srf_spconv_check, csrc/spconv_frame.hpp); any other runs on srf_spconv_fwd."""
+    return 0 < 4 * rows * Cin < (1 << 31)
+
+
+def _rulebook(nbr):
+    if not nbr.is_cuda or nbr.dtype != torch.int32 or nbr.stride(1) != 1:
+        raise RuntimeError("srfdet3d_amd: `nbr` must be a GPU int32 tensor with unit inner stride")
+    return nbr.shape
 
 
 def pack_spconv_weights(weight):
@@ -525,7 +544,7 @@ def pack_spconv_weights(weight):
 
 
 def spconv_bf16_supported(K, Cin, Cout):
-    """True for the layer shapes `srf_spconv_fwd_bf16` takes (include/srfdet3d.h); a host call, no GPU work."""
+    """True for the layer shapes `srf_spconv_fwd_bf16` takes."""
     return _lib.lib().srf_spconv_bf16_packed_weight_bytes(K, Cin, Cout) > 0
 
 
@@ -560,7 +579,7 @@ def pack_spconv_bf16_weights(weight):
 def spconv_tiles_wanted(Cin, Cout):
     """True for the layer shapes whose packed kernel takes a row plan (`tiles=` of spconv_fwd): work-balanced row ranges
     (`spconv_tiles`) for the 64- / 128-channel kernels, a mask-sorted row order (`spconv_order`) for the 32-channel one."""
-    return (Cout == 128 and Cin in (64, 128)) or (Cout == 64 and Cin in (32, 64)) or spconv_order_wanted(Cin, Cout)
+    return spconv_plan_kind(27, Cin, Cout) == 1 or spconv_order_wanted(Cin, Cout)
 
 
 SPCONV_ORDER_MIN_ROWS = 100000   # rows of a level from which the sorted order pays for its launch (tools/spconv_order_probe.py, MI355X:
@@ -572,7 +591,7 @@ def spconv_order_wanted(Cin, Cout, K=27, rows=None):
     """rows=None: is this a layer shape the plan exists for; with rows: also, is the level large enough for it to pay
     (SRF_SPCONV_ORDER=0 / 2: never / at any size)."""
     mode = os.environ.get("SRF_SPCONV_ORDER", "1")
-    if not (Cout == 32 and Cin in (16, 32) and K == 27 and mode != "0"):
+    if not (spconv_plan_kind(K, Cin, Cout) == 2 and mode != "0"):
         return False
     return rows is None or mode == "2" or rows >= SPCONV_ORDER_MIN_ROWS
 
@@ -580,9 +599,7 @@ def spconv_order_wanted(Cin, Cout, K=27, rows=None):
 def spconv_order(nbr, rows_dev=None):
     """The plan of `srf_spconv_order_build` for the rulebook nbr (K, A_out): int32 [order | sorted rulebook].  Built once per
     rulebook and passed as `tiles=` to every 32-channel spconv_fwd(..., packed=) that uses it."""
-    if not nbr.is_cuda or nbr.dtype != torch.int32 or nbr.stride(1) != 1:
-        raise RuntimeError("srfdet3d_amd: `nbr` must be a GPU int32 tensor with unit inner stride")
-    K, A_out = nbr.shape
+    K, A_out = _rulebook(nbr)
     L = _lib.lib()
     plan = _empty((max(L.srf_spconv_order_ints(A_out, K), 1),), torch.int32, nbr.device)
     check(L.srf_spconv_order_build(_ptr(nbr), nbr.stride(0) if A_out > 0 else 0, K, A_out, _ptr(rows_dev), _ptr(plan), _stream()),
@@ -593,9 +610,7 @@ def spconv_order(nbr, rows_dev=None):
 def spconv_tiles(nbr, rows_dev=None):
     """Row ranges of equal pair count for the rulebook nbr (K, A_out): int32 (srf_spconv_tiles_count(A_out) + 1,).
     Built once per rulebook and passed to every spconv_fwd(..., packed=, tiles=) that uses it."""
-    if not nbr.is_cuda or nbr.dtype != torch.int32 or nbr.stride(1) != 1:
-        raise RuntimeError("srfdet3d_amd: `nbr` must be a GPU int32 tensor with unit inner stride")
-    K, A_out = nbr.shape
+    K, A_out = _rulebook(nbr)
     L = _lib.lib()
     tiles = _empty((L.srf_spconv_tiles_count(A_out) + 1,), torch.int32, nbr.device)
     ws = _empty((max(L.srf_spconv_tiles_workspace_bytes(A_out), 4),), torch.uint8, nbr.device)
@@ -624,10 +639,18 @@ def spconv_fwd(feats, weight, nbr, alpha=None, beta=None, residual=None, relu=Fa
         return torch.relu(out) if relu else out
     feats = _dev(feats, "feats", torch.float32)
     weight = _dev(weight, "weight", torch.float32)
-    if not nbr.is_cuda or nbr.dtype != torch.int32 or nbr.stride(1) != 1:
-        raise RuntimeError("srfdet3d_amd: `nbr` must be a GPU int32 tensor with unit inner stride")
     K, Cin, Cout = weight.shape
-    A_out = nbr.shape[1]
+    if packed is not None and spconv_input_ok(feats.shape[0], Cin):
+        return _spconv_launch("spconv_fwd_packed", feats, packed, weight.shape, nbr, alpha, beta, residual, relu, pair_counts, rows_dev,
+                              _ptr(tiles) if spconv_tiles_wanted(Cin, Cout) else None)
+    return _spconv_launch("spconv_fwd", feats, weight, weight.shape, nbr, alpha, beta, residual, relu, pair_counts, rows_dev)
+
+
+def _spconv_launch(entry, feats, operand, wshape, nbr, alpha, beta, residual, relu, pair_counts, rows_dev, *plan):
+    """One launch of the forward entry point srf_`entry`: rulebook check, output, timing bracket, record.  `operand`: the weights in the
+    form that entry point reads; `plan`: its `tiles` argument, where it has one."""
+    K, Cin, Cout = wshape
+    A_out = _rulebook(nbr)[1]
     out = _empty((A_out, Cout), torch.float32, feats.device)
     if residual is not None:
         residual = _dev(residual, "residual", torch.float32)
@@ -637,17 +660,9 @@ def spconv_fwd(feats, weight, nbr, alpha=None, beta=None, residual=None, relu=Fa
     if timing is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    if packed is not None and 0 < feats.shape[0] * Cin * 4 < 2 ** 31:   # the packed kernels address the input with 32-bit offsets
-        check(_lib.lib().srf_spconv_fwd_packed(_ptr(feats), feats.shape[0], Cin, _ptr(packed), K, _ptr(nbr),
-                                               nbr.stride(0) if A_out > 0 else 0, A_out, Cout, _ptr(alpha), _ptr(beta),
-                                               _ptr(residual), int(bool(relu)), _ptr(out), _ptr(rows_dev),
-                                               _ptr(tiles) if spconv_tiles_wanted(Cin, Cout) else None, _stream()),
-              "spconv_fwd_packed")
-    else:
-        check(_lib.lib().srf_spconv_fwd(_ptr(feats), feats.shape[0], Cin, _ptr(weight), K, _ptr(nbr),
-                                        nbr.stride(0) if A_out > 0 else 0, A_out, Cout,
-                                        _ptr(alpha), _ptr(beta), _ptr(residual), int(bool(relu)), _ptr(out), _ptr(rows_dev),
-                                        _stream()), "spconv_fwd")
+    check(getattr(_lib.lib(), "srf_" + entry)(_ptr(feats), feats.shape[0], Cin, _ptr(operand), K, _ptr(nbr), nbr.stride(0) if A_out > 0 else 0,
+                                              A_out, Cout, _ptr(alpha), _ptr(beta), _ptr(residual), int(bool(relu)), _ptr(out), _ptr(rows_dev),
+                                              *plan, _stream()), entry)
     if timing is not None:
         ev1.record()
         timing["spconv"].append(_SpconvRecord(ev0, ev1, Cin, Cout, K, feats.shape[0], A_out, pair_counts, residual is not None))
@@ -669,27 +684,10 @@ def spconv_fwd_bf16(feats, weight, nbr, packed_bf16, alpha=None, beta=None, resi
         raise RuntimeError("srfdet3d_amd: spconv_fwd_bf16 needs pack_spconv_bf16_weights(weight); this shape has no bf16-product form")
     feats = _dev(feats, "feats", torch.float32)
     K, Cin, Cout = weight.shape
-    if not 0 < feats.shape[0] * Cin * 4 < 2 ** 31:   # 32-bit buffer offsets into the input
+    if not spconv_input_ok(feats.shape[0], Cin):
         return spconv_fwd(feats, weight, nbr, alpha, beta, residual, relu, pair_counts=pair_counts, rows_dev=rows_dev)
-    if not nbr.is_cuda or nbr.dtype != torch.int32 or nbr.stride(1) != 1:
-        raise RuntimeError("srfdet3d_amd: `nbr` must be a GPU int32 tensor with unit inner stride")
-    A_out = nbr.shape[1]
-    out = _empty((A_out, Cout), torch.float32, feats.device)
-    if residual is not None:
-        residual = _dev(residual, "residual", torch.float32)
-    timing = KERNEL_TIMING
-    if timing is not None and torch.cuda.is_current_stream_capturing():
-        timing = None
-    if timing is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(_lib.lib().srf_spconv_fwd_bf16(_ptr(feats), feats.shape[0], Cin, _ptr(packed_bf16), K, _ptr(nbr),
-                                         nbr.stride(0) if A_out > 0 else 0, A_out, Cout, _ptr(alpha), _ptr(beta), _ptr(residual),
-                                         int(bool(relu)), _ptr(out), _ptr(rows_dev), _ptr(tiles), _stream()), "spconv_fwd_bf16")
-    if timing is not None:
-        ev1.record()
-        timing["spconv"].append(_SpconvRecord(ev0, ev1, Cin, Cout, K, feats.shape[0], A_out, pair_counts, residual is not None))
-    return out
+    return _spconv_launch("spconv_fwd_bf16", feats, packed_bf16, weight.shape, nbr, alpha, beta, residual, relu, pair_counts, rows_dev,
+                          _ptr(tiles))
 
 
 class _SpconvRecord:

@@ -204,24 +204,27 @@ class _SparseConv(SparseModule):
     def _packable(self):   # (a shape rule of the library: asked once per layer, not twice per call)
         return ops.spconv_packed_supported(math.prod(self.kernel_size), self.in_channels, self.out_channels)
 
-    def index(self, level):
+    def _route(self):
+        """The kernel this call of the layer runs on -> (why not the bf16-product one: None when the active mode takes the layer, else why it
+        keeps its f32 route, "" outside the mode; whether that f32 route is the packed-weight kernel)."""
+        if mfma_dtype.active() is None:
+            why = ""
+        elif self.training or torch.is_grad_enabled():
+            why = "training mode or gradients enabled"
+        else:
+            why = ops.spconv_bf16_why_not(math.prod(self.kernel_size), self.in_channels, self.out_channels)
+        return why, why is not None and not self.training and self._packable
+
+    def index(self, level, route=None):
         """-> (Rulebook, row plan or None, output Level): what this layer needs of the coordinates alone, built on first use, kept on `level`."""
         rb, out = (level.subm(self.kernel_size), level) if self.subm else level.strided(self.indice_key, self.kernel_size, self.stride, self.padding)
-        plan = None if self.training or not self._packable or self._bf16_why_not() is None else \
-            rb.plan(self.in_channels, self.out_channels, rb.nbr.shape[0], self.subm, out.rows_dev)
+        plan = rb.plan(self.in_channels, self.out_channels, rb.nbr.shape[0], self.subm, out.rows_dev) if (route or self._route())[1] else None
         return rb, plan, out
-
-    def _bf16_why_not(self):
-        """None when the active bf16-product mode takes this layer, else why it keeps its f32 route ("" outside the mode)."""
-        if mfma_dtype.active() is None:
-            return ""
-        if self.training or torch.is_grad_enabled():
-            return "training mode or gradients enabled"
-        return ops.spconv_bf16_why_not(math.prod(self.kernel_size), self.in_channels, self.out_channels)
 
     def forward(self, x, bn=None, relu=False, residual=None):
         """conv, optionally with an eval-mode BatchNorm1d, residual rows and ReLU fused into the same kernel."""
-        rb, plan, out = self.index(x.level)
+        why, packable = route = self._route()
+        rb, plan, out = self.index(x.level, route)
         w = self.weight.view(-1, self.in_channels, self.out_channels)
         alpha = beta = None
         if bn is not None:
@@ -230,7 +233,7 @@ class _SparseConv(SparseModule):
                 beta = beta + self.bias * alpha
         elif self.bias is not None:
             alpha, beta = torch.ones_like(self.bias), self.bias
-        why, mode = self._bf16_why_not(), mfma_dtype.active()
+        mode = mfma_dtype.active()
         if mode is not None:
             mode.report(f"{self.in_channels}->{self.out_channels} k{rb.nbr.shape[0]} {'subm' if self.subm else 'strided'} @{rb.nbr.shape[1]}", why)
         if why is None:   # (an input of 2 GiB or more falls back to srf_spconv_fwd inside ops.spconv_fwd_bf16)
@@ -238,8 +241,7 @@ class _SparseConv(SparseModule):
             feats = ops.spconv_fwd_bf16(x.features, w, rb.nbr, packed_bf16, alpha, beta, residual, relu, pair_counts=rb.counts,
                                         rows_dev=out.rows_dev)
             return SparseConvTensor(feats, level=out)
-        packed = None if self.training or not self._packable else \
-            derived.get(self, "spconv", (self.weight,), lambda: ops.pack_spconv_weights(w.detach()))
+        packed = derived.get(self, "spconv", (self.weight,), lambda: ops.pack_spconv_weights(w.detach())) if packable else None
         feats = ops.spconv_fwd(x.features, w, rb.nbr, alpha, beta, residual, relu, pair_counts=rb.counts, packed=packed,
                                rows_dev=out.rows_dev, tiles=plan, subm=self.subm)
         return SparseConvTensor(feats, level=out)

@@ -11,8 +11,8 @@ its record; `--full FILE` writes the records themselves, for comparing two trees
 
 The stand-ins look at no coordinate: an eager strided conv on A rows gives `live_rows(A)` = 7 * A // 8 + 1 output rows (120 000 -> 105 001:
 the 32-channel layers of the second level stay above ops.SPCONV_ORDER_MIN_ROWS, so their order plan is reached), a static one its
-capacity, the eager size + 300.  `ops.spconv_packed_supported` is stood in for by its shape rule (csrc/spconv.hip, srf_packed_layout),
-so that no library is loaded.  `ops.densify_bev` has a stand-in too, but lies behind an `is_cuda` test that no CPU tensor passes: the
+capacity, the eager size + 300.  `ops.spconv_packed_supported` and `ops.spconv_plan_kind` are stood in for by their shape rule
+(csrc/spconv_frame.hpp, srf_spconv_shape; tests/test_spconv_shapes.py holds the stand-ins to it), so that no library is loaded.  `ops.densify_bev` has a stand-in too, but lies behind an `is_cuda` test that no CPU tensor passes: the
 recorded encoders end in `densify`.  tests/test_sparse_calls.py runs the same recorder on the tree under test and compares: same calls,
 same order, same arguments, same sharing -- with unchanged kernels, unchanged bits.
 
@@ -136,15 +136,20 @@ STANDINS = {
 
 
 def _packed_supported(K, Cin, Cout):
-    """ops.spconv_packed_supported without the library: srf_packed_layout of csrc/spconv.hip."""
+    """ops.spconv_packed_supported without the library: srf_spconv_shape of csrc/spconv_frame.hpp."""
     return 0 < K <= 27 and ((K == 27 and Cout == 32 and Cin in (16, 32)) or (Cout == 64 and Cin in (32, 64))
                             or (Cout == 128 and Cin in (64, 128)))
+
+
+def _plan_kind(K, Cin, Cout):
+    """ops.spconv_plan_kind without the library: a row order for the 32-channel layout, row ranges for the other."""
+    return (2 if Cout == 32 else 1) if _packed_supported(K, Cin, Cout) else 0
 
 
 @contextlib.contextmanager
 def recording(ops, calls):
     """Within the context the encoder's `ops` calls are appended to `calls` instead of launched."""
-    real = {name: getattr(ops, name) for name in (*STANDINS, "spconv_packed_supported")}
+    real = {name: getattr(ops, name) for name in (*STANDINS, "spconv_packed_supported", "spconv_plan_kind")}
     serial = _Serials()
 
     def standin(name):
@@ -160,7 +165,7 @@ def recording(ops, calls):
     try:
         for name in STANDINS:
             setattr(ops, name, standin(name))
-        ops.spconv_packed_supported = _packed_supported
+        ops.spconv_packed_supported, ops.spconv_plan_kind = _packed_supported, _plan_kind
         yield serial
     finally:
         for name, fn in real.items():

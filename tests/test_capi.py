@@ -63,6 +63,12 @@ def test_host_side_helpers():
     assert L.srf_spconv_order_ints(0, 27) == 0 and L.srf_spconv_order_ints(100, 28) == 0
     assert L.srf_spconv_order_build(None, 5, 27, 10, None, None, None) == -1          # row stride below the row count / no tables
     assert L.srf_spconv_order_build(None, 0, 27, 0, None, None, None) == 0            # an empty level is nothing to do
+    # the plan a layer shape takes: none, row ranges (64- / 128-channel kernel, any K), row order (32-channel kernel, K = 27)
+    assert [L.srf_spconv_plan_kind(*s) for s in ((27, 16, 16), (27, 64, 64), (3, 128, 128), (27, 32, 32), (3, 32, 32), (28, 64, 64))] == [0, 1, 1, 2, 0, 0]
+    import make_sparse_calls as gen
+    from test_spconv_shapes import GRID
+    for K, cin, cout in GRID:       # ... and the rule the call recorder stands in for it with
+        assert gen._plan_kind(K, cin, cout) == L.srf_spconv_plan_kind(K, cin, cout), (K, cin, cout)
     assert L.srf_conv_wgrad_workspace_bytes(12, 58, 100, 192, 192, 3) >= 192 * 192 * 9 * 4
     assert L.srf_conv_wgrad_workspace_bytes(12, 58, 100, 192, 192, 2) == 0            # 1x1 and 3x3 only
     assert L.srf_conv_wgrad_nhwc(None, 192, None, 192, 12, 58, 100, 192, 192, 3, None, 0, None, None) == -1

@@ -66,13 +66,3 @@ def test_the_stand_ins_are_taken_off_again():
     _recorded()
     for name in (*gen.STANDINS, "spconv_packed_supported"):
         assert getattr(ops, name).__module__ == ops.__name__, name
-
-
-def test_the_stood_in_shape_rule_is_the_librarys():
-    """`gen._packed_supported` against `ops.spconv_packed_supported` (a host call into the built library) over every layer shape in use
-    and their neighbours."""
-    from srfdet3d_amd import ops
-    for K in (1, 3, 9, 27, 28):
-        for cin in (4, 5, 16, 32, 64, 128, 256):
-            for cout in (16, 32, 64, 128, 256):
-                assert gen._packed_supported(K, cin, cout) == ops.spconv_packed_supported(K, cin, cout), (K, cin, cout)
