@@ -44,7 +44,13 @@ int srf_device_count(void);
  * for active sets whose rows are kept sorted by (b, y, x, z): one occupancy bit per cell of the level's grid plus an
  * exclusive popcount prefix per 32-bit word give "active? which row?" without a hash table, and the prefix scan of a
  * strided conv's output bitmap emits the new active set already sorted (a canonical order: independent of scheduling).
- * cell = ((b*H + y)*W + x)*D + z.  shape = host {D,H,W}.  bitmap: srf_bitmap_words() uint32; prefix: as many ints. */
+ * cell = ((b*H + y)*W + x)*D + z.  shape = host {D,H,W}.  bitmap: srf_bitmap_words() uint32; prefix: as many ints.
+ * Valid geometries are those of K4 below (the window must fit the padded grid: shape[d] + 2*pad[d] >= ksize[d]); the SubM entry
+ * wants odd kernel extents besides (SRF_EUNSUPPORTED).
+ * Overflow of a strided step (more outputs than out_capacity): nothing is written past out_capacity rows / nbr_stride columns,
+ * *num_out is the TRUE count (not clamped: the caller compares it with its capacity), the output bitmap and prefix are complete, and
+ * the rows [0, out_capacity) are the first rows of the sorted set.  A consumer that is given such a level with A = out_capacity
+ * (in_rows = out_capacity) reads every site whose rank is >= that as absent (-1). */
 size_t srf_bitmap_words(const int *shape, int batch);
 /* pair_counts may be NULL (the counts are bookkeeping, no kernel needs them).  ints a pair_counts buffer of the
  * srf_bitmap_* entry points must hold otherwise: the K counts come first, the rest is scratch
@@ -313,8 +319,13 @@ int srf_scatter_reduce(const float *feats, const int *order, const int *offsets,
  * nbr[k * nbr_stride + o] = input row feeding output row o through kernel offset k, or -1;
  * k = (kz*KH + ky)*KW + kx.  pair_counts[k] = number of valid pairs of offset k.
  * Strided convs number their output rows in first-seen order over (input row, k) ascending.
+ * Geometry (every entry point here and in the bitmap section): extents >= 1, pad >= 0, K <= 27, fewer than 2^32 - 1 cells in the
+ * input and in the output grid, and the window fits the padded grid, shape[d] + 2*pad[d] >= ksize[d], in every dimension;
+ * out_shape[d] = floor((shape[d] + 2*pad[d] - ksize[d]) / stride[d]) + 1.  Anything else is SRF_EINVAL -- a window larger than
+ * the padded grid too, whatever the stride.  Every refusal is decided on the host before anything is enqueued.
+ * Preconditions the library cannot check: rows distinct and inside the grid.
  * ------------------------------------------------------------------------------------------------------- */
-int srf_coord_table_capacity(int max_rows); /* power of two >= 2*max_rows */
+int srf_coord_table_capacity(int max_rows); /* smallest power of two >= max(1024, 2*max_rows) */
 size_t srf_coord_table_bytes(int capacity);
 int srf_coord_table_build(const int *indices /* A x 4 */, int A, const int *shape /*host[3] D,H,W*/, int batch,
                           void *table, int capacity, srf_stream_t stream);

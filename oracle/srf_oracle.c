@@ -289,7 +289,11 @@ int orc_rulebook_strided(const int *indices, int A, const int *shape, const int 
 {
     int K = ksize[0] * ksize[1] * ksize[2];
     int oshape[3];
-    for (int d = 0; d < 3; ++d) oshape[d] = (shape[d] + 2 * pad[d] - ksize[d]) / stride[d] + 1;
+    for (int d = 0; d < 3; ++d) {
+        /* a window larger than the padded grid has no output: C's division would turn (-1) / 2 + 1 into 1 */
+        if (stride[d] <= 0 || shape[d] + 2 * pad[d] < ksize[d]) return ORC_EINVAL;
+        oshape[d] = (shape[d] + 2 * pad[d] - ksize[d]) / stride[d] + 1;
+    }
     orc_map m;
     if (map_init(&m, (uint64_t)cap_out)) return ORC_ENOMEM;
     for (size_t t = 0; t < (size_t)K * cap_out; ++t) nbr[t] = -1;

@@ -155,9 +155,13 @@ __global__ __launch_bounds__(256) void srf_strided_fill_k(int A, int K, const in
     if (threadIdx.x < K && hist[threadIdx.x]) atomicAdd(&pair_counts[threadIdx.x], hist[threadIdx.x]);
 }
 
+// A geometry is valid when every extent is >= 1, the window fits the padded grid (shape + 2*pad >= ksize) in every dimension,
+// K <= 27 and both grids have fewer than 2^32 - 1 cells.  The window rule is its own test: C's division truncates, so for
+// shape + 2*pad - ksize = -1 and a stride >= 2 the extent formula alone gives 0 + 1 = 1 output that does not exist.
 static bool srf_fill_conv_geom(ConvGeom &g, const int *shape, const int *ksize, const int *stride, const int *pad,
                                int batch)
 {
+    if (!shape || !ksize) return false;
     g.K = 1;
     unsigned long long vol = (unsigned long long)(batch > 0 ? batch : 1), ovol = vol;
     for (int d = 0; d < 3; ++d) {
@@ -165,9 +169,10 @@ static bool srf_fill_conv_geom(ConvGeom &g, const int *shape, const int *ksize, 
         g.ks[d] = ksize[d];
         g.st[d] = stride ? stride[d] : 1;
         g.pd[d] = pad ? pad[d] : ksize[d] / 2;
-        if (shape[d] <= 0 || ksize[d] <= 0 || g.st[d] <= 0 || g.pd[d] < 0) return false;
-        g.oshape[d] = (shape[d] + 2 * g.pd[d] - ksize[d]) / g.st[d] + 1;
-        if (g.oshape[d] <= 0) return false;
+        if (shape[d] <= 0 || ksize[d] <= 0 || ksize[d] > SRF_MAX_K || g.st[d] <= 0 || g.pd[d] < 0) return false;
+        const long long span = (long long)shape[d] + 2LL * g.pd[d] - ksize[d];
+        if (span < 0 || span / g.st[d] + 1 > 0x7FFFFFFFLL) return false;
+        g.oshape[d] = (int)(span / g.st[d]) + 1;
         g.K *= ksize[d];
         vol *= (unsigned long long)shape[d];
         ovol *= (unsigned long long)g.oshape[d];
@@ -187,14 +192,14 @@ extern "C" size_t srf_coord_table_bytes(int capacity) { return (size_t)capacity 
 extern "C" int srf_coord_table_build(const int *indices, int A, const int *shape, int batch, void *table, int capacity,
                                      srf_stream_t stream)
 {
-    if (A < 0 || !shape || !table || capacity < 1024 || (capacity & (capacity - 1)) || capacity < 2 * A) return SRF_EINVAL;
+    if (A < 0 || !shape || !table || capacity < 1024 || (capacity & (capacity - 1)) || capacity / 2 < A) return SRF_EINVAL;
     const int one[3] = {1, 1, 1};
     ConvGeom g;
     if (!srf_fill_conv_geom(g, shape, one, one, nullptr, batch)) return SRF_EINVAL;
+    if (A > 0 && !indices) return SRF_EINVAL;  // every refusal comes before the first enqueued byte
     hipStream_t st = (hipStream_t)stream;
     SRF_HIP_TRY(srf_fill_bytes(table, 0xFF, (size_t)capacity * 8, st));
     if (A == 0) return SRF_OK;
-    if (!indices) return SRF_EINVAL;
     uint32_t *keys = (uint32_t *)table;
     int *rows = (int *)(keys + capacity);
     hipLaunchKernelGGL(srf_table_build_k, dim3(srf_ceil_div(A, 256)), dim3(256), 0, st, (const int4 *)indices, A, g, keys,
@@ -206,14 +211,15 @@ extern "C" int srf_coord_table_build(const int *indices, int A, const int *shape
 extern "C" int srf_rulebook_subm(const int *indices, int A, const int *shape, const int *ksize, const void *table,
                                  int capacity, int *nbr, int *pair_counts, srf_stream_t stream)
 {
-    if (A < 0 || !shape || !ksize || !table || !pair_counts || (capacity & (capacity - 1))) return SRF_EINVAL;
+    if (A < 0 || !shape || !ksize || !table || !pair_counts) return SRF_EINVAL;
+    if (capacity < 1024 || (capacity & (capacity - 1)) || capacity / 2 < A) return SRF_EINVAL;  // no table of these rows is smaller
     ConvGeom g;
     const int one[3] = {1, 1, 1};
     if (!srf_fill_conv_geom(g, shape, ksize, one, nullptr, 1)) return SRF_EINVAL;
+    if (A > 0 && (!indices || !nbr)) return SRF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     SRF_HIP_TRY(srf_fill_bytes(pair_counts, 0, sizeof(int) * g.K, st));
     if (A == 0) return SRF_OK;
-    if (!indices || !nbr) return SRF_EINVAL;
     const uint32_t *keys = (const uint32_t *)table;
     const int *rows = (const int *)(keys + capacity);
     hipLaunchKernelGGL(srf_subm_k, dim3(srf_ceil_div((long long)A * g.K, 256)), dim3(256), 0, st, (const int4 *)indices, A,
@@ -271,6 +277,8 @@ extern "C" int srf_rulebook_strided_outputs(const int *indices, int A, const int
     size_t off_min, off_partial;
     size_t need = srf_strided_ws_layout(A, g.K, out_capacity, &off_min, &off_partial);
     if (workspace_bytes < need) return SRF_EWORKSPACE;
+    const long long nc = (long long)A * g.K;
+    if (nc > 0x7F000000 || (A > 0 && (!indices || !out_indices))) return SRF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     uint32_t *okeys = (uint32_t *)out_table;
     int *orows = (int *)(okeys + out_capacity);
@@ -283,9 +291,6 @@ extern "C" int srf_rulebook_strided_outputs(const int *indices, int A, const int
         SRF_HIP_TRY(srf_fill_bytes(num_out, 0, sizeof(int), st));
         return SRF_OK;
     }
-    if (!indices || !out_indices) return SRF_EINVAL;
-    const long long nc = (long long)A * g.K;
-    if (nc > 0x7F000000) return SRF_EINVAL;
     hipLaunchKernelGGL(srf_strided_insert_k, dim3(srf_ceil_div(nc, 256)), dim3(256), 0, st, (const int4 *)indices, A, g,
                        okeys, (uint32_t)(out_capacity - 1), mincand, cand_slot);
     SRF_LAUNCH_CHECK();
@@ -299,12 +304,15 @@ extern "C" int srf_rulebook_strided_pairs(int A, const int *ksize, const void *o
                                           srf_stream_t stream)
 {
     if (A < 0 || !ksize || !out_table || !workspace || !pair_counts || num_out_host < 0) return SRF_EINVAL;
+    for (int d = 0; d < 3; ++d)
+        if (ksize[d] <= 0 || ksize[d] > SRF_MAX_K) return SRF_EINVAL;
     const int K = ksize[0] * ksize[1] * ksize[2];
-    if (K <= 0 || K > SRF_MAX_K) return SRF_EINVAL;
+    if (K > SRF_MAX_K) return SRF_EINVAL;
+    if (out_capacity < 1024 || (out_capacity & (out_capacity - 1))) return SRF_EINVAL;
+    if (A > 0 && num_out_host > 0 && !nbr) return SRF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     SRF_HIP_TRY(srf_fill_bytes(pair_counts, 0, sizeof(int) * K, st));
     if (A == 0 || num_out_host == 0) return SRF_OK;
-    if (!nbr) return SRF_EINVAL;
     SRF_HIP_TRY(srf_fill_bytes(nbr, 0xFF, (size_t)K * num_out_host * 4, st));
     const int *orows = (const int *)((const uint32_t *)out_table + out_capacity);
     const int *cand_slot = (const int *)workspace;
@@ -549,6 +557,7 @@ static int srf_bitmap_build_impl(const int *indices, int A, const int *shape, in
     ConvGeom g;
     const int one[3] = {1, 1, 1};
     if (!srf_fill_conv_geom(g, shape, one, one, nullptr, batch)) return SRF_EINVAL;
+    if (A > 0 && !indices) return SRF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     SrfFillRegions fill = {};
     fill.ptr[0] = (uint32_t *)bitmap, fill.value[0] = 0u, fill.nwords[0] = words;
@@ -557,11 +566,9 @@ static int srf_bitmap_build_impl(const int *indices, int A, const int *shape, in
         fill.ptr[2] = (uint32_t *)sorted_indices, fill.value[2] = 0xFFFFFFFFu, fill.nwords[2] = (size_t)A * 4;
     }
     SRF_HIP_TRY(srf_fill_regions(fill, st));
-    if (A > 0) {
-        if (!indices) return SRF_EINVAL;
+    if (A > 0)
         hipLaunchKernelGGL(srf_bm_mark_k, dim3(srf_ceil_div(A, 256)), dim3(256), 0, st, (const int4 *)indices, A, g,
                            (uint32_t *)bitmap);
-    }
     int rc = srf_device_scan((int)words, BmPop{(const uint32_t *)bitmap}, BmPrefix{prefix}, (int *)workspace, nullptr, -1, st);
     if (rc) return rc;
     if (A > 0 && order && sorted_indices)
@@ -592,10 +599,10 @@ extern "C" int srf_bitmap_rulebook_subm(const int *sorted_indices, int A, const 
     if (A < 0 || !shape || !ksize || !srf_fill_conv_geom(g, shape, ksize, nullptr, nullptr, batch)) return SRF_EINVAL;
     for (int d = 0; d < 3; ++d)
         if (!(ksize[d] & 1)) return SRF_EUNSUPPORTED;
+    if (A > 0 && (!sorted_indices || !nbr || !bitmap || !prefix)) return SRF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (pair_counts) SRF_HIP_TRY(srf_fill_bytes(pair_counts, 0, sizeof(int) * SRF_MAX_K * (SRF_BM_REPLICAS + 1), st));
     if (A == 0) return SRF_OK;
-    if (!sorted_indices || !nbr || !bitmap || !prefix) return SRF_EINVAL;
     hipLaunchKernelGGL(srf_bm_subm_k, dim3(srf_ceil_div(A, 256), g.K), dim3(256), 0, st, (const int4 *)sorted_indices, A, g,
                        (const uint32_t *)bitmap, prefix, nbr, pair_counts ? pair_counts + SRF_MAX_K : nullptr);
     if (pair_counts)
@@ -616,17 +623,16 @@ static int srf_bitmap_strided_outputs_impl(const int *indices, int A, const int 
     const size_t words = srf_bitmap_words(g.oshape, batch);
     if (words == 0) return SRF_EINVAL;
     if (workspace_bytes < srf_bitmap_workspace_bytes(words)) return SRF_EWORKSPACE;
+    if (A > 0 && (!indices || !out_indices)) return SRF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     SrfFillRegions fill = {};
     fill.ptr[0] = (uint32_t *)out_bitmap, fill.value[0] = 0u, fill.nwords[0] = words;
     if (fill_tail && out_indices && out_capacity > 0)  // rows past the output count stay (-1, -1, -1, -1): same launch as the clear
         fill.ptr[1] = (uint32_t *)out_indices, fill.value[1] = 0xFFFFFFFFu, fill.nwords[1] = (size_t)out_capacity * 4;
     SRF_HIP_TRY(srf_fill_regions(fill, st));
-    if (A > 0) {
-        if (!indices || !out_indices) return SRF_EINVAL;
+    if (A > 0)
         hipLaunchKernelGGL(srf_bm_strided_mark_k, dim3(srf_ceil_div(A, 256), g.K), dim3(256), 0, st, (const int4 *)indices, A, g,
                            (uint32_t *)out_bitmap);
-    }
     int rc = srf_device_scan((int)words, BmPop{(const uint32_t *)out_bitmap}, BmPrefix{out_prefix}, (int *)workspace, num_out, -1, st);
     if (rc) return rc;
     if (A > 0)
@@ -663,10 +669,10 @@ extern "C" int srf_bitmap_strided_pairs(const int *out_indices, const int *num_o
     ConvGeom g;
     if (max_out < 0 || nbr_stride < max_out || in_rows < 0 || !shape || !ksize || !stride || !pad || !num_out) return SRF_EINVAL;
     if (!srf_fill_conv_geom(g, shape, ksize, stride, pad, batch)) return SRF_EINVAL;
+    if (max_out > 0 && (!out_indices || !nbr || !in_bitmap || !in_prefix)) return SRF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (pair_counts) SRF_HIP_TRY(srf_fill_bytes(pair_counts, 0, sizeof(int) * SRF_MAX_K * (SRF_BM_REPLICAS + 1), st));
     if (max_out == 0) return SRF_OK;
-    if (!out_indices || !nbr || !in_bitmap || !in_prefix) return SRF_EINVAL;
     hipLaunchKernelGGL(srf_bm_strided_pairs_k, dim3(srf_ceil_div(max_out, 256), g.K), dim3(256), 0, st, (const int4 *)out_indices,
                        num_out, nbr_stride, in_rows, fill_tail, g, (const uint32_t *)in_bitmap, in_prefix, nbr,
                        pair_counts ? pair_counts + SRF_MAX_K : nullptr);
