@@ -985,6 +985,31 @@ int srf_ota_assign(const float *pred_boxes, const float *pred_logits, const floa
                    float gamma, float eps, float center_radius, int candidate_topk, int num_heads, int *count, int *pred_idx, int *gt_idx,
                    int *status, void *workspace, size_t workspace_bytes, srf_stream_t stream);
 
+/* The losses of the decoder's deep supervision on the assignment srf_ota_assign made: sigmoid focal loss and weighted L1 loss (FocalLoss /
+ * L1Loss, reduction "sum") of all S decoder stages and B samples of a step, values and gradients in one pass (csrc/setloss.hip, whose header
+ * holds the exact definition; tests/set_loss_ref.py is the same text in numpy).
+ *
+ * pred_logits (S, B, P, C); pred_boxes (S, B, P, D) normalised boxes; count (S, B), pred_idx / gt_idx (S, B, P) as srf_ota_assign writes
+ * them (count is clamped into [0, P]; a slot whose pred_idx is outside [0, P) or whose gt_idx is outside [0, Gpad) is skipped); gt_boxes
+ * (B, Gpad, Dg) gravity centre [x, y, z, dx, dy, dz, yaw, (vx, vy)], padded; gt_labels (B, Gpad) int32, a label outside [0, C) is
+ * background; code_weights (Dw) on the device; num (S, 2) on the HOST: the divisor of the class loss and of the box loss of each stage;
+ * alpha / gamma / w_cls = loss_weight of the focal loss, w_box = loss_weight of the L1 loss.
+ * Outputs, every element written: loss (S, 2) = [class loss, box loss] per stage after nan_to_num; grad_logits (S, B, P, C) and grad_boxes
+ * (S, B, P, D) = the derivatives of loss[s, 0] and loss[s, 1] by the stage's own predictions.  A stage whose loss value is not finite
+ * gets the nan_to_num value and all-zero gradients for that loss.
+ * Two launches per 64 stages (element pass with per-workgroup float64 partial sums, fixed-order reduction), no float atomics: two calls
+ * give the same bytes.  workspace: srf_set_loss_workspace_bytes(S, B, P, C, D).
+ *
+ * Checked before any HIP call, in this order: non-positive S, B, P, C, D, Dw, Gpad or Dg, or a num[s][k] that is <= 0 or not finite:
+ * SRF_EINVAL; null pointers: SRF_EINVAL; limits (P <= 4096; Gpad <= 512; S * B <= 65535; C <= 64; (D, Dw, Dg) one of (8, 8, 7), (10, 8, 7),
+ * (10, 8, 9), (10, 10, 9); gamma >= 1 and finite; alpha in [0, 1]; every tensor below 2^31 bytes): SRF_EUNSUPPORTED; workspace too small:
+ * SRF_EWORKSPACE.  The workspace size is 0 outside the limits. */
+size_t srf_set_loss_workspace_bytes(int S, int B, int P, int C, int D);
+int srf_set_loss(const float *pred_logits, const float *pred_boxes, const int *count, const int *pred_idx, const int *gt_idx,
+                 const float *gt_boxes, const int *gt_labels, const float *code_weights, const float *num, int S, int B, int P, int C, int D,
+                 int Dw, int Gpad, int Dg, float alpha, float gamma, float w_cls, float w_box, float *loss, float *grad_logits,
+                 float *grad_boxes, void *workspace, size_t workspace_bytes, srf_stream_t stream);
+
 size_t srf_nms_rotated_workspace_bytes(int n);
 int srf_nms_rotated(const float *boxes, int n, float iou_threshold, int *keep, void *workspace, size_t workspace_bytes,
                     srf_stream_t stream);

@@ -213,6 +213,9 @@ SIGNATURES = {
     "srf_ota_match": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "srf_ota_assign": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                c_float, c_float, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "srf_set_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "srf_set_loss": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _HF, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                             c_float, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "srf_box_rois": (c_int, [_P, c_int, c_int, c_int, _HF, _HF, c_int, _P, _P, c_int, _P, _P]),
 }
 

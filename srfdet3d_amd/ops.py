@@ -2561,3 +2561,61 @@ def ota_match(cost, iou, n_gt, head_idx, candidate_topk, num_heads):
     check(L.srf_ota_match(_ptr(cost), _ptr(iou), _ptr(n_gt), _ptr(head_idx), S, B, P, G, candidate_topk, num_heads, _ptr(both[0]), _ptr(pred_idx), _ptr(gt_idx), _ptr(both[1]),
                           _ptr(ws), ws_bytes, _stream()), "ota_match")
     return both[0], pred_idx, gt_idx, both[1]
+
+
+# ------------------------------------------------------------------------------------------------------- decoder losses of a step
+SET_LOSS_MAX_P, SET_LOSS_MAX_G, SET_LOSS_MAX_C, SET_LOSS_MAX_PAIRS = 4096, 512, 64, 65535
+SET_LOSS_BOX_COLUMNS = ((8, 8, 7), (10, 8, 7), (10, 8, 9), (10, 10, 9))        # (D, Dw, Dg)
+
+
+def set_loss_enabled():
+    """SRF_SET_LOSS=1 sends the focal and L1 losses of `SRFDetHead.loss_ota` through `set_loss` (csrc/setloss.hip).  Off by default: the
+    default route's losses are held bit for bit to the torch operators, and another summation order cannot keep those bits.  Read at every
+    call."""
+    return os.environ.get("SRF_SET_LOSS", "0") == "1"
+
+
+def set_loss_ok(S, B, P, C, D, Dw, Gpad, Dg, gamma=2.0, alpha=0.25):
+    """The arguments `srf_set_loss` takes (csrc/setloss.hip, the SRF_EINVAL and SRF_EUNSUPPORTED lines of the entry point): at most 4096
+    predictions, 512 padded ground-truth boxes, 65535 (stage, sample) pairs and 64 classes, the box columns (D, Dw, Dg) one of
+    `SET_LOSS_BOX_COLUMNS`, gamma >= 1 and finite, alpha in [0, 1], every tensor inside a 32-bit byte range."""
+    return (S >= 1 and B >= 1 and 1 <= P <= SET_LOSS_MAX_P and 1 <= Gpad <= SET_LOSS_MAX_G and S * B <= SET_LOSS_MAX_PAIRS
+            and 1 <= C <= SET_LOSS_MAX_C and (D, Dw, Dg) in SET_LOSS_BOX_COLUMNS and 1.0 <= gamma < float("inf") and 0.0 <= alpha <= 1.0
+            and below_2gb(S * B * P, C) and below_2gb(S * B * P, D) and below_2gb(B * Gpad, Dg))
+
+
+def set_loss(pred_logits, pred_boxes, count, pred_idx, gt_idx, gt_boxes, gt_labels, code_weights, num, alpha, gamma, w_cls, w_box):
+    """The sigmoid focal loss and the weighted L1 loss of S decoder stages x B samples on the assignment `ota_assign` returned, values and
+    gradients in one call (`srf_set_loss`; definition in csrc/setloss.hip and, as numpy, in tests/set_loss_ref.py).  pred_logits (S, B, P, C);
+    pred_boxes (S, B, P, 8 | 10); count (S, B), pred_idx / gt_idx (S, B, P) int32; gt_boxes (B, Gpad, 7 | 9) gravity-centre boxes, padded;
+    gt_labels (B, Gpad) int32; code_weights (8 | 10) on the device; num: S pairs of host numbers, the divisors of the class and of the box
+    loss.  -> loss (S, 2), grad_logits (S, B, P, C), grad_boxes (S, B, P, D), all float32.  Nothing is read back here."""
+    pred_logits, pred_boxes = _dev(pred_logits, "pred_logits", torch.float32), _dev(pred_boxes, "pred_boxes", torch.float32)
+    count, pred_idx, gt_idx = _dev(count, "count", torch.int32), _dev(pred_idx, "pred_idx", torch.int32), _dev(gt_idx, "gt_idx", torch.int32)
+    gt_boxes, gt_labels = _dev(gt_boxes, "gt_boxes", torch.float32), _dev(gt_labels, "gt_labels", torch.int32)
+    code_weights = _dev(code_weights, "code_weights", torch.float32)
+    if pred_logits.dim() != 4 or pred_boxes.dim() != 4 or pred_logits.shape[:3] != pred_boxes.shape[:3]:
+        raise ValueError("set_loss: pred_logits (S, B, P, C) and pred_boxes (S, B, P, D)")
+    S, B, P, C = pred_logits.shape
+    D, Dw = pred_boxes.shape[3], code_weights.numel()
+    if tuple(count.shape) != (S, B) or tuple(pred_idx.shape) != (S, B, P) or tuple(gt_idx.shape) != (S, B, P):
+        raise ValueError("set_loss: count (S, B), pred_idx and gt_idx (S, B, P)")
+    if gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or tuple(gt_labels.shape) != tuple(gt_boxes.shape[:2]) or code_weights.dim() != 1:
+        raise ValueError("set_loss: gt_boxes (B, Gpad, Dg), gt_labels (B, Gpad) and code_weights (Dw)")
+    G, Dg = gt_boxes.shape[1], gt_boxes.shape[2]
+    num = [float(v) for pair in num for v in pair]
+    if len(num) != 2 * S or not all(0.0 < v < float("inf") for v in num):
+        raise ValueError("set_loss: num is S pairs of positive finite numbers")
+    if not set_loss_ok(S, B, P, C, D, Dw, G, Dg, gamma, alpha):
+        raise ValueError(f"set_loss: S {S} B {B} P {P} C {C} D {D} Dw {Dw} Gpad {G} Dg {Dg} gamma {gamma} alpha {alpha} is outside the limits "
+                         "of srf_set_loss (ops.set_loss_ok)")
+    dev = pred_logits.device
+    loss = _empty((S, 2), torch.float32, dev)
+    grad_logits, grad_boxes = _empty((S, B, P, C), torch.float32, dev), _empty((S, B, P, D), torch.float32, dev)
+    L = _lib.lib()
+    ws_bytes = L.srf_set_loss_workspace_bytes(S, B, P, C, D)
+    ws = _empty((max(ws_bytes, 1),), torch.uint8, dev)
+    check(L.srf_set_loss(_ptr(pred_logits), _ptr(pred_boxes), _ptr(count), _ptr(pred_idx), _ptr(gt_idx), _ptr(gt_boxes), _ptr(gt_labels),
+                         _ptr(code_weights), hf(num), S, B, P, C, D, Dw, G, Dg, alpha, gamma, w_cls, w_box, _ptr(loss), _ptr(grad_logits),
+                         _ptr(grad_boxes), _ptr(ws), ws_bytes, _stream()), "set_loss")
+    return loss, grad_logits, grad_boxes

@@ -881,21 +881,39 @@ class SRFDetHead(BaseModule):
         An assigner with `assign_layers` (OTAssignerSRFDet) assigns all layers in one call whose own read-back -- the matched counts --
         is the only device-to-host copy of the step in one process: the counts are then host numbers, and the losses select their rows by
         the index tensors that call returns.  Under torch.distributed the all-reduce of the counts brings a second one."""
-        import torch.distributed as dist
-        from .training import reduce_mean
         dev = gt_labels_list[0].device
         gts = [torch.cat((g.gravity_center, g.tensor[:, 3:]), dim=1).to(dev) for g in gt_bboxes_list]
-        losses = {}
         layers = [(outputs, self.num_heads, "")] + [(aux, i + 1, f"s.{i}.") for i, aux in enumerate(outputs.get("aux_outputs", []))]
         if hasattr(self.assigner, "assign_layers"):
             assigned = self.assigner.assign_layers([(out, head_idx) for out, head_idx, _ in layers], gts, gt_labels_list)
         else:
             assigned = [self.assigner(out, gts, gt_labels_list, head_idx) for out, head_idx, _ in layers]
+        return self.losses_of_assigned(layers, assigned, gts, gt_labels_list)
+
+    def losses_of_assigned(self, layers, assigned, gts, gt_labels_list):
+        """The loss stage of `loss_ota` from finished assignments on.  layers: [(outputs, head_idx, key prefix)]; assigned: per layer, per
+        sample the assigner's result; gts: the samples' gravity-centre boxes.  With SRF_SET_LOSS=1 and everything `training.set_loss_route`
+        asks for, all losses of the step and their gradients are ONE call of `ops.set_loss` (csrc/setloss.hip) under one autograd node;
+        everything else goes loss by loss through `loss_classification` / `loss_boxes`.  Same keys in the same order on both routes."""
+        import torch.distributed as dist
+        from .training import SetLoss, reduce_mean, set_loss_route
+        dev = gt_labels_list[0].device
+        losses = {}
         local = [float(sum(int(a[1].numel()) for a in idx)) for idx in assigned]          # host-known: no synchronisation
         if dist.is_available() and dist.is_initialized():
             reduced = reduce_mean(torch.tensor(local, dtype=torch.float32, device=dev)).tolist()   # one collective, one read-back
         else:
             reduced = local                                                               # reduce_mean of one process: the counts themselves
+        outs = [out for out, _, _ in layers]
+        if set_loss_route(self, outs, assigned, gts):
+            num = [(max(n_mean if self.sync_cls_avg_factor else n_local, 1.0), max(n_mean, 1.0)) for n_local, n_mean in zip(local, reduced)]
+            scalars = dict(alpha=float(self.loss_cls.alpha), gamma=float(self.loss_cls.gamma), w_cls=float(self.loss_cls.loss_weight),
+                           w_box=float(self.loss_bbox.loss_weight))
+            values = SetLoss.apply(assigned.raw, num, scalars, self.code_weights.detach(), *[o["pred_logits"] for o in outs],
+                                   *[o["pred_boxes"] for o in outs]).view(-1).unbind(0)
+            for s, (_, _, prefix) in enumerate(layers):
+                losses[prefix + "loss_cls"], losses[prefix + "loss_bbox"] = values[2 * s], values[2 * s + 1]
+            return losses
         for (out, _, prefix), idx, n_local, n_mean in zip(layers, assigned, local, reduced):
             n_cls = n_mean if self.sync_cls_avg_factor else n_local
             losses[prefix + "loss_cls"] = self.loss_classification(out, gt_labels_list, idx, num=max(n_cls, 1.0))

@@ -2,6 +2,8 @@
 the dynamic-k OTA label assignment and the frozen-LiDAR-branch helper.  The losses and match costs are plain torch.  The label assignment
 on the GPU is HIP: all decoder stages and samples of a step in one call (`ops.ota_assign`, csrc/ota.hip; SRF_OTA=0 switches it off), with
 the torch restatement kept as the route of everything that call does not take; so is the rotated BEV IoU under `bbox_overlaps_3d`.
+With SRF_SET_LOSS=1 the focal and L1 losses of all decoder stages are one call as well (`SetLoss` around `ops.set_loss`, csrc/setloss.hip;
+`set_loss_route` says when).
 
 Mirrors: OTAssignerSRFDet  mmdet3d_plugin/core/bbox/assigners/ota_srfdet.py:18-327
          BBox3DL1Cost / IoU3DCost  mmdet3d_plugin/core/bbox/match_costs/match_cost.py:5-36
@@ -191,6 +193,13 @@ class Assigned(tuple):
         return self
 
 
+class AssignedLayers(list):
+    """What `OTAssignerSRFDet.assign_layers` returns: the per-stage lists of per-sample `Assigned`, and on the kernel route `raw` = the
+    tensors of the one `ops.ota_assign` call as they came back -- count (S, B), pred_idx / gt_idx (S, B, P) int32 -- with the padded ground
+    truth beside them: gt_boxes (B, Gpad, 7 | 9), gt_labels (B, Gpad) int32.  `raw` is None on the torch route."""
+    raw = None
+
+
 @BBOX_ASSIGNERS.register_module()
 class OTAssignerSRFDet(nn.Module):
     """1-to-k dynamic matching of predictions to ground truth (ota_srfdet.py:18-327).  On the GPU the whole assignment of a step -- every
@@ -251,18 +260,24 @@ class OTAssignerSRFDet(nn.Module):
         On the kernel route (`kernel_route`) this is ONE call of `ops.ota_assign` and ONE device-to-host copy (the matched counts and the
         status words); a (stage, sample) pair whose repair loop hit the kernel's cap is assigned again by the torch route."""
         if not self.kernel_route(layers, gts, labels):
-            return [[self._single_torch(out["pred_boxes"][i], out["pred_logits"][i], gts[i], labels[i], head_idx) for i in range(len(gts))]
-                    for out, head_idx in layers]
+            return AssignedLayers([self._single_torch(out["pred_boxes"][i], out["pred_logits"][i], gts[i], labels[i], head_idx)
+                                   for i in range(len(gts))] for out, head_idx in layers)
         dev = gts[0].device
         S, B, P, G = len(layers), len(gts), layers[0][0]["pred_boxes"].shape[1], self._gpad(gts)
         boxes = torch.stack([out["pred_boxes"].detach() for out, _ in layers])
         logits = torch.stack([out["pred_logits"].detach() for out, _ in layers])
         ns = [int(g.shape[0]) for g in gts]                                  # host-known: no synchronisation
         gt_pad, lab_pad = torch.zeros((B, G, 7), dtype=torch.float32, device=dev), torch.zeros((B, G), dtype=torch.int32, device=dev)
+        # the ground truth with all its columns (velocities) for `ops.set_loss`, only where that route is on and the boxes have more than 7
+        Dg = int(gts[0].shape[1])
+        wide = ops.set_loss_enabled() and Dg > 7 and all(int(g.shape[1]) == Dg for g in gts)
+        gt_wide = torch.zeros((B, G, Dg), dtype=torch.float32, device=dev) if wide else None
         for b, (g, l) in enumerate(zip(gts, labels)):
             if ns[b]:
                 gt_pad[b, :ns[b]] = g[:, :7]
                 lab_pad[b, :ns[b]] = l
+                if wide:
+                    gt_wide[b, :ns[b]] = g
         # the box counts and head indices go up in one copy from pinned memory: a copy from pageable memory waits for the stream
         meta = torch.tensor(ns + [h for _, h in layers], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
         n_gt, heads = meta[:B], meta[B:]
@@ -276,7 +291,8 @@ class OTAssignerSRFDet(nn.Module):
         fg_all.index_fill_(0, flat.view(-1), True)
         fg_all = fg_all[:S * B * P].view(S, B, P)
         rows_all, j_all = pred_idx.long(), gt_idx.long()
-        res = []
+        res = AssignedLayers()
+        res.raw = dict(count=count, pred_idx=pred_idx, gt_idx=gt_idx, gt_boxes=gt_wide if wide else gt_pad, gt_labels=lab_pad)
         for s, (out, head_idx) in enumerate(layers):
             stage = []
             for b in range(B):
@@ -344,6 +360,55 @@ class OTAssignerSRFDet(nn.Module):
                 match[multi, best] = 1.0
         fg = match.sum(1) > 0
         return fg, match[fg].argmax(1)
+
+
+def set_loss_route(head, outs, assigned, gts):
+    """Whether `SRFDetHead.loss_ota` computes the losses of the whole step in the one call of `ops.set_loss` (csrc/setloss.hip):
+    SRF_SET_LOSS is 1; the assignment came from `ops.ota_assign` (`assigned.raw`) and every (stage, sample) pair carries `rows`, so none
+    fell back on a status word; the losses are exactly FocalLoss and L1Loss with reduction "sum"; every prediction is a float32 GPU tensor
+    of one shape; and the shape is inside `ops.set_loss_ok`.  outs: the stages' output dicts; gts: the samples' (n, 7 | 9) boxes."""
+    raw = getattr(assigned, "raw", None)
+    if not ops.set_loss_enabled() or raw is None or not outs or len(assigned) != len(outs):
+        return False
+    if not all(getattr(a, "rows", None) is not None for stage in assigned for a in stage):
+        return False
+    lc, lb = getattr(head, "loss_cls", None), getattr(head, "loss_bbox", None)
+    if type(lc) is not FocalLoss or type(lb) is not L1Loss or lc.reduction != "sum" or lb.reduction != "sum":
+        return False
+    logits, boxes = outs[0]["pred_logits"], outs[0]["pred_boxes"]
+    for out in outs:
+        l, b = out["pred_logits"], out["pred_boxes"]
+        if not (l.is_cuda and b.is_cuda and l.dtype == b.dtype == torch.float32 and l.dim() == 3 and l.shape == logits.shape
+                and b.shape == boxes.shape and b.shape[:2] == l.shape[:2]):
+            return False
+    cw, gt = head.code_weights, raw["gt_boxes"]
+    if not (cw.is_cuda and cw.dtype == torch.float32 and cw.dim() == 1) or len(gts) != logits.shape[0]:
+        return False
+    if any(int(g.shape[1]) != int(gt.shape[2]) for g in gts):          # the losses read every column the head's `gts` have
+        return False
+    return ops.set_loss_ok(len(outs), logits.shape[0], logits.shape[1], logits.shape[2], boxes.shape[2], cw.numel(), gt.shape[1], gt.shape[2],
+                           float(lc.gamma), float(lc.alpha))
+
+
+class SetLoss(torch.autograd.Function):
+    """The focal and L1 losses of S decoder stages as one autograd node around `ops.set_loss`: forward(raw, num, scalars, code_weights,
+    S logits..., S boxes...) stacks the stages, makes the one call and keeps the two gradient tensors; -> loss (S, 2).  backward scales the
+    kept gradients by the incoming (S, 2) gradient -- two element-wise launches -- and hands every stage its view."""
+
+    @staticmethod
+    def forward(ctx, raw, num, scalars, code_weights, *preds):
+        S = len(preds) // 2
+        logits, boxes = torch.stack([p.detach() for p in preds[:S]]), torch.stack([p.detach() for p in preds[S:]])
+        loss, ctx.grad_logits, ctx.grad_boxes = ops.set_loss(logits, boxes, raw["count"], raw["pred_idx"], raw["gt_idx"], raw["gt_boxes"],
+                                                             raw["gt_labels"], code_weights, num, **scalars)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        S = grad.shape[0]
+        gl = ctx.grad_logits * grad[:, 0].view(S, 1, 1, 1)
+        gb = ctx.grad_boxes * grad[:, 1].view(S, 1, 1, 1)
+        return (None, None, None, None) + gl.unbind(0) + gb.unbind(0)
 
 
 def freeze_lidar_components(model):

@@ -47,6 +47,9 @@ def main():
     ap.add_argument("--ota-ab", type=int, default=0, metavar="R",
                     help="after the timed iterations, R more alternated pairs of --iters iterations with the label assignment on its HIP "
                          "route and on the torch route (SRF_OTA unset / 0, read at every call): iterations/s of each, one model, one process")
+    ap.add_argument("--set-loss-ab", type=int, default=0, metavar="R",
+                    help="the same alternation for the focal / L1 losses of the decoder stages: SRF_SET_LOSS=1 (one call of srf_set_loss per step) "
+                         "against SRF_SET_LOSS=0 (the torch operators, the default)")
     a = ap.parse_args()
     rank, local, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(local)
@@ -159,16 +162,18 @@ def main():
                                                        "(they include queueing behind earlier buckets and overlap one another: an UPPER bound, as is the "
                                                        "first-start-to-last-end span); the buckets overlap with backward (world == 1: no collective)"),
                               loss_scalar_allreduces_per_step=1 if world > 1 else 0)))
-    if a.ota_ab:
-        keep = os.environ.get("SRF_OTA")
-        its = {"hip": [], "torch": []}
-        fwd_ms = {"hip": [], "torch": []}
-        for _ in range(a.ota_ab):
-            for name in ("hip", "torch"):
-                if name == "hip":
-                    os.environ.pop("SRF_OTA", None)
+    def alternate(var, routes, repeats, metric):
+        """`repeats` alternated pairs of --iters iterations with the environment variable `var` at the two settings of `routes`
+        ((name, value or None for unset), read at every call by the code it switches): iterations/s of each, one model, one process."""
+        keep = os.environ.get(var)
+        its = {name: [] for name, _ in routes}
+        fwd_ms = {name: [] for name, _ in routes}
+        for _ in range(repeats):
+            for name, value in routes:
+                if value is None:
+                    os.environ.pop(var, None)
                 else:
-                    os.environ["SRF_OTA"] = "0"
+                    os.environ[var] = value
                 step()
                 del phases[:]
                 torch.cuda.synchronize()
@@ -183,14 +188,20 @@ def main():
                 its[name].append(round(a.iters / (time.perf_counter() - t1), 3))
                 fwd_ms[name].append(round(sum(e[0].elapsed_time(e[1]) for e in phases) / len(phases), 2))
         if keep is None:
-            os.environ.pop("SRF_OTA", None)
+            os.environ.pop(var, None)
         else:
-            os.environ["SRF_OTA"] = keep
+            os.environ[var] = keep
         if rank == 0:
-            print(json.dumps(dict(metric="training iterations/s, label assignment on the HIP route against the torch route (SRF_OTA=0), alternated",
-                                  n_gpus=world, bs_per_gpu=a.bs, num_proposals=a.np, image=f"{h}x{w}", train_mfma_dtype=a.train_mfma_dtype,
-                                  iters_per_window=a.iters, it_per_s=its, forward_and_loss_ms=fwd_ms,
+            print(json.dumps(dict(metric=metric, n_gpus=world, bs_per_gpu=a.bs, num_proposals=a.np, image=f"{h}x{w}",
+                                  train_mfma_dtype=a.train_mfma_dtype, iters_per_window=a.iters, it_per_s=its, forward_and_loss_ms=fwd_ms,
                                   spread_it_per_s={k: round(max(v) - min(v), 3) for k, v in its.items()})))
+
+    if a.ota_ab:
+        alternate("SRF_OTA", (("hip", None), ("torch", "0")), a.ota_ab,
+                  "training iterations/s, label assignment on the HIP route against the torch route (SRF_OTA=0), alternated")
+    if a.set_loss_ab:
+        alternate("SRF_SET_LOSS", (("hip", "1"), ("torch", "0")), a.set_loss_ab,
+                  "training iterations/s, decoder losses on the HIP route (SRF_SET_LOSS=1) against the torch route (SRF_SET_LOSS=0), alternated")
     if rank == 0 and a.kernel_table:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
