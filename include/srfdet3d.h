@@ -368,12 +368,23 @@ int srf_spconv_fwd(const float *in, int A_in, int Cin, const float *W, int K, co
  *   transposed).  It is srf_spconv_fwd with the roles swapped, so Cin must be one of its output widths (16, 32, 64, 128).
  *   A submanifold layer may pass nbrT = its own nbr with W_T's offsets reversed (the rulebook is symmetric).
  * srf_spconv_bwd_weight: d_W[k][ci][co] = sum_o in[nbr[k][o]][ci] d_out[o][co], (K, Cin, Cout); Cin, Cout <= 128.  Row
- *   ranges are combined with float atomics: reproducible to rounding, not bitwise. */
+ *   ranges are combined with float atomics: reproducible to rounding, not bitwise (srf_spconv_bwd_weight_ordered below is). */
 int srf_spconv_transpose_rulebook(const int *nbr, int nbr_stride, int K, int A_out, int *nbrT, int A_in, srf_stream_t stream);
 int srf_spconv_bwd_data(const float *grad_out, int A_out, int Cout, const float *W_T, int K, const int *nbrT, int nbrT_stride,
                         int A_in, int Cin, float *grad_in, srf_stream_t stream);
 int srf_spconv_bwd_weight(const float *in, int A_in, int Cin, const float *grad_out, int A_out, int Cout, const int *nbr,
                           int nbr_stride, int K, float *grad_W, srf_stream_t stream);
+
+/* srf_spconv_bwd_weight in a fixed order: two calls give the same bytes.  The output rows are cut into ranges j = 0, 1, ... of 2048
+ * rows; the kernel of srf_spconv_bwd_weight (the same K loop) STORES the (Cin, Cout) partial of (offset k, range j), zeros
+ * included, to workspace[j][k][ci][co], and a second kernel writes d_W[k][ci][co] = the __fadd_rn sum of the partials for
+ * j = 0, 1, ... in ascending order, starting from range 0's value (a single range is stored straight into grad_W).  Limits, codes
+ * and check order of srf_spconv_bwd_weight, then: a NULL workspace with work to do SRF_EINVAL, a workspace smaller than
+ * srf_spconv_bwd_weight_ordered_workspace_bytes SRF_EWORKSPACE.  A_out == 0 or A_in == 0 gives zeros.  The size is 0 for
+ * non-positive arguments and outside the limits. */
+size_t srf_spconv_bwd_weight_ordered_workspace_bytes(int A_out, int Cin, int Cout, int K);
+int srf_spconv_bwd_weight_ordered(const float *in, int A_in, int Cin, const float *grad_out, int A_out, int Cout, const int *nbr,
+                                  int nbr_stride, int K, float *grad_W, void *workspace, size_t workspace_bytes, srf_stream_t stream);
 
 /* Fast path of K5 for constant weights: re-lay W once (srf_spconv_pack_weights -> packed, of
  * srf_spconv_packed_weight_bytes bytes) into the operand layout of the kernel, then call srf_spconv_fwd_packed with
@@ -468,11 +479,33 @@ int srf_roi_extract_sum(const srf_featmap *levels /*host[num_levels]*/, int num_
 
 /* Backward of srf_roi_extract with respect to the feature maps (training of the image branch; RoIs carry no
  * gradient, as in mmcv's roi_align_backward).  grad_levels[i] has the layout of levels[i] and must be zeroed by
- * the caller; grad_out has the strides given. */
+ * the caller; grad_out has the strides given.  Every tap is added with a float atomic: the bits depend on the order in which
+ * the adds arrive (srf_roi_extract_bwd_ordered below fixes the order). */
 int srf_roi_extract_bwd(const srf_featmap *levels /*host*/, float *const *grad_levels /*host array of device ptrs*/,
                         int num_levels, int C, const float *rois, int R, int pooled, int sampling_ratio,
                         float finest_scale, const float *grad_out, int64_t out_stride_r, int64_t out_stride_c,
                         int64_t out_stride_bin, srf_stream_t stream);
+
+/* srf_roi_extract_bwd with the adds of every map element in a fixed order and no float atomic: two calls give the same bytes
+ * (csrc/roi_bwd_ordered.hip; tests/roi_bwd_ordered_ref.py is the definition in numpy float32).
+ *   A record is (RoI r, output row ph, column pw, sample iy, ix, tap t in 0..3), the taps ordered (y_low, x_low), (y_low, x_high),
+ *   (y_high, x_low), (y_high, x_high).  Level, sample point, validity rules and the f32 weights are those of srf_roi_extract_bwd
+ *   (the same __f*_rn sequence; hy = 1 - ly; w = hy * hx and the other three likewise).  A record with w == 0, a sample that is
+ *   NaN or out of range, or a batch id outside [0, N) contributes nothing.  For every element (level, n, y, x, c) touched by at
+ *   least one record:  acc = +0; for the element's records in ascending (r, ph, pw, iy, ix, t):
+ *       acc = __fadd_rn(acc, __fmul_rn(w, __fmul_rn(grad_out[r][bin][c], 1.0f / (sr * sr))))
+ *   and the element is STORED, not added.  Elements without a record are left as the caller passed them (the caller zero-fills).
+ * Arguments, codes and check order of srf_roi_extract_bwd (a level with H <= 0 or W <= 0 is SRF_EINVAL too), then, before any
+ * launch: the levels' N H W summing to 2^30 or more (record keys are 30 bits: level base + flat pixel), R > 2^24 or more than 2^30
+ * records (R pooled^2 sr^2 4): SRF_EUNSUPPORTED; a NULL workspace SRF_EINVAL; one smaller than
+ * srf_roi_extract_bwd_ordered_workspace_bytes SRF_EWORKSPACE; one that is not 16-byte aligned SRF_EUNSUPPORTED.  R == 0 is SRF_OK with
+ * nothing launched.  The workspace size is a worst case computed on the host from (R, pooled, sampling_ratio) alone -- 24 bytes per
+ * record and the scan tables -- and 0 for non-positive arguments and outside the limits. */
+size_t srf_roi_extract_bwd_ordered_workspace_bytes(int R, int pooled, int sampling_ratio);
+int srf_roi_extract_bwd_ordered(const srf_featmap *levels /*host*/, float *const *grad_levels /*host array of device ptrs*/,
+                                int num_levels, int C, const float *rois, int R, int pooled, int sampling_ratio, float finest_scale,
+                                const float *grad_out, int64_t out_stride_r, int64_t out_stride_c, int64_t out_stride_bin,
+                                void *workspace, size_t workspace_bytes, srf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * a11-a13  proposal box -> RoI geometry, fused.

@@ -64,6 +64,8 @@ SIGNATURES = {
     "srf_spconv_transpose_rulebook": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P]),
     "srf_spconv_bwd_data": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "srf_spconv_bwd_weight": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, _P]),
+    "srf_spconv_bwd_weight_ordered_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "srf_spconv_bwd_weight_ordered": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "srf_spconv_packed_weight_bytes": (c_size_t, [c_int, c_int, c_int]),
     "srf_spconv_pack_weights": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "srf_spconv_fwd_packed": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P]),
@@ -205,6 +207,9 @@ SIGNATURES = {
     "srf_nms_finish": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "srf_roi_extract_bwd": (c_int, [POINTER(FeatMap), POINTER(c_void_p), c_int, c_int, _P, c_int, c_int, c_int, c_float, _P,
                                     c_int64, c_int64, c_int64, _P]),
+    "srf_roi_extract_bwd_ordered_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "srf_roi_extract_bwd_ordered": (c_int, [POINTER(FeatMap), POINTER(c_void_p), c_int, c_int, _P, c_int, c_int, c_int, c_float, _P,
+                                            c_int64, c_int64, c_int64, _P, c_size_t, _P]),
     "srf_box_iou_rotated": (c_int, [_P, c_int, _P, c_int, _P, _P]),
     "srf_ota_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "srf_ota_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -10,7 +10,8 @@ tensors' own dtype, with autograd, no host synchronisation: CPU tensors, SRF_MSD
 inference `BaseTransformerLayer.forward_rows` runs a whole layer on channels-last rows: srf_linear GEMMs around `ops.msda`
 (csrc/msda.hip), six launches and one add per layer.  With gradients enabled on float32 GPU tensors the module's forward hands the
 core to `ops.msda_autograd` (forward csrc/msda.hip, backward csrc/msda_bwd.hip; SRF_MSDA_TRAIN=0 keeps the torch core); the Linears,
-the dropout and the LayerNorms around it stay torch modules under autograd."""
+the dropout and the LayerNorms around it stay torch modules under autograd.  Under SRF_DETERMINISTIC=1 a pass that records a gradient
+for `value` raises on either training route: grad_value is float atomics in srf_msda_bwd and in grid_sample's backward alike."""
 import copy
 import math
 
@@ -170,6 +171,11 @@ class MultiScaleDeformableAttention(BaseModule):
                                       "not built, only (x, y) (DESIGN.md section 7)")
         heads, L, P = self.num_heads, self.num_levels, self.num_points
         value = _lin(self.value_proj, value)
+        if ops.deterministic_enabled() and torch.is_grad_enabled() and value.requires_grad:
+            # grad_value is float atomics on either route: srf_msda_bwd on the HIP node, grid_sample's backward on the torch core
+            raise RuntimeError("MultiScaleDeformableAttention: SRF_DETERMINISTIC=1 and a gradient is recorded for `value`, but its only "
+                               "kernels add with float atomics (srf_msda_bwd; torch's grid_sample backward on the torch core) and no "
+                               "fixed-order srf_msda_bwd is built (DESIGN.md section 4).  Unset SRF_DETERMINISTIC or freeze this encoder.")
         offsets = _lin(self.sampling_offsets, query)
         logits = _lin(self.attention_weights, query)
         if self._train_node_ok(value, query, reference_points, bs, S, Q):

@@ -10,27 +10,9 @@
 // samples, so a channels-last map is read 512 B at a time per tap.  Feature maps are addressed through element
 // strides, so NCHW tensors work too (uncoalesced).  Arithmetic follows oracle/srf_oracle.c operation by operation
 // (no fma contraction) so that the two agree exactly.
-#include "common.hpp"
-
-#define SRF_MAX_LEVELS 4
-#define SRF_MAX_POOLED 8
-#define SRF_MAX_SR 4
+#include "roi_frame.hpp"
 
 #define SRF_ROI_NC 4   /* channels per thread whose running sums srf_roi_extract_k keeps in registers (C <= 4 x 128) */
-
-struct RoiLevels {
-    srf_featmap lv[SRF_MAX_LEVELS];
-    int num;
-};
-
-__device__ __forceinline__ int srf_roi_level(const float *b, int num_levels, float finest_scale)
-{
-    float area = __fmul_rn(__fsub_rn(b[3], b[1]), __fsub_rn(b[4], b[2]));
-    float scale = sqrtf(area);
-    float t = floorf(log2f(__fadd_rn(__fdiv_rn(scale, finest_scale), 1e-6f)));
-    if (!(t == t)) return 0;
-    return t < 0.0f ? 0 : (t > (float)(num_levels - 1) ? num_levels - 1 : (int)t);
-}
 
 // n_sum > 1 (srf_roi_extract_sum): output row r is the SUM over s = 0 .. n_sum - 1 of the gathers of the RoIs s * R + r, added in
 // that order -- the per-camera image RoIs of a proposal (srfdet_head.py:2543-2562 gathers all n_cam * R RoIs and then sums the
@@ -246,12 +228,9 @@ extern "C" int srf_roi_extract_sum(const srf_featmap *levels, int num_levels, in
 // branch but VoVNet stages 3-5, the image FPN and img_convs receive gradients through RoIAlign).  Same geometry as
 // the forward kernel; every tap adds weight * grad / count into its map with a float atomic (the order of the adds,
 // and therefore the last bits of the gradient, is not deterministic -- the same holds for the reference's mmcv op).
-// RoIs carry no gradient, as in mmcv.
+// The same terms added in a fixed order, two calls giving the same bytes, are srf_roi_extract_bwd_ordered
+// (roi_bwd_ordered.hip), which training takes under SRF_DETERMINISTIC=1.  RoIs carry no gradient, as in mmcv.
 // ---------------------------------------------------------------------------------------------------------------------
-struct RoiGradLevels {
-    float *grad[SRF_MAX_LEVELS];
-};
-
 __global__ __launch_bounds__(128) void srf_roi_extract_bwd_k(RoiLevels L, RoiGradLevels G, int C, const float *__restrict__ rois,
                                                            int R, int pooled, int sr, float finest_scale,
                                                            const float *__restrict__ gout, long long so_r, long long so_c,

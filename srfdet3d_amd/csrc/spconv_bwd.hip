@@ -10,8 +10,10 @@
 //               Submanifold layers need no transposed table: their rulebook is symmetric, nbrT[k] = nbr[K - 1 - k].
 // weight grad:  d_W[k][ci][co] = sum_o in[nbr[k][o]][ci] d_out[o][co]            -- one (Cin x Cout) GEMM per offset,
 //               reduced over the output rows: srf_spconv_bwd_weight_k below (f32 MFMA, rows staged through LDS, partial
-//               sums of the row ranges combined with float atomics -- the order of those adds is not fixed: gradients are
-//               reproducible to rounding, not bitwise; the forward stays bit-exact).
+//               sums of the row ranges combined with float atomics -- the order of those adds is not fixed: this entry's
+//               gradients are reproducible to rounding, not bitwise; the forward stays bit-exact).
+//               srf_spconv_bwd_weight_ordered is the same K loop with the partial sums STORED per row range and added in
+//               ascending range order by a second kernel: two calls give the same bytes (training under SRF_DETERMINISTIC=1).
 #include "common.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -52,12 +54,14 @@ extern "C" int srf_spconv_bwd_data(const float *grad_out, int A_out, int Cout, c
 // gathered input rows X[32][Cp] and the gradient rows G[32][Np] in LDS (channels zero-padded to multiples of 32); the
 // (Cp / 32) x (Np / 32) accumulator tiles of v_mfma_f32_32x32x2_f32 are dealt round-robin to the 4 waves (A operand =
 // X^T: lane (ci, h) reads X[2 s + h][ci], B = G: lane (co, h) reads G[2 s + h][co]); the partial sums go to d_W[k] with
-// float atomics.
+// float atomics (ORDERED = false), or are stored, zeros included, to the workgroup's own (Cin, Cout) block
+// out[range][k][ci][co] for srf_spconv_bwd_weight_sum_k to add in ascending range order (ORDERED = true).
 // ---------------------------------------------------------------------------------------------------------------------
 #define BW_ROWS 2048
 
-__global__ __launch_bounds__(256) void srf_spconv_bwd_weight_k(const float *__restrict__ in, int Cin, const float *__restrict__ gout, int Cout,
-                                                              const int *__restrict__ nbr, int nbr_stride, int A_out, float *__restrict__ dW)
+template <bool ORDERED>
+__device__ __forceinline__ void srf_spconv_bwd_weight_body(const float *__restrict__ in, int Cin, const float *__restrict__ gout, int Cout,
+                                                           const int *__restrict__ nbr, int nbr_stride, int A_out, float *__restrict__ dW)
 {
     __shared__ float s_x[32][128 + 4];
     __shared__ float s_g[32][128 + 4];
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void srf_spconv_bwd_weight_k(const float *__re
         }
         __syncthreads();
     }
-    float *dwk = dW + (size_t)k * Cin * Cout;
+    float *dwk = dW + ((ORDERED ? (size_t)blockIdx.y * gridDim.x : 0) + (size_t)k) * Cin * Cout;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int tile = wave + 4 * t;
@@ -109,10 +113,48 @@ __global__ __launch_bounds__(256) void srf_spconv_bwd_weight_k(const float *__re
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ci = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (ci < Cin && co < Cout && acc[t][r] != 0.f) atomicAdd(&dwk[(size_t)ci * Cout + co], acc[t][r]);
+                if (ORDERED) {
+                    if (ci < Cin && co < Cout) dwk[(size_t)ci * Cout + co] = acc[t][r];
+                } else {
+                    if (ci < Cin && co < Cout && acc[t][r] != 0.f) atomicAdd(&dwk[(size_t)ci * Cout + co], acc[t][r]);
+                }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void srf_spconv_bwd_weight_k(const float *__restrict__ in, int Cin, const float *__restrict__ gout, int Cout,
+                                                              const int *__restrict__ nbr, int nbr_stride, int A_out, float *__restrict__ dW)
+{
+    srf_spconv_bwd_weight_body<false>(in, Cin, gout, Cout, nbr, nbr_stride, A_out, dW);
+}
+
+// the (Cin x Cout) tiles of a workgroup cover its whole block (Cin, Cout <= 128: at most 4 x 4 tiles on 4 waves x 4): nothing of
+// `parts` is left unwritten
+__global__ __launch_bounds__(256) void srf_spconv_bwd_weight_ordered_k(const float *__restrict__ in, int Cin, const float *__restrict__ gout,
+                                                                      int Cout, const int *__restrict__ nbr, int nbr_stride, int A_out,
+                                                                      float *__restrict__ parts)
+{
+    srf_spconv_bwd_weight_body<true>(in, Cin, gout, Cout, nbr, nbr_stride, A_out, parts);
+}
+
+// dW[e] = parts[0][e] + parts[1][e] + ... in that order, one thread per element e of (K, Cin, Cout); the loads do not depend on
+// the adds, four ranges are in flight per step
+__global__ __launch_bounds__(256) void srf_spconv_bwd_weight_sum_k(const float *__restrict__ parts, size_t elems, int ranges, float *__restrict__ dW)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= elems) return;
+    float v = parts[e];
+    int j = 1;
+    for (; j + 4 <= ranges; j += 4) {
+        float p[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p[u] = parts[(size_t)(j + u) * elems + e];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v = __fadd_rn(v, p[u]);
+    }
+    for (; j < ranges; ++j) v = __fadd_rn(v, parts[(size_t)j * elems + e]);
+    dW[e] = v;
 }
 
 extern "C" int srf_spconv_bwd_weight(const float *in, int A_in, int Cin, const float *grad_out, int A_out, int Cout, const int *nbr,
@@ -126,6 +168,38 @@ extern "C" int srf_spconv_bwd_weight(const float *in, int A_in, int Cin, const f
     if (!in || !grad_out || !nbr) return SRF_EINVAL;
     hipLaunchKernelGGL(srf_spconv_bwd_weight_k, dim3(K, srf_ceil_div(A_out, BW_ROWS)), dim3(256), 0, (hipStream_t)stream, in, Cin, grad_out, Cout,
                        nbr, nbr_stride, A_out, grad_W);
+    SRF_LAUNCH_CHECK();
+    return SRF_OK;
+}
+
+extern "C" size_t srf_spconv_bwd_weight_ordered_workspace_bytes(int A_out, int Cin, int Cout, int K)
+{
+    if (A_out <= 0 || Cin <= 0 || Cout <= 0 || K <= 0 || Cin > 128 || Cout > 128) return 0;
+    return (size_t)srf_ceil_div(A_out, BW_ROWS) * K * Cin * Cout * sizeof(float);
+}
+
+// srf_spconv_bwd_weight with the row ranges' partial sums added in ascending range order (see the header of this file).  A single
+// range (A_out <= BW_ROWS) is stored straight into grad_W.
+extern "C" int srf_spconv_bwd_weight_ordered(const float *in, int A_in, int Cin, const float *grad_out, int A_out, int Cout, const int *nbr,
+                                             int nbr_stride, int K, float *grad_W, void *workspace, size_t workspace_bytes, srf_stream_t stream)
+{
+    if (A_in < 0 || A_out < 0 || Cin <= 0 || Cout <= 0 || K <= 0 || nbr_stride < A_out) return SRF_EINVAL;
+    if (Cin > 128 || Cout > 128) return SRF_EUNSUPPORTED;
+    if (!grad_W) return SRF_EINVAL;
+    if (A_out == 0 || A_in == 0) {
+        SRF_HIP_TRY(srf_fill_bytes(grad_W, 0, (size_t)K * Cin * Cout * sizeof(float), (hipStream_t)stream));
+        return SRF_OK;
+    }
+    if (!in || !grad_out || !nbr || !workspace) return SRF_EINVAL;
+    if (workspace_bytes < srf_spconv_bwd_weight_ordered_workspace_bytes(A_out, Cin, Cout, K)) return SRF_EWORKSPACE;
+    if ((uintptr_t)workspace & 3) return SRF_EINVAL;
+    const int ranges = srf_ceil_div(A_out, BW_ROWS);
+    const size_t elems = (size_t)K * Cin * Cout;
+    hipLaunchKernelGGL(srf_spconv_bwd_weight_ordered_k, dim3(K, ranges), dim3(256), 0, (hipStream_t)stream, in, Cin, grad_out, Cout, nbr,
+                       nbr_stride, A_out, ranges == 1 ? grad_W : (float *)workspace);
+    if (ranges > 1)
+        hipLaunchKernelGGL(srf_spconv_bwd_weight_sum_k, dim3(srf_ceil_div((long long)elems, 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const float *)workspace, elems, ranges, grad_W);
     SRF_LAUNCH_CHECK();
     return SRF_OK;
 }

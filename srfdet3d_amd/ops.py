@@ -910,9 +910,16 @@ class _SpconvFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             gw = _empty((K, Cin, Cout), torch.float32, g.device)
             f = feats.detach().contiguous()
-            check(_lib.lib().srf_spconv_bwd_weight(_ptr(f), f.shape[0], Cin, _ptr(g), g.shape[0], Cout, _ptr(nbr),
-                                                   nbr.stride(0) if nbr.shape[1] > 0 else 0, K, _ptr(gw), _stream()),
-                  "spconv_bwd_weight")
+            nbr_ld = nbr.stride(0) if nbr.shape[1] > 0 else 0
+            if deterministic_enabled():   # the row ranges' partial sums stored and added in ascending order: no float atomics
+                L = _lib.lib()
+                ws_bytes = L.srf_spconv_bwd_weight_ordered_workspace_bytes(g.shape[0], Cin, Cout, K)
+                ws = _empty((max(ws_bytes, 4) // 4,), torch.float32, g.device)
+                check(L.srf_spconv_bwd_weight_ordered(_ptr(f), f.shape[0], Cin, _ptr(g), g.shape[0], Cout, _ptr(nbr), nbr_ld, K, _ptr(gw),
+                                                      _ptr(ws), ws_bytes, _stream()), "spconv_bwd_weight_ordered")
+            else:
+                check(_lib.lib().srf_spconv_bwd_weight(_ptr(f), f.shape[0], Cin, _ptr(g), g.shape[0], Cout, _ptr(nbr), nbr_ld, K, _ptr(gw),
+                                                       _stream()), "spconv_bwd_weight")
         return gf, gw, None, None
 
 
@@ -2448,9 +2455,24 @@ class _RoIExtractFn(torch.autograd.Function):
         gp = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grads])
         bins = out_size * out_size
         so_c, so_b = (1, C) if bin_major else (bins, 1)
-        check(_lib.lib().srf_roi_extract_bwd(fm, gp, nl, C, _ptr(rois), R, out_size, sampling_ratio, float(finest_scale),
-                                             _ptr(grad_out), C * bins, so_c, so_b, _stream()), "roi_extract_bwd")
+        if deterministic_enabled():   # every map element's adds in a fixed order; a shape the entry refuses raises (no fall-back)
+            L = _lib.lib()
+            ws_bytes = L.srf_roi_extract_bwd_ordered_workspace_bytes(R, out_size, sampling_ratio)
+            ws = _empty((max(ws_bytes, 4) // 4,), torch.float32, grad_out.device)
+            check(L.srf_roi_extract_bwd_ordered(fm, gp, nl, C, _ptr(rois), R, out_size, sampling_ratio, float(finest_scale), _ptr(grad_out),
+                                                C * bins, so_c, so_b, _ptr(ws), ws_bytes, _stream()),
+                  "roi_extract_bwd_ordered (SRF_DETERMINISTIC=1)")
+        else:
+            check(_lib.lib().srf_roi_extract_bwd(fm, gp, nl, C, _ptr(rois), R, out_size, sampling_ratio, float(finest_scale),
+                                                 _ptr(grad_out), C * bins, so_c, so_b, _stream()), "roi_extract_bwd")
         return (None, None, None, None, None, None, *grads)
+
+
+def deterministic_enabled():
+    """SRF_DETERMINISTIC=1: a gradient that would need one of this library's float-atomic kernels takes a fixed-order kernel instead
+    (`srf_roi_extract_bwd_ordered`, `srf_spconv_bwd_weight_ordered`) or raises (`srf_msda_bwd`, compat/transformer.py): two passes give
+    the same bytes.  Unset or 0: the routes of before.  Independent of torch's own determinism flags.  Read at every call."""
+    return os.environ.get("SRF_DETERMINISTIC", "0") == "1"
 
 
 def roi_extract_autograd(feats, rois, strides, out_size=7, sampling_ratio=2, finest_scale=56.0, bin_major=False):

@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--set-loss-ab", type=int, default=0, metavar="R",
                     help="the same alternation for the focal / L1 losses of the decoder stages: SRF_SET_LOSS=1 (one call of srf_set_loss per step) "
                          "against SRF_SET_LOSS=0 (the torch operators, the default)")
+    ap.add_argument("--deterministic-ab", type=int, default=0, metavar="R",
+                    help="the same alternation for the fixed-order gradient kernels: SRF_DETERMINISTIC=1 (srf_roi_extract_bwd_ordered, "
+                         "srf_spconv_bwd_weight_ordered) against unset (the float-atomic kernels, the default); reports the backward phase too")
     a = ap.parse_args()
     rank, local, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(local)
@@ -168,6 +171,7 @@ def main():
         keep = os.environ.get(var)
         its = {name: [] for name, _ in routes}
         fwd_ms = {name: [] for name, _ in routes}
+        bwd_ms = {name: [] for name, _ in routes}
         for _ in range(repeats):
             for name, value in routes:
                 if value is None:
@@ -187,13 +191,14 @@ def main():
                     dist.barrier()
                 its[name].append(round(a.iters / (time.perf_counter() - t1), 3))
                 fwd_ms[name].append(round(sum(e[0].elapsed_time(e[1]) for e in phases) / len(phases), 2))
+                bwd_ms[name].append(round(sum(e[1].elapsed_time(e[2]) for e in phases) / len(phases), 2))
         if keep is None:
             os.environ.pop(var, None)
         else:
             os.environ[var] = keep
         if rank == 0:
             print(json.dumps(dict(metric=metric, n_gpus=world, bs_per_gpu=a.bs, num_proposals=a.np, image=f"{h}x{w}",
-                                  train_mfma_dtype=a.train_mfma_dtype, iters_per_window=a.iters, it_per_s=its, forward_and_loss_ms=fwd_ms,
+                                  train_mfma_dtype=a.train_mfma_dtype, iters_per_window=a.iters, it_per_s=its, forward_and_loss_ms=fwd_ms, backward_ms=bwd_ms,
                                   spread_it_per_s={k: round(max(v) - min(v), 3) for k, v in its.items()})))
 
     if a.ota_ab:
@@ -202,6 +207,10 @@ def main():
     if a.set_loss_ab:
         alternate("SRF_SET_LOSS", (("hip", "1"), ("torch", "0")), a.set_loss_ab,
                   "training iterations/s, decoder losses on the HIP route (SRF_SET_LOSS=1) against the torch route (SRF_SET_LOSS=0), alternated")
+    if a.deterministic_ab:
+        alternate("SRF_DETERMINISTIC", (("ordered", "1"), ("atomic", None)), a.deterministic_ab,
+                  "training iterations/s, fixed-order RoI / sparse weight gradients (SRF_DETERMINISTIC=1) against the float-atomic kernels "
+                  "(unset), alternated")
     if rank == 0 and a.kernel_table:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
