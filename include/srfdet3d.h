@@ -296,12 +296,16 @@ int srf_hard_voxelize_static(const float *points, int n, int nf, const float *vo
  * Replaces mmcv.ops.DynamicScatter.forward as called from
  * mmdet3d_plugin/models/voxel_encoders/voxel_encoder.py:189 (mean) and :232 (max), and the dense canvas of
  * map_voxel_center_to_point (:118-158).
- * srf_voxel_unique: coors (n,4) int32 (b,z,y,x); rows with any negative entry are dropped.  Outputs, all
+ * srf_voxel_unique: coors (n,4) int32 (b,z,y,x).  A row is kept only if it names a cell of the grid: 0 <= b < batch,
+ *   0 <= z < D, 0 <= y < H, 0 <= x < W.  Every other row is dropped -- a row with a negative entry (the -1 rows of K2),
+ *   and equally a row with b >= batch or a coordinate at or over its extent: it is never filed under another cell and
+ *   never reaches past the batch*D*H*W cells.  Outputs, all
  *   caller-allocated with n rows: out_coors (n x 4, first *num_voxels rows valid, sorted lexicographically),
  *   point2voxel (n; -1 for dropped points), counts (n; points per voxel), offsets (n; start of each voxel's
- *   list in `order`), order (n; point indices grouped by voxel, ascending within a voxel), num_voxels (1 int).
- * srf_scatter_reduce: out (rows x C), rows >= *num_voxels; mode 0 = mean (sum in point order / count),
- *   1 = max.
+ *   list in `order`), order (n; point indices grouped by voxel, ascending within a voxel; the entries past the
+ *   number of kept points are not written), num_voxels (1 int).
+ * srf_scatter_reduce: out (rows x C); the first min(rows, *num_voxels) rows are written, any further rows are left as
+ *   they were; mode 0 = mean (sum in point order / count), 1 = max (v > acc ? v : acc from -inf: a NaN is never taken).
  * ------------------------------------------------------------------------------------------------------- */
 size_t srf_voxel_unique_workspace_bytes(int n, const int *grid_zyx /*host[3] D,H,W*/, int batch);
 int srf_voxel_unique(const int *coors, int n, const int *grid_zyx /*host[3]*/, int batch, int *out_coors,

@@ -89,7 +89,9 @@ def vfe_mean(voxels, num, num_features=None):
     return out
 
 
-def dynamic_scatter(feats, coors, grid_zyx, mode):
+def dynamic_scatter(feats, coors, grid_zyx, mode, batch=None):
+    """batch=None: the op as mmcv has it (rows with a negative entry are dropped).  With a batch count, rows with b >= batch
+    or a coordinate at or over its extent are dropped too -- the rule of srf_voxel_unique."""
     feats = _f32(feats)
     coors = _i32(coors)
     n, C = feats.shape
@@ -97,8 +99,9 @@ def dynamic_scatter(feats, coors, grid_zyx, mode):
     out_c = np.empty((max(n, 1), 4), np.int32)
     p2v = np.empty((max(n, 1),), np.int32)
     m = ctypes.c_int(0)
-    _check(lib().orc_dynamic_scatter(_p(feats), _p(coors), n, C, _p(_i32(grid_zyx)), 0 if mode == "mean" else 1,
-                                     _p(out_f), _p(out_c), _p(p2v), ctypes.byref(m)), "dynamic_scatter")
+    _check(lib().orc_dynamic_scatter_batch(_p(feats), _p(coors), n, C, _p(_i32(grid_zyx)), 0 if batch is None else int(batch),
+                                           0 if mode == "mean" else 1, _p(out_f), _p(out_c), _p(p2v), ctypes.byref(m)),
+           "dynamic_scatter")
     M = m.value
     return out_f[:M].copy(), out_c[:M].copy(), p2v[:n].copy()
 

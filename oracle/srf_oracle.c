@@ -176,7 +176,7 @@ int orc_vfe_mean(const float *voxels, const int *num, int M, int max_points, int
  * K3  DynamicScatter (mean | max)
  * reference call sites: mmdet3d_plugin/models/voxel_encoders/voxel_encoder.py:82,99-102,189,232
  * third-party op: mmcv.ops.DynamicScatter -> dynamic_point_to_voxel_forward (Appendix B.3):
- * rows with any negative coord are dropped; unique voxel coords sorted lexicographically over
+ * rows with any negative coord are dropped (and, given a batch count, rows outside the grid); unique voxel coords sorted lexicographically over
  * (b,z,y,x); per voxel mean (sum in point order / count) or max of the point features.
  * point2voxel[i] = row of point i in the output, or -1.
  * ---------------------------------------------------------------------------------------- */
@@ -191,10 +191,10 @@ static int kv_cmp(const void *a, const void *b)
     return x->idx < y->idx ? -1 : (x->idx > y->idx);
 }
 
-int orc_dynamic_scatter(const float *feats, const int *coors /* n x 4 (b,z,y,x) */, int n, int C,
-                        const int *grid_zyx /* D,H,W */, int mode /* 0 mean, 1 max */,
-                        float *out_feats /* n x C */, int *out_coors /* n x 4 */, int *point2voxel,
-                        int *M_out)
+int orc_dynamic_scatter_batch(const float *feats, const int *coors /* n x 4 (b,z,y,x) */, int n, int C,
+                              const int *grid_zyx /* D,H,W */, int batch /* > 0: rows outside the grid are dropped too */,
+                              int mode /* 0 mean, 1 max */, float *out_feats /* n x C */, int *out_coors /* n x 4 */,
+                              int *point2voxel, int *M_out)
 {
     orc_kv *kv = (orc_kv *)malloc(sizeof(orc_kv) * (size_t)(n > 0 ? n : 1));
     if (!kv) return ORC_ENOMEM;
@@ -203,6 +203,9 @@ int orc_dynamic_scatter(const float *feats, const int *coors /* n x 4 (b,z,y,x) 
         const int *c = coors + 4 * i;
         point2voxel[i] = -1;
         if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[3] < 0) continue;
+        /* the coordinate rule of the library (include/srfdet3d.h, K3): a row that names no cell of the
+         * batch x D x H x W grid is dropped, not filed under the cell its linearised key happens to hit */
+        if (batch > 0 && (c[0] >= batch || c[1] >= grid_zyx[0] || c[2] >= grid_zyx[1] || c[3] >= grid_zyx[2])) continue;
         kv[nv].key = (((int64_t)c[0] * grid_zyx[0] + c[1]) * grid_zyx[1] + c[2]) * grid_zyx[2] + c[3];
         kv[nv].idx = i;
         ++nv;
@@ -234,6 +237,13 @@ int orc_dynamic_scatter(const float *feats, const int *coors /* n x 4 (b,z,y,x) 
     *M_out = M;
     free(kv);
     return ORC_OK;
+}
+
+/* the op as mmcv defines it, with no batch count: only rows with a negative entry are dropped */
+int orc_dynamic_scatter(const float *feats, const int *coors, int n, int C, const int *grid_zyx, int mode,
+                        float *out_feats, int *out_coors, int *point2voxel, int *M_out)
+{
+    return orc_dynamic_scatter_batch(feats, coors, n, C, grid_zyx, 0, mode, out_feats, out_coors, point2voxel, M_out);
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -12,13 +12,17 @@
 #include "common.hpp"
 
 struct ScatterGeom {
-    int D, H, W;
+    int B, D, H, W;
     uint32_t nwords;
 };
 
+// a row (b, z, y, x) has a key only inside [0, B) x [0, D) x [0, H) x [0, W): every other row is dropped, so no key reaches past the
+// B*D*H*W bits of the bitmap and no point is filed under another cell (one unsigned compare per column covers both sides)
 __device__ __forceinline__ bool srf_coor_key(const int4 &c, const ScatterGeom &g, uint32_t &key)
 {
-    if (c.x < 0 || c.y < 0 || c.z < 0 || c.w < 0) return false;
+    if ((uint32_t)c.x >= (uint32_t)g.B || (uint32_t)c.y >= (uint32_t)g.D || (uint32_t)c.z >= (uint32_t)g.H ||
+        (uint32_t)c.w >= (uint32_t)g.W)
+        return false;
     key = (((uint32_t)c.x * (uint32_t)g.D + (uint32_t)c.y) * (uint32_t)g.H + (uint32_t)c.z) * (uint32_t)g.W + (uint32_t)c.w;
     return true;
 }
@@ -144,6 +148,7 @@ static bool srf_scatter_geom(ScatterGeom &g, const int *grid_zyx, int batch)
         vol *= (unsigned long long)grid_zyx[d];
     }
     if (vol >= 0xFFFFFFFFull) return false;
+    g.B = batch;
     g.D = grid_zyx[0];
     g.H = grid_zyx[1];
     g.W = grid_zyx[2];
