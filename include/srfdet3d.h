@@ -538,7 +538,10 @@ int srf_box_rois(float *boxes, int B, int P, int box_dim, const float *pc_range 
  *   replaces the attention core of nn.MultiheadAttention(batch 1) at srfdet_head.py:1489.
  * srf_dynconv_mid: feats (R x S x C) bin-major RoI features, params (R x 2*C*D) from dynamic_layer ->
  *   relu(LN_C(relu(LN_D(feats W1)) W2)) (R x S x C); srfdet_head.py:2671-2686.  (C, D) in {(128,32), (256,64)}, S <= 64.
- * srf_apply_deltas: srfdet_head.py:1534-1625; weights6 / pc_range are host arrays.
+ * srf_apply_deltas: srfdet_head.py:1534-1625; deltas (R x Dd) on boxes (R x Dd) [centres in metres, log sizes, ...] -> out (R x Dd):
+ *   clip((d / w * exp(b_size) + b_ctr - lo) / ext, 0, 1) | log(exp(min(d / w, scale_clamp)) * exp(b_size)) | the deltas from column 6 on,
+ *   copied.  weights6 / pc_range are host arrays of 6 floats; ext = pc_range[3 + i] - pc_range[i], formed in float32.  Checked in this
+ *   order: R < 0, Dd < 8 (no upper limit), a NULL weights6 or pc_range: SRF_EINVAL; R == 0: SRF_OK; a NULL deltas, boxes or out: SRF_EINVAL.
  * ------------------------------------------------------------------------------------------------------- */
 size_t srf_linear_workspace_bytes(int M, int N, int K);
 int srf_linear(const float *X, int M, int K, int ldx, const float *W, int N, int ldw, const float *bias,
@@ -917,7 +920,9 @@ int srf_nhwc_dwconv3x3s2(const float *x, long long x_ld, int N, int H, int W, in
  *   n_cam = 1 for the BEV pyramid); out rows have out_ld >= Ho * Wo floats, the tail zero-filled (K padding of fc1).
  * srf_dpg_mix: softmax over the E experts of the logits wl (B, E * P) (with wi: of (wl + wi) / 2), the expert-weighted sums of
  *   the proposal boxes (E * P, D) and features (E * P, C), and the sigmoid of the box centres (:957) -> boxes (B, P, D),
- *   feats (B, P, C). */
+ *   feats (B, P, C).  The logits are expert-major: expert e of proposal p of sample b is wl[(b * E + e) * P + p]; a logit of -inf gives
+ *   that expert the weight 0 (every expert of a (b, p) at -inf is not defined).  Checked in this order: B < 0, E outside 1..16,
+ *   P <= 0, D < 3, C <= 0: SRF_EINVAL; B == 0: SRF_OK; a NULL wl, boxes_w, feats_w, boxes or feats: SRF_EINVAL (wi may be NULL). */
 int srf_nhwc_dwconv3x3s2_cat(const float *x, long long x_ld, int N, int H, int W, int C, const float *w, const float *scale,
                              const float *shift, int relu, float *y, long long y_ld, const float *side, long long side_ld, int Cs,
                              float *side_out, srf_stream_t stream);
@@ -950,7 +955,12 @@ int srf_dpg_mix(const float *wl, const float *wi /*or NULL*/, int B, int E, int 
 /* srf_stage_tail: the row-local remainder of a stage in one launch (srfdet_head.py:1506-1520): FFN + residual + norm3,
  * classification tower + class_logits, regression tower + bboxes_delta + apply_deltas.  obj_in (R x C) is norm2's
  * output; outputs obj_out (R x C), logits (R x ncls), pred (R x Dd).  cls_/reg_ arrays are HOST arrays of n_cls / n_reg
- * device pointers (weights (C x C), LayerNorm gamma/beta) and host eps values.  C == 128, F in {128,...,512}.
+ * device pointers (weights (C x C), LayerNorm gamma/beta) and host eps values; boxes_m (R x Dd) are the boxes of srf_apply_deltas,
+ * weights6 / pc_range / scale_clamp its geometry.
+ * Limits, checked in this order: R >= 0, C == 128, F in {128, 256, 384, 512}, 0 <= n_cls, n_reg <= 4, 1 <= ncls <= 32, 8 <= Dd <= 32, else
+ * SRF_EUNSUPPORTED; R == 0: SRF_OK, no pointer is touched; a NULL among obj_in, w1, b1, w2, b2, n3_g, n3_b, wl, bl, wd, bd, boxes_m,
+ * weights6, pc_range, obj_out, logits, pred: SRF_EINVAL (the tower arrays are read for the first n_cls / n_reg entries only); a workspace
+ * shorter than srf_stage_tail_workspace_bytes: SRF_EWORKSPACE, nothing written.  plugin/heads.py::_tail_fusable restates the limits.
  * workspace (srf_stage_tail_workspace_bytes(R, C, F), may be NULL): with it the FFN runs as its own launch, one workgroup per
  * (32 rows, 128 hidden units), and the tail adds the slices in a fixed order (deterministic; the sum of F / 128 partial chains
  * instead of one chain over F, i.e. equal to the in-line FFN to rounding, not bit for bit); without it everything is one launch. */

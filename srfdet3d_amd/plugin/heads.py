@@ -235,11 +235,12 @@ class _StageBase(BaseModule):
                 and isinstance(self.activation_lidar, nn.ReLU) and dc.dynamic_num == 2)
 
     def _tail_fusable(self):
-        """srf_stage_tail covers C == 128, FFN width a multiple of 128 up to 512 and towers of at most 4 layers."""
+        """The limits of srf_stage_tail (include/srfdet3d.h): C == 128, FFN width 128, 256, 384 or 512, towers of at most 4 layers
+        (three modules each), 1..32 classes, 8..32 box columns.  tests/test_linear_args.py holds this to the entry point's own answer."""
         F = self.linear1_lidar.weight.shape[0]
-        return (self.fuse_stage_tail and self.feat_channels_lidar == 128 and F % 128 == 0 and F <= 512
+        return (self.fuse_stage_tail and self.feat_channels_lidar == 128 and F % 128 == 0 and 128 <= F <= 512
                 and len(self.cls_module_lidar) <= 12 and len(self.reg_module_lidar) <= 12
-                and self.class_logits_lidar.weight.shape[0] <= 32 and 8 <= self.bboxes_delta_lidar.weight.shape[0] <= 32)
+                and 1 <= self.class_logits_lidar.weight.shape[0] <= 32 and 8 <= self.bboxes_delta_lidar.weight.shape[0] <= 32)
 
     def _attend_hip(self, q0, bs):
         """The half of a stage that needs no RoI feature (srfdet_head.py:1486-1496, :2636-2646 and the head of DynamicConv, :2671):

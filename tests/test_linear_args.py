@@ -1,8 +1,10 @@
-"""Return codes of `srf_linear`, `srf_self_attention_batched`, `srf_dynconv_mid` and `srf_ese_gate`, in the order the entry points check
-them: sizes and pitches SRF_EINVAL, a half-given LayerNorm SRF_EINVAL, nothing to do SRF_OK, null pointers SRF_EINVAL, a shape outside the
-limits SRF_EUNSUPPORTED, a workspace too small SRF_EWORKSPACE -- all before any HIP call: the library loads and answers on a machine
+"""Return codes of `srf_linear`, `srf_self_attention_batched`, `srf_dynconv_mid`, `srf_ese_gate`, `srf_stage_tail`, `srf_apply_deltas` and
+`srf_dpg_mix`, in the order the entry points check them: sizes and pitches SRF_EINVAL, a half-given LayerNorm SRF_EINVAL, nothing to do
+SRF_OK, null pointers SRF_EINVAL, a shape outside the limits SRF_EUNSUPPORTED (`srf_stage_tail` answers its limits first, then nothing to
+do, then the null pointers), a workspace too small SRF_EWORKSPACE -- all before any HIP call: the library loads and answers on a machine
 without a GPU.  Every pointer handed in here is a made-up address that no kernel may ever see, so every call in this file ends in a
-refusal or in a nothing-to-do SRF_OK (M == 0, P == 0, B == 0, R == 0, N == 0); none passes every check."""
+refusal or in a nothing-to-do SRF_OK (M == 0, P == 0, B == 0, R == 0, N == 0); none passes every check.  (The one test marked `gpu`
+below brings real buffers: a workspace one byte short is refused after the device has been asked for.)"""
 import ctypes
 
 import pytest
@@ -137,6 +139,113 @@ def test_ese_gate_codes():
         assert ese(N=1, **{name: None}) == EINVAL and ese(N=8, **{name: None}) == EINVAL
 
 
+# ------------------------------------------------------------------------------------------------------------------- stage tail
+TAIL_POINTERS = ["obj_in", "w1", "b1", "w2", "b2", "n3_g", "n3_b", "wl", "bl", "wd", "bd", "boxes_m", "weights6", "pc_range", "obj_out", "logits",
+                 "pred"]
+HOST6 = _lib.hf([1.0] * 6)
+
+
+def tail(R=10, C=128, F=512, n_cls=2, n_reg=3, ncls=10, Dd=10, ws=None, ws_bytes=0, **ptr):
+    """obj_in is NULL by default: a call that passes the shape checks with R > 0 ends at SRF_EINVAL, never in a launch.  The tower arrays
+    are host arrays the entry point reads only after every check here; NULL."""
+    a = {name: PTR for name in TAIL_POINTERS}
+    a.update(weights6=HOST6, pc_range=HOST6, obj_in=None)
+    a.update(ptr)
+    towers = (None, None, None, None)
+    return _lib.lib().srf_stage_tail(a["obj_in"], R, C, F, a["w1"], a["b1"], a["w2"], a["b2"], a["n3_g"], a["n3_b"], 1e-5, n_cls, *towers,
+                                     n_reg, *towers, a["wl"], a["bl"], ncls, a["wd"], a["bd"], Dd, a["boxes_m"], a["weights6"], a["pc_range"],
+                                     5.0, a["obj_out"], a["logits"], a["pred"], ws, ws_bytes, None)
+
+
+TAIL_OUTSIDE = [dict(C=64), dict(C=256), dict(F=100), dict(F=640), dict(F=0), dict(F=-128), dict(n_cls=5), dict(n_cls=-1), dict(n_reg=5),
+                dict(n_reg=-1), dict(ncls=0), dict(ncls=33), dict(Dd=7), dict(Dd=33)]
+TAIL_INSIDE = [dict(F=128), dict(F=256), dict(F=384), dict(F=512), dict(n_cls=0, n_reg=0), dict(n_cls=4, n_reg=4), dict(ncls=1), dict(ncls=32),
+               dict(Dd=8), dict(Dd=32)]
+
+
+def test_stage_tail_codes():
+    for kw in TAIL_OUTSIDE:
+        assert tail(**kw) == EUNSUPPORTED, kw
+        assert tail(**kw, R=0) == EUNSUPPORTED, kw                                # the shapes come before the nothing-to-do answer
+        assert tail(**kw, obj_in=PTR, w1=None) == EUNSUPPORTED, kw               # and before the null pointers
+    assert tail(R=-1) == EUNSUPPORTED
+    for kw in TAIL_INSIDE:
+        assert tail(**kw, R=0) == OK, kw
+        assert tail(**kw) == EINVAL, kw                                          # obj_in is NULL
+    assert tail(R=0, **{name: None for name in TAIL_POINTERS}) == OK             # nothing to do comes before the null pointers
+    for name in TAIL_POINTERS[1:]:
+        assert tail(obj_in=PTR, **{name: None}) == EINVAL, name
+        assert tail(obj_in=PTR, **{name: None}, ws=PTR, ws_bytes=0) == EINVAL, name      # null pointers before the workspace
+    need = _lib.lib().srf_stage_tail_workspace_bytes
+    assert need(200, 128, 512) == 4 * 200 * 128 * 4 and need(37, 128, 384) == 3 * 37 * 128 * 4 and need(0, 128, 512) == 0
+
+
+def _stub_head(C, F, n_cls, n_reg, ncls, Dd, fuse=True):
+    from types import SimpleNamespace as NS
+    lin = lambda n: NS(weight=NS(shape=(n, C)))
+    return NS(fuse_stage_tail=fuse, feat_channels_lidar=C, linear1_lidar=lin(F), cls_module_lidar=[None] * (3 * n_cls),
+              reg_module_lidar=[None] * (3 * n_reg), class_logits_lidar=lin(ncls), bboxes_delta_lidar=lin(Dd))
+
+
+def test_the_head_fuses_exactly_what_stage_tail_supports():
+    """plugin/heads.py::_tail_fusable restates the limits of srf_stage_tail; the entry point answers R == 0 after its shape checks and before
+    it touches a pointer.  (C, F, cls layers, reg layers, ncls, Dd) on both sides of every limit."""
+    from srfdet3d_amd.plugin import heads
+    base = dict(C=128, F=512, n_cls=2, n_reg=3, ncls=10, Dd=10)
+    seen = set()
+    for kw in TAIL_OUTSIDE + TAIL_INSIDE + [{}]:
+        if any(v < 0 for v in kw.values()):
+            continue                                                             # a module cannot have fewer than no layers or rows
+        c = {**base, **kw}
+        fusable = bool(heads._StageBase._tail_fusable(_stub_head(**c)))
+        assert fusable == (tail(**c, R=0) == OK), c
+        seen.add(fusable)
+    assert seen == {True, False}
+    assert not heads._StageBase._tail_fusable(_stub_head(**base, fuse=False))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("short", [1, 4])
+def test_stage_tail_workspace_short_writes_nothing(dev, short):
+    """With real buffers: a workspace `short` bytes short is SRF_EWORKSPACE and all three outputs keep the sentinel."""
+    import decoder_ref as R
+    params, boxes = R.stage_tail_inputs(37, 384, 1, 1, 3, 8, seed=3)
+    d = R.stage_tail_device(params, boxes, dev)
+    need = _lib.lib().srf_stage_tail_workspace_bytes(37, 128, 384)
+    rc, *outs = R.call_stage_tail(d, R.GEOM, True, ws_bytes=need - short, sentinel=777.0)
+    assert rc == EWORKSPACE and all((o == 777.0).all() for o in outs)
+
+
+# ----------------------------------------------------------------------------------------------------- apply_deltas, dpg_mix
+def deltas(d=None, boxes=PTR, R=9, Dd=10, weights6=HOST6, pc_range=HOST6, out=PTR):
+    """deltas is NULL by default: a call that passes the other checks with R > 0 ends at SRF_EINVAL."""
+    return _lib.lib().srf_apply_deltas(d, boxes, R, Dd, weights6, pc_range, 5.0, out, None)
+
+
+def test_apply_deltas_codes():
+    for kw in (dict(Dd=7), dict(Dd=0), dict(weights6=None), dict(pc_range=None), dict(R=-1)):
+        assert deltas(**kw) == EINVAL, kw
+        assert deltas(**{**kw, "R": min(0, kw.get("R", 0))}) == EINVAL, kw       # before the nothing-to-do answer
+    assert deltas(R=0) == OK and deltas(R=0, boxes=None, out=None) == OK and deltas(R=0, Dd=8) == OK and deltas(R=0, Dd=64) == OK
+    assert deltas() == EINVAL and deltas(d=PTR, boxes=None) == EINVAL and deltas(d=PTR, out=None) == EINVAL
+
+
+def mix(wl=None, wi=None, B=2, E=4, P=200, boxes_w=PTR, D=10, feats_w=PTR, C=128, boxes=PTR, feats=PTR):
+    """wl is NULL by default: a call that passes the size checks with B > 0 ends at SRF_EINVAL."""
+    return _lib.lib().srf_dpg_mix(wl, wi, B, E, P, boxes_w, D, feats_w, C, boxes, feats, None)
+
+
+def test_dpg_mix_codes():
+    for kw in (dict(E=0), dict(E=17), dict(E=-1), dict(D=2), dict(P=0), dict(P=-1), dict(C=0), dict(B=-1)):
+        assert mix(**kw) == EINVAL, kw
+        assert mix(**kw, wl=PTR) == EINVAL, kw
+        assert mix(**{**kw, "B": min(0, kw.get("B", 0))}) == EINVAL, kw          # before the nothing-to-do answer
+    assert mix(B=0) == OK and mix(B=0, E=1, D=3, C=1) == OK and mix(B=0, E=16) == OK
+    assert mix() == EINVAL                                                       # wl is NULL; wi may be
+    for name in ("boxes_w", "feats_w", "boxes", "feats"):
+        assert mix(wl=PTR, **{name: None}) == EINVAL, name
+
+
 def test_all_are_declared_and_bound():
     assert {"srf_linear", "srf_linear_workspace_bytes", "srf_self_attention", "srf_self_attention_batched", "srf_dynconv_mid",
-            "srf_ese_gate"} <= set(_lib.SIGNATURES)
+            "srf_ese_gate", "srf_stage_tail", "srf_stage_tail_workspace_bytes", "srf_apply_deltas", "srf_dpg_mix"} <= set(_lib.SIGNATURES)
