@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "../../include/srfdet3d.h"
 
 #define SRF_WAVE 64
@@ -22,6 +24,33 @@
 
 static inline int srf_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t srf_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// A launch with more than 64 KB of dynamic LDS needs an opt-in on the kernel function, and the attribute belongs to the function
+// ON A DEVICE.  `done` is the call site's own `static bool [64]`, one flag per device for the whole list (idempotent: a race only
+// repeats the calls).  Use as SRF_LDS_OPT_IN(done, {kernel_a, bytes_a}, {kernel_b, bytes_b}): a HIP error returns as from SRF_HIP_TRY.
+struct SrfLdsFn {
+    const void *fn;
+    size_t bytes;
+    template <class F>
+    SrfLdsFn(F *f, size_t b) : fn((const void *)f), bytes(b) {}
+};
+
+static inline int srf_lds_opt_in(bool (&done)[64], std::initializer_list<SrfLdsFn> fns)
+{
+    int dev = 0;
+    SRF_HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
+    if (done[dev]) return SRF_OK;
+    for (const SrfLdsFn &f : fns) SRF_HIP_TRY(hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.bytes));
+    done[dev] = true;
+    return SRF_OK;
+}
+
+#define SRF_LDS_OPT_IN(done, ...)                                 \
+    do {                                                          \
+        const int _rc = srf_lds_opt_in(done, {__VA_ARGS__});      \
+        if (_rc != SRF_OK) return _rc;                            \
+    } while (0)
 
 // Developer A/B knobs.  Each one chooses between kernel forms that produce IDENTICAL bits; the launchers read them once per
 // process (into function-local statics), so the parity tests run each setting in its own interpreter (tests/forms.py).

@@ -981,24 +981,24 @@ extern "C" int srf_wino3x3(const float *x, int N, int H, int W, int Cin, long lo
     a.nspatial = (int)nspatial;
     a.relu = relu;
     const long long blocks = ((nspatial + 7) / 8) * 8 * a.coutBlocks;
-    int dev = 0;
+    int dev = 0;  // also for srf_cu_count below
     SRF_HIP_TRY(hipGetDevice(&dev));
-    static bool attr_set[64] = {false};
-    if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-    if (!attr_set[dev]) {
-#define WN_ATTR(L, HB) SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_k<L, HB>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES))
-        WN_ATTR(1, false);
-        WN_ATTR(2, false);
-        WN_ATTR(3, false);
-        WN_ATTR(1, true);
-        WN_ATTR(2, true);
-        WN_ATTR(3, true);
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_mixed_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES));
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_mixed_k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES));
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino3x3_mixed_k<3>, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES));
-#undef WN_ATTR
-        attr_set[dev] = true;
-    }
+    // every instance one of the launches below can pick, by tile-block shape 1 .. 3
+    static bool lds_set[64] = {false};
+    SRF_LDS_OPT_IN(lds_set,
+                   // full blocks
+                   {srf_wino3x3_k<1, false>, WN_LDS_BYTES},
+                   {srf_wino3x3_k<2, false>, WN_LDS_BYTES},
+                   {srf_wino3x3_k<3, false>, WN_LDS_BYTES},
+                   // half blocks
+                   {srf_wino3x3_k<1, true>, WN_LDS_BYTES},
+                   {srf_wino3x3_k<2, true>, WN_LDS_BYTES},
+                   {srf_wino3x3_k<3, true>, WN_LDS_BYTES},
+                   // full and half blocks in one launch
+                   {srf_wino3x3_mixed_k<1>, WN_LDS_BYTES},
+                   {srf_wino3x3_mixed_k<2>, WN_LDS_BYTES},
+                   {srf_wino3x3_mixed_k<3>, WN_LDS_BYTES});
+
     const dim3 blk(256);
     a.cb0 = 0;
     a.ncb = a.coutBlocks;

@@ -4,7 +4,7 @@
 // srfdet_head.py:1484-1525 (== :2281-2322): nn.MultiheadAttention self-attention over the proposals (+ residual +
 // LayerNorm), DynamicConv (:2633-2693), FFN, classification / regression towers, and the fused projection of the
 // LiDAR+camera RoI features (:2255-2264).  In the reference each of these is a chain of torch ops (~60 launches per
-// stage); here a stage is ~20 launches of three kernels:
+// stage); here a stage is ~20 launches of four kernels:
 //
 //   srf_linear        Y = epilogue(X W^T + b): 32x128 output tile per workgroup, 32-deep K chunks staged through the
 //                     same swizzled LDS operand images as the sparse conv (ds_read_b128 fragments, register-prefetched
@@ -17,12 +17,23 @@
 //   srf_dynconv_mid   per proposal: (49 x C)(C x d) -> LN -> ReLU -> (49 x d)(d x C) -> LN -> ReLU with the
 //                     proposal's own weights, all operands resident in LDS, v_mfma_f32_16x16x4_f32.
 //
+//   srf_stage_tail    FFN + norm3 + both towers + heads + apply_deltas of 32 proposals in one launch (srf_stage_ffn_k runs the
+//                     FFN beside it when the caller gives a workspace).
+//
+// Stated once and shared (all __forceinline__): the LayerNorm (srf_ln_stats / srf_ln_norm, rows over 4, 8, 16 or 64 lanes),
+// the row epilogue (srf_row_epilogue over ColsRegs / ColsMem), the 32 x 128 MFMA tile frame of srf_linear_k, srf_stage_ffn_k
+// and srf_stage_tail_k (srf_tile_*), and the box refinement (DeltaGeom, srf_delta_geom, srf_delta_box).
+//
 // All arithmetic is f32 (the reference is f32 and the contract is 1e-4 on box parameters; gfx950 has no xf32).
 #include "common.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+#define LIN_TM 32    // the output tile of the three f32-MFMA kernels: 32 rows x 128 columns, K in chunks of 32
+#define LIN_TN 128
+#define LIN_KC 32
 
 struct RowEpilogue {
     const float *bias;      // [N] or null
@@ -36,59 +47,71 @@ struct RowEpilogue {
     float eps1, eps2;
 };
 
-// LayerNorm over one row spread across a wave: NV values per lane (columns lane, lane+64, ...); biased variance,
-// two-pass, like torch.nn.LayerNorm
-template <int NV>
-__device__ __forceinline__ void srf_wave_layernorm(float (&v)[NV], int N, int lane, const float *g, const float *b, float eps)
+// ---------------------------------------------------------------------------------------------------------------------
+// LayerNorm (two-pass, biased variance, like torch.nn.LayerNorm), stated once for every kernel of this file.  A row of n
+// values is held by G adjacent lanes.  Each site adds up its own lane's values in its own order and hands in the partial sum
+// `s` and `sq(mean)`, its lane's partial sum of squared deviations; the G partials are combined by xor-shuffles, distances
+// G/2 -> 1 (DOWN, the whole-wave form) or 1 -> G/2 (the group forms).  The order of those adds is part of the result's bits.
+// ---------------------------------------------------------------------------------------------------------------------
+struct LnStats {
+    float mean, rstd;
+};
+
+// (maybe_undef as on __shfl_xor's own argument: without it the partial sum becomes `noundef` here and the compiler drops the
+// freeze it places in front of a shuffle, which changes the code of every site)
+template <int G, bool DOWN>
+__device__ __forceinline__ float srf_group_sum(__attribute__((maybe_undef)) float s)
+{
+#pragma unroll
+    for (int d = DOWN ? G / 2 : 1; DOWN ? d > 0 : d < G; d = DOWN ? d >> 1 : d << 1) s += __shfl_xor(s, d, 64);
+    return s;
+}
+
+template <int G, bool DOWN, class SqF>
+__device__ __forceinline__ LnStats srf_ln_stats(__attribute__((maybe_undef)) float s, int n, float eps, SqF sq)
+{
+    static_assert(G == 4 || G == 8 || G == 16 || G == 64, "lanes per row");
+    const float mean = srf_group_sum<G, DOWN>(s) / (float)n;
+    const float q = srf_group_sum<G, DOWN>(sq(mean));
+    return {mean, 1.0f / sqrtf(q / (float)n + eps)};
+}
+
+__device__ __forceinline__ float srf_ln_norm(float v, const LnStats &st, float g, float b) { return (v - st.mean) * st.rstd * g + b; }
+
+// The 8-lanes-per-row pass of the 32 x 128 tile: thread (row = tid >> 3, q = tid & 7) holds the 16 columns ch * 32 + 4 q .. + 3
+// of its row (what it writes into the operand image), the 8 threads of a row are adjacent lanes.
+__device__ __forceinline__ LnStats srf_row8_stats(const f32x4 (&v)[4], float eps)
 {
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < NV; ++i)
-        if (lane + i * 64 < N) s += v[i];
+    for (int ch = 0; ch < 4; ++ch) s += (v[ch][0] + v[ch][1]) + (v[ch][2] + v[ch][3]);
+    return srf_ln_stats<8, false>(s, LIN_TN, eps, [&](float mean) {
+        float q = 0.f;
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-    const float mean = s / (float)N;
-    float q = 0.f;
+        for (int ch = 0; ch < 4; ++ch)
 #pragma unroll
-    for (int i = 0; i < NV; ++i)
-        if (lane + i * 64 < N) {
-            const float t = v[i] - mean;
-            q += t * t;
-        }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) q += __shfl_xor(q, d, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)N + eps);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = lane + i * 64;
-        if (c < N) v[i] = (v[i] - mean) * rstd * g[c] + b[c];
-    }
+            for (int i = 0; i < 4; ++i) {
+                const float t = v[ch][i] - mean;
+                q += t * t;
+            }
+        return q;
+    });
 }
 
-template <int NV>
-__device__ __forceinline__ void srf_row_epilogue(float (&v)[NV], int N, int lane, int row, const RowEpilogue &ep)
-{
-    if (ep.bias)
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-            if (lane + i * 64 < N) v[i] += ep.bias[lane + i * 64];
-    if (ep.ln1_g) srf_wave_layernorm<NV>(v, N, lane, ep.ln1_g, ep.ln1_b, ep.eps1);
-    if (ep.relu1)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
-    if (ep.residual)
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-            if (lane + i * 64 < N) v[i] += ep.residual[(size_t)row * ep.ldr + lane + i * 64];
-    if (ep.ln2_g) srf_wave_layernorm<NV>(v, N, lane, ep.ln2_g, ep.ln2_b, ep.eps2);
-    if (ep.relu2)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
-}
+// The column vectors of a row epilogue (bias, LayerNorm gains / offsets) and the residual row, as column i of a lane
+// (c = lane + 64 i), from one of two places.  ColsMem: behind the RowEpilogue's pointers, read where they are used (NV = 16:
+// 80 floats per lane would not fit in registers).  ColsRegs: in registers, for a wave that walks several rows -- the column
+// vectors are loaded once per wave and the residual rows are fetched before the loop; read inside it, every row pays its own
+// L2 round trips (bias -> ln1 -> residual -> ln2: 16 of the 20 us of a 128 -> 128 projection at 200 rows).
+struct ColsMem {
+    const RowEpilogue &ep;
+    int row;
+    __device__ __forceinline__ float bias(int, int c) const { return ep.bias[c]; }
+    __device__ __forceinline__ float g(int k, int, int c) const { return (k ? ep.ln2_g : ep.ln1_g)[c]; }
+    __device__ __forceinline__ float b(int k, int, int c) const { return (k ? ep.ln2_b : ep.ln1_b)[c]; }
+    __device__ __forceinline__ float res(int, int c) const { return ep.residual[(size_t)row * ep.ldr + c]; }
+};
 
-// The same epilogue for a wave that walks several rows: the column vectors (bias, LayerNorm gains / offsets) are loaded once
-// per wave and the residual rows are fetched before the loop -- read inside it, every row pays its own L2 round trips
-// (bias -> ln1 -> residual -> ln2: 16 of the 20 us of a 128 -> 128 projection at 200 rows).
 template <int NV>
 struct RowVecs {
     float bias[NV], g1[NV], b1[NV], g2[NV], b2[NV];
@@ -110,59 +133,98 @@ __device__ __forceinline__ void srf_row_vecs_load(RowVecs<NV> &pv, int N, int la
 }
 
 template <int NV>
-__device__ __forceinline__ void srf_wave_layernorm_regs(float (&v)[NV], int N, int lane, const float (&g)[NV], const float (&b)[NV],
-                                                        float eps)
+struct ColsRegs {
+    const RowVecs<NV> &pv;
+    const float (&res_)[NV];
+    __device__ __forceinline__ float bias(int i, int) const { return pv.bias[i]; }
+    __device__ __forceinline__ float g(int k, int i, int) const { return k ? pv.g2[i] : pv.g1[i]; }
+    __device__ __forceinline__ float b(int k, int i, int) const { return k ? pv.b2[i] : pv.b1[i]; }
+    __device__ __forceinline__ float res(int i, int) const { return res_[i]; }
+};
+
+// LayerNorm k (0 / 1) of the epilogue over one row spread across a wave: NV values per lane (columns lane, lane + 64, ...)
+template <int NV, class Cols>
+__device__ __forceinline__ void srf_wave_layernorm(float (&v)[NV], int N, int lane, float eps, const Cols &cv, int k)
 {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
         if (lane + i * 64 < N) s += v[i];
+    const LnStats st = srf_ln_stats<64, true>(s, N, eps, [&](float mean) {
+        float q = 0.f;
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-    const float mean = s / (float)N;
-    float q = 0.f;
+        for (int i = 0; i < NV; ++i)
+            if (lane + i * 64 < N) {
+                const float t = v[i] - mean;
+                q += t * t;
+            }
+        return q;
+    });
 #pragma unroll
-    for (int i = 0; i < NV; ++i)
-        if (lane + i * 64 < N) {
-            const float t = v[i] - mean;
-            q += t * t;
-        }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) q += __shfl_xor(q, d, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)N + eps);
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-        if (lane + i * 64 < N) v[i] = (v[i] - mean) * rstd * g[i] + b[i];
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + i * 64;
+        if (c < N) v[i] = srf_ln_norm(v[i], st, cv.g(k, i, c), cv.b(k, i, c));
+    }
 }
 
-template <int NV>
-__device__ __forceinline__ void srf_row_epilogue_regs(float (&v)[NV], int N, int lane, const float (&res)[NV], const RowEpilogue &ep,
-                                                      const RowVecs<NV> &pv)
+// bias -> LayerNorm 1 -> ReLU -> + residual -> LayerNorm 2 -> ReLU on one row spread across a wave
+template <int NV, class Cols>
+__device__ __forceinline__ void srf_row_epilogue(float (&v)[NV], int N, int lane, const RowEpilogue &ep, const Cols &cv)
 {
     if (ep.bias)
 #pragma unroll
         for (int i = 0; i < NV; ++i)
-            if (lane + i * 64 < N) v[i] += pv.bias[i];
-    if (ep.ln1_g) srf_wave_layernorm_regs<NV>(v, N, lane, pv.g1, pv.b1, ep.eps1);
+            if (lane + i * 64 < N) v[i] += cv.bias(i, lane + i * 64);
+    if (ep.ln1_g) srf_wave_layernorm<NV>(v, N, lane, ep.eps1, cv, 0);
     if (ep.relu1)
 #pragma unroll
         for (int i = 0; i < NV; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
     if (ep.residual)
 #pragma unroll
         for (int i = 0; i < NV; ++i)
-            if (lane + i * 64 < N) v[i] += res[i];
-    if (ep.ln2_g) srf_wave_layernorm_regs<NV>(v, N, lane, pv.g2, pv.b2, ep.eps2);
+            if (lane + i * 64 < N) v[i] += cv.res(i, lane + i * 64);
+    if (ep.ln2_g) srf_wave_layernorm<NV>(v, N, lane, ep.eps2, cv, 1);
     if (ep.relu2)
 #pragma unroll
         for (int i = 0; i < NV; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// srf_linear
+// The tile frame of srf_linear_k, srf_stage_ffn_k and srf_stage_tail_k: 256 threads own a 32 x 128 f32 tile, wave w its
+// columns 32 w .. 32 w + 31.  Operands sit in LDS as swizzled parity images of 32-deep K chunks ([rows][32], see spconv.hip).
 // ---------------------------------------------------------------------------------------------------------------------
-#define LIN_TM 32
-#define LIN_TN 128
-#define LIN_KC 32
+// acc += A chunk (32 rows x 32) . B chunk (128 columns x 32)^T, this wave's 32 columns
+__device__ __forceinline__ void srf_tile_mma(const float *a_img, const float *b_img, f32x16 &acc)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int kh = lane >> 5, arow = lane & 31, a_swz = (arow >> 1) & 7;
+    const int bcol = wave * 32 + (lane & 31), b_swz = (bcol >> 1) & 7;
+    f32x4 af[4], bf[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        af[g] = *reinterpret_cast<const f32x4 *>(a_img + arow * 32 + (((kh << 2) + g) ^ a_swz) * 4);
+        bf[g] = *reinterpret_cast<const f32x4 *>(b_img + bcol * 32 + (((kh << 2) + g) ^ b_swz) * 4);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[j >> 2][j & 3], bf[j >> 2][j & 3], acc, 0, 0, 0);
+}
+
+__device__ __forceinline__ void srf_tile_zero(f32x16 &acc)
+{
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+}
+
+// C/D layout of the 32x32 MFMA: accumulator j of a lane is the tile's (srf_tile_row(j), srf_tile_col())
+__device__ __forceinline__ int srf_tile_row(int j) { return (j & 3) + 8 * (j >> 2) + 4 * ((threadIdx.x & 63) >> 5); }
+__device__ __forceinline__ int srf_tile_col() { return (threadIdx.x >> 6) * 32 + (threadIdx.x & 31); }
+
+// accumulators -> s_out[32][128] (row-major tile)
+__device__ __forceinline__ void srf_tile_spill(const f32x16 &acc, float (*s_out)[LIN_TN + 4])
+{
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s_out[srf_tile_row(j)][srf_tile_col()] = acc[j];
+}
 
 // 32 floats of one operand row (4 consecutive channels per call) into the swizzled parity image (see spconv.hip)
 __device__ __forceinline__ void srf_img_store(float *img, int r, int q, const f32x4 &v)
@@ -172,6 +234,40 @@ __device__ __forceinline__ void srf_img_store(float *img, int r, int q, const f3
     const f32x2 ev = {v[0], v[2]}, od = {v[1], v[3]};
     *reinterpret_cast<f32x2 *>(img + r * 32 + ((q >> 1) ^ swz) * 4 + off) = ev;
     *reinterpret_cast<f32x2 *>(img + r * 32 + ((4 + (q >> 1)) ^ swz) * 4 + off) = od;
+}
+
+// s_out[32][0 .. 128) (row-major) -> operand image (4 chunks): thread (row = tid >> 3, q = tid & 7), 4 float4 each
+__device__ __forceinline__ void srf_tile_to_image(float (*s_out)[LIN_TN + 4], float *img)
+{
+    const int r = threadIdx.x >> 3, q = threadIdx.x & 7;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(&s_out[r][ch * 32 + q * 4]);
+        srf_img_store(img + ch * 1024, r, q, v);
+    }
+}
+
+// rows row0 .. row0 + 31 of obj (R, 128) -> operand image, zeros past R
+__device__ __forceinline__ void srf_tile_load_obj(const float *__restrict__ obj, int R, int row0, float *img)
+{
+    const int r = threadIdx.x >> 3, q = threadIdx.x & 7, row = row0 + r;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (row < R) v = *reinterpret_cast<const f32x4 *>(obj + (size_t)row * LIN_TN + ch * 32 + q * 4);
+        srf_img_store(img + ch * 1024, r, q, v);
+    }
+}
+
+// s_out = relu(s_out + bias(column)); a thread visits one column: e & 127 == tid & 127 for every e of the thread
+template <class BiasF>
+__device__ __forceinline__ void srf_tile_bias_relu(float (*s_out)[LIN_TN + 4], BiasF bias)
+{
+    for (int e = threadIdx.x; e < 32 * LIN_TN; e += 256) {
+        const int r = e >> 7, c = e & (LIN_TN - 1);
+        const float v = s_out[r][c] + bias(c);
+        s_out[r][c] = v > 0.f ? v : 0.f;
+    }
 }
 
 // register-staged loads of one K chunk (branch-free: clamped addresses, validity kept in a bit mask and applied at
@@ -226,16 +322,12 @@ __global__ __launch_bounds__(256) void srf_linear_k(const float *__restrict__ X,
     const int T = (kend - kbeg + LIN_KC - 1) / LIN_KC;
 
     f32x16 acc;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    srf_tile_zero(acc);
 
     // staging: X tile 32 rows x 8 float4 = 256 (one per thread); W tile 128 rows x 8 = 1024 (four per thread)
     f32x4 rx, rw[4];
     unsigned ok = 0;
     const int xr = tid >> 3, xq = tid & 7;
-    const int kh = lane >> 5;
-    const int arow = lane & 31, a_swz = (arow >> 1) & 7;
-    const int bcol = wave * 32 + (lane & 31), b_swz = (bcol >> 1) & 7;
     if (T > 0) {
         srf_lin_load(X, M, ldx, W, N, ldw, row0, col0, kbeg, kend, xr, xq, rx, rw, ok);
         srf_lin_store(s_x[0], s_w[0], xr, xq, rx, rw, ok);
@@ -245,34 +337,26 @@ __global__ __launch_bounds__(256) void srf_linear_k(const float *__restrict__ X,
         const int buf = t & 1;
         const bool more = t + 1 < T;
         if (more) srf_lin_load(X, M, ldx, W, N, ldw, row0, col0, kbeg + (t + 1) * LIN_KC, kend, xr, xq, rx, rw, ok);
-        f32x4 af[4], bf[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            af[g] = *reinterpret_cast<const f32x4 *>(s_x[buf] + arow * 32 + (((kh << 2) + g) ^ a_swz) * 4);
-            bf[g] = *reinterpret_cast<const f32x4 *>(s_w[buf] + bcol * 32 + (((kh << 2) + g) ^ b_swz) * 4);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[j >> 2][j & 3], bf[j >> 2][j & 3], acc, 0, 0, 0);
+        srf_tile_mma(s_x[buf], s_w[buf], acc);
         if (more) srf_lin_store(s_x[buf ^ 1], s_w[buf ^ 1], xr, xq, rx, rw, ok);
         __syncthreads();
     }
 
-    // C/D layout: col = lane & 31, row = (j & 3) + 8 * (j >> 2) + 4 * (lane >> 5)
     if (partial) {  // split-K: raw partial sums, reduced by srf_rows_epilogue_k
         float *dst = partial + (size_t)split * M * N;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const int row = row0 + (j & 3) + 8 * (j >> 2) + 4 * kh, col = col0 + wave * 32 + (lane & 31);
+            const int row = row0 + srf_tile_row(j), col = col0 + srf_tile_col();
             if (row < M && col < N) dst[(size_t)row * N + col] = acc[j];
         }
         return;
     }
     if (!fuse_rows) {  // plain bias (+ReLU) epilogue straight from the accumulators
-        const int col = col0 + wave * 32 + (lane & 31);
+        const int col = col0 + srf_tile_col();
         const float b = (ep.bias && col < N) ? ep.bias[col] : 0.f;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const int row = row0 + (j & 3) + 8 * (j >> 2) + 4 * kh;
+            const int row = row0 + srf_tile_row(j);
             if (row < M && col < N) {
                 float v = acc[j] + b;
                 if (ep.relu1) v = v > 0.f ? v : 0.f;
@@ -282,8 +366,7 @@ __global__ __launch_bounds__(256) void srf_linear_k(const float *__restrict__ X,
         return;
     }
     // whole rows live in this workgroup (N <= 128): tile -> LDS, then one wave per 8 rows runs the row epilogue
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s_out[(j & 3) + 8 * (j >> 2) + 4 * kh][wave * 32 + (lane & 31)] = acc[j];
+    srf_tile_spill(acc, s_out);
     __syncthreads();
     RowVecs<2> pv;
     srf_row_vecs_load<2>(pv, N, lane, ep);
@@ -300,7 +383,7 @@ __global__ __launch_bounds__(256) void srf_linear_k(const float *__restrict__ X,
         const int r = wave * 8 + i, row = row0 + r;
         if (row < M) {
             float v[2] = {lane < N ? s_out[r][lane] : 0.f, lane + 64 < N ? s_out[r][lane + 64] : 0.f};
-            srf_row_epilogue_regs<2>(v, N, lane, res[i], ep, pv);
+            srf_row_epilogue<2>(v, N, lane, ep, ColsRegs<2>{pv, res[i]});
             if (lane < N) Y[(size_t)row * ldy + lane] = v[0];
             if (lane + 64 < N) Y[(size_t)row * ldy + lane + 64] = v[1];
         }
@@ -342,8 +425,8 @@ __global__ __launch_bounds__(256) void srf_rows_epilogue_k(const float *__restri
         }
         v[i] = c < N ? s : 0.f;
     }
-    if (NV <= 2) srf_row_epilogue_regs<NV>(v, N, lane, res, ep, pv);
-    else srf_row_epilogue<NV>(v, N, lane, row, ep);
+    if (NV <= 2) srf_row_epilogue<NV>(v, N, lane, ep, ColsRegs<NV>{pv, res});
+    else srf_row_epilogue<NV>(v, N, lane, ep, ColsMem{ep, row});
 #pragma unroll
     for (int i = 0; i < NV; ++i)
         if (lane + i * 64 < N) Y[(size_t)row * ldy + lane + i * 64] = v[i];
@@ -365,25 +448,6 @@ __global__ __launch_bounds__(256) void srf_cols_epilogue_k(const float *__restri
         if (relu) s = s > 0.f ? s : 0.f;
         Y[(size_t)row * ldy + col] = s;
     }
-}
-
-static RowEpilogue srf_make_epilogue(const float *bias, const float *ln1_g, const float *ln1_b, float eps1, int relu1,
-                                     const float *residual, int ldr, const float *ln2_g, const float *ln2_b, float eps2,
-                                     int relu2)
-{
-    RowEpilogue ep;
-    ep.bias = bias;
-    ep.ln1_g = ln1_g;
-    ep.ln1_b = ln1_b;
-    ep.residual = residual;
-    ep.ln2_g = ln2_g;
-    ep.ln2_b = ln2_b;
-    ep.ldr = ldr;
-    ep.relu1 = relu1;
-    ep.relu2 = relu2;
-    ep.eps1 = eps1;
-    ep.eps2 = eps2;
-    return ep;
 }
 
 extern "C" size_t srf_linear_workspace_bytes(int M, int N, int K)
@@ -462,7 +526,7 @@ extern "C" int srf_linear(const float *X, int M, int K, int ldx, const float *W,
     const bool rows = ln1_g || ln2_g || residual || relu2;
     if (rows && N > 1024) return SRF_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    RowEpilogue ep = srf_make_epilogue(bias, ln1_g, ln1_b, eps1, relu1, residual, ldr, ln2_g, ln2_b, eps2, relu2);
+    const RowEpilogue ep = {bias, ln1_g, ln1_b, residual, ln2_g, ln2_b, ldr, relu1, relu2, eps1, eps2};
     int nsplit = 1, kps = K;
     if (K >= 2048) {
         kps = 256;
@@ -476,7 +540,7 @@ extern "C" int srf_linear(const float *X, int M, int K, int ldx, const float *W,
     const bool two_pass = nsplit > 1 || (rows && N > LIN_TN);
     if (two_pass) {
         if (!workspace || workspace_bytes < (size_t)nsplit * M * N * sizeof(float)) return SRF_EWORKSPACE;
-        RowEpilogue none = srf_make_epilogue(nullptr, nullptr, nullptr, 0.f, 0, nullptr, 0, nullptr, nullptr, 0.f, 0);
+        const RowEpilogue none = {};
         hipLaunchKernelGGL(srf_linear_k, dim3(srf_ceil_div(N, LIN_TN), srf_ceil_div(M, LIN_TM), nsplit), dim3(256), 0, st, X, M, K,
                            ldx, W, N, ldw, Y, ldy, kps, (float *)workspace, none, 0);
         if (N <= 128)
@@ -506,9 +570,55 @@ extern "C" int srf_linear(const float *X, int M, int K, int ldx, const float *W,
 #define TAIL_C 128
 #define TAIL_MAX_TOWER 4
 
-struct DeltaGeomFwd {
-    float w[6], lo[3], ext[3], clamp;
+// apply_deltas (srfdet_head.py:1534-1625): deltas on a box with its centre in metres -> the refined box with its centre
+// normalised to [0, 1] over the point-cloud range; sin / cos / velocity are the deltas themselves.
+struct RangeGeom {
+    float lo[3], ext[3];
 };
+
+struct DeltaGeom {
+    float w[6];
+    RangeGeom range;
+    float clamp;
+};
+
+static RangeGeom srf_range_geom(const float *pc_range)
+{
+    RangeGeom g;
+    for (int i = 0; i < 3; ++i) {
+        g.lo[i] = pc_range[i];
+        g.ext[i] = pc_range[3 + i] - pc_range[i];
+    }
+    return g;
+}
+
+static DeltaGeom srf_delta_geom(const float *weights6, const float *pc_range, float scale_clamp)
+{
+    DeltaGeom g;
+    for (int i = 0; i < 6; ++i) g.w[i] = weights6[i];
+    g.range = srf_range_geom(pc_range);
+    g.clamp = scale_clamp;
+    return g;
+}
+
+// one row: delta(i), i < Dd, is the row's i-th delta as the caller holds it; divide by the weight, multiply by the size, add
+// the centre, normalise, clamp -- in that order
+template <class DeltaF>
+__device__ __forceinline__ void srf_delta_box(DeltaF delta, const float *b, int Dd, const DeltaGeom &g, float *o)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float size = expf(b[3 + i]);
+        const float ctr = (delta(i) / g.w[i]) * size + b[i];
+        float n = (ctr - g.range.lo[i]) / g.range.ext[i];
+        n = n < 0.f ? 0.f : (n > 1.f ? 1.f : n);
+        o[i] = n;
+        float ds = delta(3 + i) / g.w[3 + i];
+        ds = ds > g.clamp ? g.clamp : ds;
+        o[3 + i] = logf(expf(ds) * size);
+    }
+    for (int i = 6; i < Dd; ++i) o[i] = delta(i);
+}
 
 struct TailWeights {
     const float *w1, *b1;              // linear1: (F, C), (F)
@@ -556,84 +666,26 @@ __device__ __forceinline__ void srf_tail_commit(const TailBlock &blk, float *s_w
 // acc += src image (4 chunks of [32 rows x 32]) . s_w block (4 chunks of [128 cols x 32])^T, this wave's 32 columns
 __device__ __forceinline__ void srf_tail_mma(const float *src_img, const float *s_w, f32x16 &acc)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int kh = lane >> 5, arow = lane & 31, a_swz = (arow >> 1) & 7;
-    const int bcol = wave * 32 + (lane & 31), b_swz = (bcol >> 1) & 7;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        f32x4 af[4], bf[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            af[g] = *reinterpret_cast<const f32x4 *>(src_img + t * 1024 + arow * 32 + (((kh << 2) + g) ^ a_swz) * 4);
-            bf[g] = *reinterpret_cast<const f32x4 *>(s_w + t * (LIN_TN * 32) + bcol * 32 + (((kh << 2) + g) ^ b_swz) * 4);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[j >> 2][j & 3], bf[j >> 2][j & 3], acc, 0, 0, 0);
-    }
+    for (int t = 0; t < 4; ++t) srf_tile_mma(src_img + t * 1024, s_w + t * (LIN_TN * 32), acc);
 }
 
-__device__ __forceinline__ void srf_tail_zero(f32x16 &acc)
-{
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-}
-
-// accumulators -> s_out[32][128] (row-major tile)
-__device__ __forceinline__ void srf_tail_spill(const f32x16 &acc, float (*s_out)[LIN_TN + 4])
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kh = lane >> 5;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s_out[(j & 3) + 8 * (j >> 2) + 4 * kh][wave * 32 + (lane & 31)] = acc[j];
-}
-
-// s_out[32][0 .. 128) (row-major) -> operand image (4 chunks)
-__device__ __forceinline__ void srf_tail_to_image(float (*s_out)[LIN_TN + 4], float *img)
-{
-    const int r = threadIdx.x >> 3, q = threadIdx.x & 7;
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(&s_out[r][ch * 32 + q * 4]);
-        srf_img_store(img + ch * 1024, r, q, v);
-    }
-}
-
-// s_out[32][0 .. 128) -> LayerNorm (two-pass, biased variance, as torch) -> ReLU -> operand image, in one pass: thread
-// (row = tid >> 3, q = tid & 7) owns the 16 columns ch * 32 + 4 q .. + 3 of its row (exactly what it writes into the image),
-// the 8 threads of a row are 8 adjacent lanes and combine their partial sums with three xor-shuffles.  Replaces a per-wave
+// s_out[32][0 .. 128) -> LayerNorm -> ReLU -> operand image, in one pass over the 8-lane rows (srf_row8_*).  Replaces a per-wave
 // loop over 8 rows (two 64-lane reductions per row), a write-back to s_out, a barrier and the separate image pass.
 __device__ __forceinline__ void srf_tail_ln_relu_to_image(float (*s_out)[LIN_TN + 4], const float *g, const float *b, float eps, float *img)
 {
     const int r = threadIdx.x >> 3, q = threadIdx.x & 7;
     f32x4 v[4];
-    float s = 0.f;
 #pragma unroll
-    for (int ch = 0; ch < 4; ++ch) {
-        v[ch] = *reinterpret_cast<const f32x4 *>(&s_out[r][ch * 32 + q * 4]);
-        s += (v[ch][0] + v[ch][1]) + (v[ch][2] + v[ch][3]);
-    }
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    const float mean = s / (float)LIN_TN;
-    float qq = 0.f;
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float t = v[ch][i] - mean;
-            qq += t * t;
-        }
-    qq += __shfl_xor(qq, 1, 64);
-    qq += __shfl_xor(qq, 2, 64);
-    qq += __shfl_xor(qq, 4, 64);
-    const float rstd = 1.0f / sqrtf(qq / (float)LIN_TN + eps);
+    for (int ch = 0; ch < 4; ++ch) v[ch] = *reinterpret_cast<const f32x4 *>(&s_out[r][ch * 32 + q * 4]);
+    const LnStats st = srf_row8_stats(v, eps);
 #pragma unroll
     for (int ch = 0; ch < 4; ++ch) {
         const f32x4 gg = *reinterpret_cast<const f32x4 *>(g + ch * 32 + q * 4), bb = *reinterpret_cast<const f32x4 *>(b + ch * 32 + q * 4);
         f32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float y = (v[ch][i] - mean) * rstd * gg[i] + bb[i];
+            const float y = srf_ln_norm(v[ch][i], st, gg[i], bb[i]);
             o[i] = y > 0.f ? y : 0.f;
         }
         srf_img_store(img + ch * 1024, r, q, o);
@@ -654,51 +706,50 @@ __global__ __launch_bounds__(256) void srf_stage_ffn_k(const float *__restrict__
     float *img_h = img_obj + 4 * 1024;
     float *s_w = img_h + 4 * 1024;
     float(*s_out)[LIN_TN + 4] = reinterpret_cast<float(*)[LIN_TN + 4]>(s_w + 4 * LIN_TN * 32);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int row0 = blockIdx.x * 32, n0 = blockIdx.y * LIN_TN;
     const int C = TAIL_C;
     TailBlock blk;
     srf_tail_load(blk, w1, C, n0, F, 0);
-    {  // obj tile -> image
-        const int r = tid >> 3, q = tid & 7, row = row0 + r;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (row < R) v = *reinterpret_cast<const f32x4 *>(obj_in + (size_t)row * C + ch * 32 + q * 4);
-            srf_img_store(img_obj + ch * 1024, r, q, v);
-        }
-    }
+    srf_tile_load_obj(obj_in, R, row0, img_obj);
     const float bias = b1[n0 + (tid & (LIN_TN - 1))];  // the column this thread visits in the bias + ReLU pass below
     srf_tail_commit(blk, s_w);
     __syncthreads();
     srf_tail_load(blk, w2, F, 0, C, n0);
     f32x16 acc;
-    srf_tail_zero(acc);
+    srf_tile_zero(acc);
     srf_tail_mma(img_obj, s_w, acc);
-    srf_tail_spill(acc, s_out);
+    srf_tile_spill(acc, s_out);
     __syncthreads();
-    for (int e = tid; e < 32 * LIN_TN; e += 256) {  // e & 127 == tid & 127 for every e of this thread
-        const int r = e >> 7, c = e & (LIN_TN - 1);
-        const float v = s_out[r][c] + bias;
-        s_out[r][c] = v > 0.f ? v : 0.f;
-    }
+    srf_tile_bias_relu(s_out, [&](int) { return bias; });
     __syncthreads();
-    srf_tail_to_image(s_out, img_h);
+    srf_tile_to_image(s_out, img_h);
     srf_tail_commit(blk, s_w);
     __syncthreads();
-    srf_tail_zero(acc);
+    srf_tile_zero(acc);
     srf_tail_mma(img_h, s_w, acc);
     float *dst = partial + (size_t)blockIdx.y * R * C;
-    const int kh = lane >> 5, col = wave * 32 + (lane & 31);
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-        const int row = row0 + (j & 3) + 8 * (j >> 2) + 4 * kh;
-        if (row < R) dst[(size_t)row * C + col] = acc[j];
+        const int row = row0 + srf_tile_row(j);
+        if (row < R) dst[(size_t)row * C + srf_tile_col()] = acc[j];
+    }
+}
+
+// the first weight block of a tower: its first layer, or its head when the tower has no layers
+__device__ __forceinline__ void srf_tail_load_tower(TailBlock &blk, const TailWeights &tw, int tower)
+{
+    if (tower == 0) {
+        if (tw.n_cls > 0) srf_tail_load(blk, tw.cls_w[0], TAIL_C, 0, TAIL_C, 0);
+        else srf_tail_load(blk, tw.wl, TAIL_C, 0, tw.ncls, 0);
+    } else {
+        if (tw.n_reg > 0) srf_tail_load(blk, tw.reg_w[0], TAIL_C, 0, TAIL_C, 0);
+        else srf_tail_load(blk, tw.wd, TAIL_C, 0, tw.Dd, 0);
     }
 }
 
 __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict__ obj_in, int R, TailWeights tw,
-                                                      const float *__restrict__ boxes_m, DeltaGeomFwd g,
+                                                      const float *__restrict__ boxes_m, DeltaGeom g,
                                                       float *__restrict__ obj_out, float *__restrict__ logits,
                                                       float *__restrict__ pred, const float *__restrict__ partial)
 {
@@ -724,13 +775,7 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
     float *p_bl = p_tw + 4 * TAIL_MAX_TOWER * C, *p_bd = p_bl + 32;
     TailBlock blk;
     if (!partial) srf_tail_load(blk, tw.w1, C, 0, F, 0);
-    else if (first_tower == 0) {
-        if (tw.n_cls > 0) srf_tail_load(blk, tw.cls_w[0], C, 0, C, 0);
-        else srf_tail_load(blk, tw.wl, C, 0, tw.ncls, 0);
-    } else {
-        if (tw.n_reg > 0) srf_tail_load(blk, tw.reg_w[0], C, 0, C, 0);
-        else srf_tail_load(blk, tw.wd, C, 0, tw.Dd, 0);
-    }
+    else srf_tail_load_tower(blk, tw, first_tower);
     for (int e = tid; e < F; e += 256) p_b1[e] = tw.b1[e];
     if (tid < C) {
         p_b2[tid] = tw.b2[tid];
@@ -749,43 +794,25 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
         p_bl[i] = i < tw.ncls ? tw.bl[i] : 0.f;
         p_bd[i] = i < tw.Dd ? tw.bd[i] : 0.f;
     }
-    if (!partial) {  // obj tile -> image (the FFN's operand; with `partial` the FFN ran elsewhere)
-        const int r = tid >> 3, q = tid & 7, row = row0 + r;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (row < R) v = *reinterpret_cast<const f32x4 *>(obj_in + (size_t)row * C + ch * 32 + q * 4);
-            srf_img_store(img_obj + ch * 1024, r, q, v);
-        }
-    }
+    if (!partial) srf_tile_load_obj(obj_in, R, row0, img_obj);  // the FFN's operand; with `partial` the FFN ran elsewhere
     f32x16 acc, acc2;
-    srf_tail_zero(acc2);
+    srf_tile_zero(acc2);
     // ---- FFN, one 128-wide slice of the hidden layer at a time: h = relu(obj W1[n0:n0+128]^T + b1); acc2 += h W2[:, n0:]^T
     for (int n0 = 0; n0 < (partial ? 0 : F); n0 += LIN_TN) {
         srf_tail_commit(blk, s_w);                 // W1 slice
         __syncthreads();
         srf_tail_load(blk, tw.w2, F, 0, C, n0);    // W2 k-block, in flight during the MFMAs below
-        srf_tail_zero(acc);
+        srf_tile_zero(acc);
         srf_tail_mma(img_obj, s_w, acc);
-        srf_tail_spill(acc, s_out);
+        srf_tile_spill(acc, s_out);
         __syncthreads();
-        for (int e = tid; e < 32 * LIN_TN; e += 256) {
-            const int r = e >> 7, c = e & (LIN_TN - 1);
-            const float v = s_out[r][c] + p_b1[n0 + c];
-            s_out[r][c] = v > 0.f ? v : 0.f;
-        }
+        srf_tile_bias_relu(s_out, [&](int c) { return p_b1[n0 + c]; });
         __syncthreads();
-        srf_tail_to_image(s_out, img_h);
+        srf_tile_to_image(s_out, img_h);
         srf_tail_commit(blk, s_w);                 // W2 k-block (all waves are past the MFMAs that read s_w)
         __syncthreads();
         if (n0 + LIN_TN < F) srf_tail_load(blk, tw.w1, C, n0 + LIN_TN, F, 0);
-        else if (first_tower == 0) {
-            if (tw.n_cls > 0) srf_tail_load(blk, tw.cls_w[0], C, 0, C, 0);
-            else srf_tail_load(blk, tw.wl, C, 0, tw.ncls, 0);
-        } else {
-            if (tw.n_reg > 0) srf_tail_load(blk, tw.reg_w[0], C, 0, C, 0);
-            else srf_tail_load(blk, tw.wd, C, 0, tw.Dd, 0);
-        }
+        else srf_tail_load_tower(blk, tw, first_tower);
         srf_tail_mma(img_h, s_w, acc2);
         __syncthreads();
     }
@@ -833,37 +860,20 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
                 for (int i = 0; i < 4; ++i) v[ch][i] = __fadd_rn(v[ch][i], t[ch][i]);
         }
         __syncthreads();  // the bias / LayerNorm vectors in s_par are complete
-        float sm = 0.f;
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) {
             const f32x4 bb = *reinterpret_cast<const f32x4 *>(p_b2 + ch * 32 + q * 4);
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[ch][i] = live ? (v[ch][i] + bb[i]) + rsv[ch][i] : bb[i];
-            sm += (v[ch][0] + v[ch][1]) + (v[ch][2] + v[ch][3]);
         }
-        sm += __shfl_xor(sm, 1, 64);
-        sm += __shfl_xor(sm, 2, 64);
-        sm += __shfl_xor(sm, 4, 64);
-        const float mean = sm / (float)TAIL_C;
-        float qq = 0.f;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float t = v[ch][i] - mean;
-                qq += t * t;
-            }
-        qq += __shfl_xor(qq, 1, 64);
-        qq += __shfl_xor(qq, 2, 64);
-        qq += __shfl_xor(qq, 4, 64);
-        const float rstd = 1.0f / sqrtf(qq / (float)TAIL_C + tw.eps_n3);
+        const LnStats st = srf_row8_stats(v, tw.eps_n3);
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) {
             const f32x4 gg = *reinterpret_cast<const f32x4 *>(p_n3g + ch * 32 + q * 4), bb = *reinterpret_cast<const f32x4 *>(p_n3b + ch * 32 + q * 4);
             f32x4 o = {0.f, 0.f, 0.f, 0.f};
             if (live) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = (v[ch][i] - mean) * rstd * gg[i] + bb[i];
+                for (int i = 0; i < 4; ++i) o[i] = srf_ln_norm(v[ch][i], st, gg[i], bb[i]);
                 if (first_tower == 0) *reinterpret_cast<f32x4 *>(obj_out + (size_t)row * C + ch * 32 + q * 4) = o;
             }
             srf_img_store(img_obj + ch * 1024, r, q, o);
@@ -876,7 +886,7 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
         res[i][0] = row < R ? obj_in[(size_t)row * C + lane] : 0.f;
         res[i][1] = row < R ? obj_in[(size_t)row * C + lane + 64] : 0.f;
     }
-    srf_tail_spill(acc2, s_out);
+    srf_tile_spill(acc2, s_out);
     __syncthreads();
     {
         RowEpilogue ep = {p_b2, nullptr, nullptr, obj_in, p_n3g, p_n3b, C, 0, 0, 0.f, tw.eps_n3};
@@ -888,7 +898,7 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
             const int row = row0 + r;
             float v[2] = {s_out[r][lane], s_out[r][lane + 64]};
             if (row < R) {
-                srf_row_epilogue_regs<2>(v, C, lane, res[i], ep, pv);
+                srf_row_epilogue<2>(v, C, lane, ep, ColsRegs<2>{pv, res[i]});
                 if (first_tower == 0) {
                     obj_out[(size_t)row * C + lane] = v[0];
                     obj_out[(size_t)row * C + lane + 64] = v[1];
@@ -901,7 +911,7 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
         }
     }
     __syncthreads();
-    srf_tail_to_image(s_out, img_obj);  // img_obj now holds obj2, the input of both towers
+    srf_tile_to_image(s_out, img_obj);  // img_obj now holds obj2, the input of both towers
     }
     // ---- towers ---------------------------------------------------------------------------------------------------------
     for (int tower = first_tower; tower <= last_tower; ++tower) {
@@ -914,13 +924,10 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
             // next block: the next layer of this tower, its head, or the first block of the other tower
             if (l + 1 < nl) srf_tail_load(blk, tower == 0 ? tw.cls_w[l + 1] : tw.reg_w[l + 1], C, 0, C, 0);
             else if (l + 1 == nl) srf_tail_load(blk, tower == 0 ? tw.wl : tw.wd, C, 0, N, 0);
-            else if (tower == 0 && last_tower == 1) {
-                if (tw.n_reg > 0) srf_tail_load(blk, tw.reg_w[0], C, 0, C, 0);
-                else srf_tail_load(blk, tw.wd, C, 0, tw.Dd, 0);
-            }
-            srf_tail_zero(acc);
+            else if (tower == 0 && last_tower == 1) srf_tail_load_tower(blk, tw, 1);
+            srf_tile_zero(acc);
             srf_tail_mma(src, s_w, acc);
-            srf_tail_spill(acc, s_out);
+            srf_tile_spill(acc, s_out);
             __syncthreads();
             if (l < nl) {
                 const float *pg = p_tw + (2 * TAIL_MAX_TOWER * tower + 2 * l) * C;
@@ -933,19 +940,7 @@ __global__ __launch_bounds__(256) void srf_stage_tail_k(const float *__restrict_
                 }
             } else if (tid < 32 && row0 + tid < R) {
                 const int row = row0 + tid;
-                const float *b = boxes_m + (size_t)row * N;
-                float *o = pred + (size_t)row * N;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const float size = expf(b[3 + i]);
-                    const float ctr = ((s_out[tid][i] + p_bd[i]) / g.w[i]) * size + b[i];
-                    float n = (ctr - g.lo[i]) / g.ext[i];
-                    o[i] = n < 0.f ? 0.f : (n > 1.f ? 1.f : n);
-                    float ds = (s_out[tid][3 + i] + p_bd[3 + i]) / g.w[3 + i];
-                    ds = ds > g.clamp ? g.clamp : ds;
-                    o[3 + i] = logf(expf(ds) * size);
-                }
-                for (int i = 6; i < N; ++i) o[i] = s_out[tid][i] + p_bd[i];
+                srf_delta_box([&](int i) { return s_out[tid][i] + p_bd[i]; }, boxes_m + (size_t)row * N, N, g, pred + (size_t)row * N);
             }
             __syncthreads();
         }
@@ -1151,19 +1146,16 @@ __global__ __launch_bounds__(256) void srf_dynconv_mid_k(const float *__restrict
             v[i] = s_x1[row * (D + 1) + part + i * 4];
             s += v[i];
         }
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        const float mean = s / (float)D;
-        float qv = 0.f;
+        const LnStats st = srf_ln_stats<4, false>(s, D, eps1, [&](float mean) {
+            float qv = 0.f;
 #pragma unroll
-        for (int i = 0; i < D / 4; ++i) qv += (v[i] - mean) * (v[i] - mean);
-        qv += __shfl_xor(qv, 1, 64);
-        qv += __shfl_xor(qv, 2, 64);
-        const float rstd = 1.0f / sqrtf(qv / (float)D + eps1);
+            for (int i = 0; i < D / 4; ++i) qv += (v[i] - mean) * (v[i] - mean);
+            return qv;
+        });
 #pragma unroll
         for (int i = 0; i < D / 4; ++i) {
             const int c = part + i * 4;
-            const float y = (v[i] - mean) * rstd * g1[c] + b1[c];
+            const float y = srf_ln_norm(v[i], st, g1[c], b1[c]);
             s_x1[row * (D + 1) + c] = (row < S && y > 0.f) ? y : 0.f;
         }
     }
@@ -1185,21 +1177,18 @@ __global__ __launch_bounds__(256) void srf_dynconv_mid_k(const float *__restrict
             float s = 0.f;
 #pragma unroll
             for (int t = 0; t < C / 16; ++t) s += acc[t][j];
+            const LnStats st = srf_ln_stats<16, false>(s, C, eps2, [&](float mean) {
+                float qv = 0.f;
 #pragma unroll
-            for (int dd = 1; dd < 16; dd <<= 1) s += __shfl_xor(s, dd, 64);
-            const float mean = s / (float)C;
-            float qv = 0.f;
-#pragma unroll
-            for (int t = 0; t < C / 16; ++t) qv += (acc[t][j] - mean) * (acc[t][j] - mean);
-#pragma unroll
-            for (int dd = 1; dd < 16; dd <<= 1) qv += __shfl_xor(qv, dd, 64);
-            const float rstd = 1.0f / sqrtf(qv / (float)C + eps2);
+                for (int t = 0; t < C / 16; ++t) qv += (acc[t][j] - mean) * (acc[t][j] - mean);
+                return qv;
+            });
             const int row = wave * 16 + lq * 4 + j;
             if (row < S) {
 #pragma unroll
                 for (int t = 0; t < C / 16; ++t) {
                     const int c = t * 16 + l15;
-                    const float y = (acc[t][j] - mean) * rstd * g2[c] + b2[c];
+                    const float y = srf_ln_norm(acc[t][j], st, g2[c], b2[c]);
                     out[((size_t)r * S + row) * C + c] = y > 0.f ? y : 0.f;
                 }
             }
@@ -1221,15 +1210,8 @@ extern "C" int srf_dynconv_mid(const float *F, const float *params, int R, int S
                            b2, eps2, out);
     } else if (C == 256 && D == 64) {
         const size_t sh = sizeof(float) * (64 * 257 + 256 * 65 + 64 * 65);
-        int dev = 0;
-        SRF_HIP_TRY(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-        static bool attr_set[64] = {false};
-        if (!attr_set[dev]) {  // > 64 KB of dynamic LDS needs the opt-in, per device (idempotent; a race only repeats the call)
-            SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_dynconv_mid_k<256, 64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)sh));
-            attr_set[dev] = true;
-        }
+        static bool lds_set[64] = {false};
+        SRF_LDS_OPT_IN(lds_set, {srf_dynconv_mid_k<256, 64>, sh});
         hipLaunchKernelGGL(HIP_KERNEL_NAME(srf_dynconv_mid_k<256, 64>), dim3(R), dim3(256), sh, st, F, params, S, g1, b1, eps1, g2,
                            b2, eps2, out);
     } else {
@@ -1243,29 +1225,13 @@ extern "C" int srf_dynconv_mid(const float *F, const float *params, int R, int S
 // srf_apply_deltas (srfdet_head.py:1534-1625): deltas (R, Dd) on boxes (R, Dd) with centres in metres -> refined boxes
 // with centres normalised to [0,1]; sin/cos/velocity copied from the deltas.
 // ---------------------------------------------------------------------------------------------------------------------
-struct DeltaGeom {
-    float w[6], lo[3], ext[3], clamp;
-};
-
 __global__ __launch_bounds__(128) void srf_apply_deltas_k(const float *__restrict__ deltas, const float *__restrict__ boxes,
                                                         int R, int Dd, DeltaGeom g, float *__restrict__ out)
 {
     const int r = blockIdx.x * 128 + threadIdx.x;
     if (r >= R) return;
-    const float *d = deltas + (size_t)r * Dd, *b = boxes + (size_t)r * Dd;
-    float *o = out + (size_t)r * Dd;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float size = expf(b[3 + i]);
-        const float ctr = (d[i] / g.w[i]) * size + b[i];
-        float n = (ctr - g.lo[i]) / g.ext[i];
-        n = n < 0.f ? 0.f : (n > 1.f ? 1.f : n);
-        o[i] = n;
-        float ds = d[3 + i] / g.w[3 + i];
-        ds = ds > g.clamp ? g.clamp : ds;
-        o[3 + i] = logf(expf(ds) * size);
-    }
-    for (int i = 6; i < Dd; ++i) o[i] = d[i];
+    const float *d = deltas + (size_t)r * Dd;
+    srf_delta_box([&](int i) { return d[i]; }, boxes + (size_t)r * Dd, Dd, g, out + (size_t)r * Dd);
 }
 
 extern "C" size_t srf_stage_tail_workspace_bytes(int R, int C, int F)
@@ -1299,25 +1265,12 @@ extern "C" int srf_stage_tail(const float *obj_in, int R, int C, int F, const fl
     }
     tw.wl = wl, tw.bl = bl, tw.wd = wd, tw.bd = bd;
     tw.F = F, tw.n_cls = n_cls, tw.n_reg = n_reg, tw.ncls = ncls, tw.Dd = Dd;
-    DeltaGeomFwd g;
-    for (int i = 0; i < 6; ++i) g.w[i] = weights6[i];
-    for (int i = 0; i < 3; ++i) {
-        g.lo[i] = pc_range[i];
-        g.ext[i] = pc_range[3 + i] - pc_range[i];
-    }
-    g.clamp = scale_clamp;
+    const DeltaGeom g = srf_delta_geom(weights6, pc_range, scale_clamp);
     const size_t sh = sizeof(float) * (4 * 1024 + 4 * 1024 + 4 * LIN_TN * 32 + 32 * (LIN_TN + 4) + 4 * LIN_TN + 3 * TAIL_C +
                                        4 * TAIL_MAX_TOWER * TAIL_C + 64);  // 125 KB
     const size_t sh_ffn = sizeof(float) * (4 * 1024 + 4 * 1024 + 4 * LIN_TN * 32 + 32 * (LIN_TN + 4));  // 113 KB
-    int dev = 0;
-    SRF_HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-    static bool attr_set[64] = {false};
-    if (!attr_set[dev]) {  // > 64 KB of dynamic LDS needs the opt-in (per device)
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_stage_tail_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_stage_ffn_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_ffn));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {false};
+    SRF_LDS_OPT_IN(lds_set, {srf_stage_tail_k, sh}, {srf_stage_ffn_k, sh_ffn});
     const float *partial = nullptr;
     if (workspace) {  // FFN split over its hidden slices (srf_stage_ffn_k); without a workspace the tail kernel runs it in line
         if (workspace_bytes < srf_stage_tail_workspace_bytes(R, C, F)) return SRF_EWORKSPACE;
@@ -1337,13 +1290,7 @@ extern "C" int srf_apply_deltas(const float *deltas, const float *boxes, int R, 
     if (R < 0 || Dd < 8 || !weights6 || !pc_range) return SRF_EINVAL;
     if (R == 0) return SRF_OK;
     if (!deltas || !boxes || !out) return SRF_EINVAL;
-    DeltaGeom g;
-    for (int i = 0; i < 6; ++i) g.w[i] = weights6[i];
-    for (int i = 0; i < 3; ++i) {
-        g.lo[i] = pc_range[i];
-        g.ext[i] = pc_range[3 + i] - pc_range[i];
-    }
-    g.clamp = scale_clamp;
+    const DeltaGeom g = srf_delta_geom(weights6, pc_range, scale_clamp);
     hipLaunchKernelGGL(srf_apply_deltas_k, dim3(srf_ceil_div(R, 128)), dim3(128), 0, (hipStream_t)stream, deltas, boxes, R, Dd, g,
                        out);
     SRF_LAUNCH_CHECK();
@@ -1357,12 +1304,8 @@ extern "C" int srf_apply_deltas(const float *deltas, const float *boxes, int R, 
 // (centres * extent + lo), torch.sigmoid, denormalize_bbox (exp, atan2, cat) and the z shift are 12 launches of ~5 us as
 // torch ops.  Same operations in the same order (multiply, then add; h * 0.5 subtracted).
 // ---------------------------------------------------------------------------------------------------------------------
-struct DecodeGeom {
-    float lo[3], ext[3];
-};
-
 __global__ __launch_bounds__(128) void srf_decode_boxes_k(const float *__restrict__ logits, const float *__restrict__ pred, int R,
-                                                        int ncls, int Dd, DecodeGeom g, float *__restrict__ scores,
+                                                        int ncls, int Dd, RangeGeom g, float *__restrict__ scores,
                                                         float *__restrict__ boxes)
 {
     const int r = blockIdx.x * 128 + threadIdx.x;
@@ -1389,11 +1332,7 @@ extern "C" int srf_decode_boxes(const float *logits, const float *pred, int R, i
     if (R < 0 || ncls <= 0 || Dd < 8 || !pc_range) return SRF_EINVAL;
     if (R == 0) return SRF_OK;
     if (!logits || !pred || !scores || !boxes) return SRF_EINVAL;
-    DecodeGeom g;
-    for (int i = 0; i < 3; ++i) {
-        g.lo[i] = pc_range[i];
-        g.ext[i] = pc_range[3 + i] - pc_range[i];
-    }
+    const RangeGeom g = srf_range_geom(pc_range);
     hipLaunchKernelGGL(srf_decode_boxes_k, dim3(srf_ceil_div(R, 128)), dim3(128), 0, (hipStream_t)stream, logits, pred, R, ncls, Dd, g,
                        scores, boxes);
     SRF_LAUNCH_CHECK();

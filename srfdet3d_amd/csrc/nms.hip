@@ -388,14 +388,8 @@ extern "C" int srf_nms_select(const float *boxes, const float *scores, int n, in
     const int P = srf_sel_pow2(n * C);
     const size_t sh = (size_t)P * 8;
     if (sh > 64 * 1024) {
-        int dev = 0;
-        SRF_HIP_TRY(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-        static bool attr_set[64] = {false};  // the attribute belongs to the function ON A DEVICE
-        if (!attr_set[dev]) {
-            SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_nms_select_k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            attr_set[dev] = true;
-        }
+        static bool lds_set[64] = {false};
+        SRF_LDS_OPT_IN(lds_set, {srf_nms_select_k, 128 * 1024});
     }
     hipLaunchKernelGGL(srf_nms_select_k, dim3(1), dim3(SRF_SEL_THREADS), sh, (hipStream_t)stream, boxes, scores, n, C, D, score_thr, L, P,
                        cand, top_s, cls, bev, m_out);

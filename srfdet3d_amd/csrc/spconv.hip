@@ -1165,15 +1165,8 @@ extern "C" int srf_spconv_fwd_packed(const float *in, int A_in, int Cin, const f
     if (rc != SRF_OK || A_out == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (layout == SRF_PACKED_W32) {
-        int dev = 0;
-        SRF_HIP_TRY(hipGetDevice(&dev));
-        static bool attr_set[64] = {false};
-        if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-        if (!attr_set[dev]) {
-            SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_spconv_w32_k<32>, hipFuncAttributeMaxDynamicSharedMemorySize, SRF_KMAX * 32 * 32 * 4));
-            SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_spconv_w32_k<16>, hipFuncAttributeMaxDynamicSharedMemorySize, SRF_KMAX * 16 * 32 * 4));
-            attr_set[dev] = true;
-        }
+        static bool lds_set[64] = {false};
+        SRF_LDS_OPT_IN(lds_set, {srf_spconv_w32_k<32>, SRF_KMAX * 32 * 32 * 4}, {srf_spconv_w32_k<16>, SRF_KMAX * 16 * 32 * 4});
         // `tiles` of a 32-channel layer = the plan of srf_spconv_order_build (NULL: rows in their own order)
         const unsigned grid32 = tiles ? (unsigned)(srf_ord_pad(A_out) / 256) : (unsigned)srf_ceil_div(A_out, 256);
         if (Cin == 32)

@@ -576,15 +576,8 @@ static int w43_launch_xform(const W43Args &a, hipStream_t stream)
 
 static int w43_launch_mm(const W43Args &a, hipStream_t stream)
 {
-    int dev = 0;
-    SRF_HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return SRF_EUNSUPPORTED;
-    static bool attr_set[64] = {false};
-    if (!attr_set[dev]) {
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino43_mm_k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, W43_X_BYTES));
-        SRF_HIP_TRY(hipFuncSetAttribute((const void *)srf_wino43_mm_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, W43_X1_BYTES));
-        attr_set[dev] = true;
-    }
+    static bool lds_set[64] = {false};
+    SRF_LDS_OPT_IN(lds_set, {srf_wino43_mm_k<2>, W43_X_BYTES}, {srf_wino43_mm_k<1>, W43_X1_BYTES});
     const long long tb8 = (((long long)(a.ntb - a.tb0) + 7) / 8) * 8;
     static const int force_nb = srf_knob("SRF_W43_NB", 0);
     // 64-channel blocks at one workgroup per CU read half the operand bytes per FLOP; 32-channel halves at two per CU hide each

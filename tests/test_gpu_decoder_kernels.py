@@ -73,10 +73,11 @@ def test_self_attention_batched_equals_the_per_sample_launches(dev):
     torch.testing.assert_close(got, want, rtol=1e-4, atol=2e-5)
 
 
+@pytest.mark.parametrize("R", [1, 50])
+@pytest.mark.parametrize("S", [1, 49, 64])   # one row, the RoI grid of the configs, every row of the padded tile
 @pytest.mark.parametrize("C,D", [(128, 32), (256, 64)])
-def test_dynconv_mid_matches_torch(dev, C, D):
+def test_dynconv_mid_matches_torch(dev, C, D, S, R):
     g = torch.Generator().manual_seed(C)
-    R, S = 50, 49
     feats = torch.randn(R, S, C, generator=g).to(dev)
     params = (torch.randn(R, 2 * C * D, generator=g) * 0.1).to(dev)
     n1, n2 = _ln(D, dev, g), _ln(C, dev, g)
