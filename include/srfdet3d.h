@@ -780,7 +780,9 @@ int srf_conv1x1_nhwc_pooled(const float *x, int N, long long HW, int K, long lon
  * path (VoVNet stem_3, vovnet.py stem; the first layer of SECONDCustom's later blocks, second_custom.py:41-52; the extra levels
  * of the BEV FPN) -- deterministic k-ordered fma chains where MIOpen's channels-last choice is an atomic split-K kernel.
  * W_packed = srf_conv1x1_nhwc_pack_weights(W reordered to (Cout, kh * kw * Cin), tap slowest).  Cin % 32 == 0, the input
- * tensor below 2 GiB.  y: (N, Ho, Wo, y_ld), Ho = (H + 2 pad - kh) / stride + 1.
+ * tensor below 2 GiB.  y: (N, Ho, Wo, y_ld), Ho = floor((H + 2 pad - kh) / stride) + 1; any kh, kw, stride > 0 and pad >= 0 (kh != kw,
+ * pad >= k and stride > k included).  A kernel larger than the padded map (H + 2 pad < kh or W + 2 pad < kw) has no output pixel and
+ * is SRF_EINVAL whatever the stride, here and in srf_conv_gemm_nhwc_split / srf_conv_gemm_nhwc_bf16.
  * srf_stem_conv_nchw: Conv2d(Cin <= 4, 64, 3, stride 2, padding 1) + scale / shift + ReLU from NCHW images to channels-last
  * (VoVNet stem_1 on the 6 camera views); Wt is the (64, Cin, 3, 3) weight. */
 int srf_conv_gemm_nhwc(const float *x, int N, int H, int W, int Cin, long long x_ld, const float *W_packed, int Cout, int kh,

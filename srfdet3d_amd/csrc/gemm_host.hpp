@@ -75,9 +75,13 @@ static inline int srf_gemm_check_conv(const SrfGemmFamily &f, int N, int H, int 
     if (N == 0) return SRF_OK;
     if (!x || !W_packed || !y) return SRF_EINVAL;
     if ((Cin & 31) || (x_ld & 3) || ((uintptr_t)x & 15) || ((uintptr_t)W_packed & 15)) return SRF_EUNSUPPORTED;
-    *Ho = (H + 2 * pad - kh) / stride + 1;
-    *Wo = (W + 2 * pad - kw) / stride + 1;
-    if (*Ho <= 0 || *Wo <= 0) return SRF_EINVAL;
+    // a kernel larger than the padded map has no output pixel.  Asked of the sizes, not of Ho: C's division rounds towards zero, so
+    // (H + 2 pad - kh) / stride + 1 is 1 for a numerator of -1 and a stride >= 2, where the floor division of Conv2d gives 0
+    if ((long long)H + 2ll * pad < kh || (long long)W + 2ll * pad < kw) return SRF_EINVAL;
+    const long long ho = ((long long)H + 2ll * pad - kh) / stride + 1, wo = ((long long)W + 2ll * pad - kw) / stride + 1;
+    if (ho >= (1ll << 31) || wo >= (1ll << 31)) return SRF_EUNSUPPORTED;   // a padding of 2^30 and more
+    *Ho = (int)ho;
+    *Wo = (int)wo;
     *x_bytes = (long long)N * H * W * x_ld * 4;
     if (*x_bytes >= (1ll << 31) || (f.y_range && y_ld * f.tile_rows * 4 >= (1ll << 31))) return SRF_EUNSUPPORTED;
     return SRF_OK;

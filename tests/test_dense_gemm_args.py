@@ -87,6 +87,8 @@ SINGLE = [
     (("topdown",), dict(N=2, Ht=1024, Wt=1024, top_ld=1024), EUNSUPPORTED),
     (("conv",), dict(N=64, H=512, W=512, K=32, x_ld=32), EUNSUPPORTED),     # 2 GiB of input
     (("conv",), dict(H=2, W=2, pad=0, stride=1), EINVAL),                   # no output pixel
+    (("conv",), dict(H=2, W=2, pad=0, stride=2), EINVAL),                   # the same where C's division gives (2 - 3) / 2 + 1 = 1
+    (("conv",), dict(kh=1, kw=19, stride=3), EINVAL),                       # a 1 x 19 kernel on a padded width of 18
 ]
 
 
